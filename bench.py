@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: query-points x frames / second of the multi-view tracking forward path.
 
-    python bench.py --gpus 1 --steps 10 --warmup 2 [--config c3|c2|c5shard]
+    python bench.py --gpus 1 --steps 10 --warmup 2 [--config c3|c2|c5shard] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -14,7 +14,9 @@ frames are encoded once across the node: the V x T images are cut evenly across 
 image list), each rank encodes its run into its slot of the level-0 store and the slots are all-gathered in place over
 RCCL/xGMI before the refinement loop, which contains no collective.
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live for the HBM-bound gather-dot correlation kernel with HIP events on
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline fields (`value`,
+`ms_per_step`, ...); `--dump-outputs DIR` also writes the last timed step's results as .npy files.  `--full` adds the rest, each
+figure under its own key: `roofline` is measured live for the HBM-bound gather-dot correlation kernel with HIP events on
 the launch stream; `roofline_mfma` gives the matrix-core fraction of the two MFMA-bound stages (updater transformer, CNN
 encoder; flops recomputed from the shapes, HIP events around every call); `cpu_baseline` times the CPU oracle (a port of the
 reference's algorithm, its CPU fallback kNN) on a bounded sample of the same workload on this host.
@@ -160,6 +162,25 @@ def two_clips_in_flight(model, a, args, MVTracker, synth, dev, V, T, H, W, Nq, c
                     "not the headline value: the reference forward is batch 1"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: the result dict of the last timed step (what a caller of the path receives: traj_e (1,T,N,3), vis_e (1,T,N),
+    feat_init (1,S,N,C)) as float32 <path>/<name>.npy.  Above 64 MB in all, the same seeded sample of the queries (axis 2 of every
+    array) is kept from each, in query order."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: res[k].detach().float().cpu().numpy() for k in ("traj_e", "vis_e", "feat_init")}
+    total = sum(v.nbytes for v in arrs.values())
+    n = arrs["traj_e"].shape[2]
+    if total > DUMP_LIMIT_BYTES:
+        keep = max(1, int(n * DUMP_LIMIT_BYTES / total))
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrs = {k: np.ascontiguousarray(v[:, :, idx]) for k, v in arrs.items()}
+    for k, v in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -171,19 +192,30 @@ def main():
     ap.add_argument("--size", type=int)
     ap.add_argument("--queries", type=int, help="queries per GPU")
     ap.add_argument("--iters", type=int, default=4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, measure the roofline of the correlation kernel (HIP events around every launch "
+                         "in the timed steps, calibration launches after them), the MFMA fraction of updater / encoder and the CPU-oracle "
+                         "baseline; without it a run only sets up, warms up, times the steps and prints the headline fields")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step returned (traj_e, vis_e, feat_init) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all (a seeded sample of the queries beyond that); rank 0's shard when N > 1")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU-oracle baseline")
     ap.add_argument("--precision", choices=["fp32", "bf16x3", "bf16"],
                     help="matrix-core arithmetic of convs/linears (default: the config's dtype; BASELINE.json quotes C3 in bf16)")
     ap.add_argument("--cpu-hw", type=int, default=0)
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--no-corr-calibration", action="store_true",
-                    help="skip the back-to-back calibration launches of the correlation kernel after the timed region (use under rocprofv3: "
-                         "the roofline kernel's row of the kernel statistics then holds the in-situ launches only)")
+                    help="(--full) skip the back-to-back calibration launches of the correlation kernel after the timed region (use under "
+                         "rocprofv3: the roofline kernel's row of the kernel statistics then holds the in-situ launches only)")
     ap.add_argument("--clips-in-flight", type=int, default=1, choices=[1, 2],
-                    help="2: AFTER the headline measurement, additionally time two independent clips in flight (two model objects, two "
-                         "host threads, two streams) and print it as the separate field `throughput_two_clips` (never `value`: the "
-                         "reference forward is batch 1)")
+                    help="2 (needs --full): AFTER the headline measurement, additionally time two independent clips in flight (two model "
+                         "objects, two host threads, two streams) and print it as the separate field `throughput_two_clips` (never "
+                         "`value`: the reference forward is batch 1)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.clips_in_flight == 2 and not args.full:
+        ap.error("--clips-in-flight 2 is a --full measurement")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -216,8 +248,8 @@ def main():
     a = {k: torch.from_numpy(v).to(dev) for k, v in clip.items()}
     runner = ShardedTracker(model)
 
-    # live timing with HIP events on the launch stream (torch events record on the current stream, which is the launch stream):
-    # every launch of the correlation kernel, every updater call, every encoder chunk
+    # --full: live timing with HIP events on the launch stream (torch events record on the current stream, which is the launch
+    # stream): every launch of the correlation kernel, every updater call, every encoder chunk.  A plain run installs none of it.
     corr_ev, upd_ev, enc_ev = [], [], []
     timing = {"on": False}
     real_corr, real_upd, real_enc = hip.corr_gather_dot, model._update_former, model._encode
@@ -238,11 +270,13 @@ def main():
             return r
         return f
 
-    hip.corr_gather_dot = timed(real_corr, corr_ev, lambda *c, **k: c[7] * c[8])          # rows = N * S
-    # (bf16 mode runs everything after the correlation -- token assembly, updater, flow head, track update -- as ONE library call)
-    hip.updateformer_forward_tokens = timed(hip.updateformer_forward_tokens, upd_ev, lambda w, co, fc, Fc, ff, Cf, mv, po, te, E, n, *r, **k: n)
-    model._update_former = timed(real_upd, upd_ev, lambda pk, x, ldx, n, *r, **k: n)       # tracks of the call
-    model._encode = timed(real_enc, enc_ev, lambda pk, x4, n, *r, **k: n)                  # images of the chunk
+    if args.full:
+        hip.corr_gather_dot = timed(real_corr, corr_ev, lambda *c, **k: c[7] * c[8])          # rows = N * S
+        # (bf16 mode runs everything after the correlation -- token assembly, updater, flow head, track update -- as ONE library call)
+        hip.updateformer_forward_tokens = timed(hip.updateformer_forward_tokens, upd_ev,
+                                                lambda w, co, fc, Fc, ff, Cf, mv, po, te, E, n, *r, **k: n)
+        model._update_former = timed(real_upd, upd_ev, lambda pk, x, ldx, n, *r, **k: n)       # tracks of the call
+        model._encode = timed(real_enc, enc_ev, lambda pk, x4, n, *r, **k: n)                  # images of the chunk
 
     def step():
         return runner(a["rgbs"], a["depths"], a["query_points"], a["intrs"], a["extrs"], iters=args.iters, gather_output=False)
@@ -261,12 +295,14 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
-        step()
+        res = step()
         marks[i + 1].record()  # (no sync between steps: the K steps are timed as one bracketed region)
     barrier()
     dt = time.perf_counter() - t0
     timing["on"] = False
     runner.check_finite_collective()  # (every rank joins: a rank raising alone would strand its peers)
+    if args.dump_outputs and rank == 0:  # (before anything else runs on the model: the last timed step's results as returned)
+        dump_outputs(args.dump_outputs, res)
     # Calibration of the HIP-event timing of the correlation kernel, outside the timed region, with the operands of the last launch
     # and nothing else on the chip: (a) the same launch 20 x back to back inside ONE event pair -> its duration alone, launch gaps
     # included, no event cost (the ~225 MB it touches may stay cache-resident between the repeats: a WARM figure); (b) 20 single
@@ -275,7 +311,7 @@ def main():
     # in the 256 MiB Infinity Cache): the COLD figure alone on the chip.  `roofline.frac` is the in-situ measurement as it is; the
     # corrected and the alone figures are reported under their own keys.  --no-corr-calibration skips all of this (rocprofv3 runs).
     alone_b2b_ms = ev_overhead_ms = alone_cold_ms = None
-    if rank == 0 and "corr" in last_call and not args.no_corr_calibration:
+    if rank == 0 and args.full and "corr" in last_call and not args.no_corr_calibration:
         cargs, ckw = last_call["corr"]
         torch.cuda.synchronize()
         for _ in range(5):
@@ -314,7 +350,7 @@ def main():
         ev_overhead_ms = max(0.0, float(np.median(single)) - alone_b2b_ms)
         alone_cold_ms = float(np.median(cold)) - ev_overhead_ms
     two_clips = None
-    if rank == 0 and world == 1 and args.clips_in_flight == 2:
+    if rank == 0 and world == 1 and args.full and args.clips_in_flight == 2:
         two_clips = two_clips_in_flight(model, a, args, MVTracker, synth, dev, V, T, H, W, Nq, clip_kw, prec)
     if world > 1:
         import torch.distributed as dist
@@ -327,60 +363,6 @@ def main():
         value = world * Nq * T / (dt / args.steps)
         per_step = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
         store_bf16 = model.store_dtype() == torch.bfloat16
-        full = [(e0.elapsed_time(e1), rows) for e0, e1, rows in corr_ev if rows == Nq * model.S]
-        raw_ms = float(np.mean([m for m, _ in full])) if full else float("nan")
-        ev_overhead_ms = ev_overhead_ms or 0.0
-        kern_ms = raw_ms - ev_overhead_ms  # launch duration without the event pair's own cost (a derived figure: own key)
-        alg = model.corr_n_levels * corr_algorithmic_bytes(Nq * model.S, model.corr_neighbors, model.latent_dim, 2 if store_bf16 else 4)
-        achieved = alg / (raw_ms * 1e-3) / 1e9 if full else float("nan")  # as measured in situ, nothing subtracted
-        # the launches of the LAST window run alone on the chip; the earlier windows share HBM with the encoder of the later frames
-        # on the second stream.  per step: windows x iters full launches, in order
-        per_win = args.iters
-        n_full_step = len(full) // args.steps if args.steps else 0
-        alone = [m for i, (m, _) in enumerate(full) if n_full_step and (i % n_full_step) >= n_full_step - per_win]
-        last_win_ms = (float(np.mean(alone)) - ev_overhead_ms) if (alone and model.overlap_encoder and n_full_step > per_win) else None
-        alone_ms = alone_b2b_ms if (alone_b2b_ms and last_call["corr"][0][7] * last_call["corr"][0][8] == Nq * model.S) else None
-        # HBM traffic of the roofline kernel: an OFFLINE PMC measurement committed under profiles/ (tools/pmc_traffic.sh: counters
-        # cannot be collected from inside the timed run).  Only quoted for the workload it was measured on; the source is named.
-        traffic, traffic_source = None, None
-        for name in ("r04_corr_traffic.json", "r03_corr_traffic.json", "r02_corr_traffic.json", "r01_corr_traffic.json"):
-            tpath = os.path.join(ROOT, "profiles", name)
-            if os.path.exists(tpath):
-                tj = json.load(open(tpath))
-                if tj.get("algorithmic_bytes_per_launch") == alg:
-                    traffic = tj["traffic_bytes_per_launch"]
-                    traffic_source = f"profiles/{name} (offline rocprofv3 PMC passes: FETCH_SIZE, WRITE_SIZE; not measured in this run)"
-                    break
-        peak_tf = MFMA_F32_TFLOPS if prec == "fp32" else MFMA_BF16_TFLOPS
-        def union_ms(evs):
-            """Wall time during which at least one of the timed calls was running: the encoder's chunks run on up to three
-            streams at once, so the SUM of their event-pair times counts overlapped wall twice (event timestamps are global: every
-            interval is placed on the axis of the first step mark)."""
-            iv = sorted((marks[0].elapsed_time(e0), marks[0].elapsed_time(e1)) for e0, e1, _ in evs)
-            tot, hi = 0.0, float("-inf")
-            for a_, b_ in iv:
-                if a_ > hi:
-                    tot += b_ - a_
-                    hi = b_
-                elif b_ > hi:
-                    tot += b_ - hi
-                    hi = b_
-            return tot
-
-        upd_ms = union_ms(upd_ev) / args.steps
-        upd_sum = sum(e0.elapsed_time(e1) for e0, e1, _ in upd_ev) / args.steps
-        upd_fl = sum(updater_flops(n, model.S) for _, _, n in upd_ev) / args.steps
-        enc_ms = union_ms(enc_ev) / args.steps
-        enc_sum = sum(e0.elapsed_time(e1) for e0, e1, _ in enc_ev) / args.steps
-        enc_fl = sum(n * encoder_flops(H, W, model.latent_dim) for _, _, n in enc_ev) / args.steps
-        x3 = 3.0 if prec == "bf16x3" else 1.0  # three bf16 MFMAs per product in the split-precision mode
-
-        def mfma(fl, t_ms, calls, t_sum):
-            tf = fl / (t_ms * 1e-3) / 1e12 if t_ms > 0 else float("nan")
-            return {"bound": "mfma", "achieved": tf, "peak": peak_tf, "unit": "TFLOP/s", "frac": tf * x3 / peak_tf,
-                    "flops_per_step": fl, "ms_per_step": t_ms, "ms_per_step_sum_of_calls": t_sum, "calls_per_step": calls,
-                    "timing": "in-situ wall (union of the calls' HIP-event intervals over all streams)"}
-
         out = {
             # (BASELINE.json's metric string for its config C3; the other workloads are labelled by their own shape)
             "metric": "query-points*frames/sec, 4-view 24-frame 512x512 @1024 queries" if (args.config == "c3" and (V, T, H, W, Nq) == (4, 24, 512, 512, 1024))
@@ -394,29 +376,86 @@ def main():
                                    f"iters={args.iters}, {len(model.last_windows)} windows, random-init weights (seeded recipe)",
                        "queries_total": Nq * world, "parallelism": f"query-shard x{world}",
                        "frame_store": "bf16 rows" if store_bf16 else "fp32 rows"},
-            "roofline": {"bound": "hbm", "kernel": "corr_gather_dot_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         # `achieved` / `frac` price the ALGORITHMIC bytes over the average in-situ launch duration
-                         # as the HIP events measured it (all windows: two of three share HBM with the encoder stream; the event
-                         # pair's own cost included).  Derived figures, each under its own key: `frac_event_corrected`: the measured
-                         # event-pair overhead subtracted; `frac_alone_cold`: one launch alone on the chip behind a 512 MiB cache
-                         # flush; `frac_alone_warm`: 20 x back to back in one event pair (operands may stay cache-resident);
-                         # `frac_last_window`: the in-situ launches of the last window (no encoder stream), overhead subtracted
-                         "frac_event_corrected": (alg / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (full and ev_overhead_ms) else None,
-                         "frac_alone_cold": (alg / (alone_cold_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (alone_ms and alone_cold_ms) else None,
-                         "frac_alone_warm": (alg / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if alone_ms else None,
-                         "frac_last_window": (alg / (last_win_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if last_win_ms else None,
-                         "hbm_GBps_from_traffic": (traffic / (raw_ms * 1e-3) / 1e9) if (traffic and full) else None,
-                         "algorithmic_bytes_per_launch": alg, "bytes_per_unit": alg // (model.corr_n_levels * Nq * model.S),
-                         "avg_launch_ms": raw_ms, "avg_launch_ms_event_corrected": kern_ms, "event_pair_overhead_ms": ev_overhead_ms,
-                         "avg_launch_ms_alone_warm": alone_ms, "avg_launch_ms_alone_cold": alone_cold_ms if alone_ms else None,
-                         "launches_timed": len(full), "min_launch_ms": float(np.min([m for m, _ in full])) if full else None},
-            "roofline_mfma": {"updater": mfma(upd_fl, upd_ms, len(upd_ev) // args.steps, upd_sum),
-                              "encoder": mfma(enc_fl, enc_ms, len(enc_ev) // args.steps, enc_sum)},
         }
+        if args.full:
+            full = [(e0.elapsed_time(e1), rows) for e0, e1, rows in corr_ev if rows == Nq * model.S]
+            raw_ms = float(np.mean([m for m, _ in full])) if full else float("nan")
+            ev_overhead_ms = ev_overhead_ms or 0.0
+            kern_ms = raw_ms - ev_overhead_ms  # launch duration without the event pair's own cost (a derived figure: own key)
+            alg = model.corr_n_levels * corr_algorithmic_bytes(Nq * model.S, model.corr_neighbors, model.latent_dim, 2 if store_bf16 else 4)
+            achieved = alg / (raw_ms * 1e-3) / 1e9 if full else float("nan")  # as measured in situ, nothing subtracted
+            # the launches of the LAST window run alone on the chip; the earlier windows share HBM with the encoder of the later frames
+            # on the second stream.  per step: windows x iters full launches, in order
+            per_win = args.iters
+            n_full_step = len(full) // args.steps if args.steps else 0
+            alone = [m for i, (m, _) in enumerate(full) if n_full_step and (i % n_full_step) >= n_full_step - per_win]
+            last_win_ms = (float(np.mean(alone)) - ev_overhead_ms) if (alone and model.overlap_encoder and n_full_step > per_win) else None
+            alone_ms = alone_b2b_ms if (alone_b2b_ms and last_call["corr"][0][7] * last_call["corr"][0][8] == Nq * model.S) else None
+            # HBM traffic of the roofline kernel: an OFFLINE PMC measurement committed under profiles/ (tools/pmc_traffic.sh: counters
+            # cannot be collected from inside the timed run).  Only quoted for the workload it was measured on; the source is named.
+            traffic, traffic_source = None, None
+            for name in ("r04_corr_traffic.json", "r03_corr_traffic.json", "r02_corr_traffic.json", "r01_corr_traffic.json"):
+                tpath = os.path.join(ROOT, "profiles", name)
+                if os.path.exists(tpath):
+                    tj = json.load(open(tpath))
+                    if tj.get("algorithmic_bytes_per_launch") == alg:
+                        traffic = tj["traffic_bytes_per_launch"]
+                        traffic_source = f"profiles/{name} (offline rocprofv3 PMC passes: FETCH_SIZE, WRITE_SIZE; not measured in this run)"
+                        break
+            peak_tf = MFMA_F32_TFLOPS if prec == "fp32" else MFMA_BF16_TFLOPS
+            def union_ms(evs):
+                """Wall time during which at least one of the timed calls was running: the encoder's chunks run on up to three
+                streams at once, so the SUM of their event-pair times counts overlapped wall twice (event timestamps are global: every
+                interval is placed on the axis of the first step mark)."""
+                iv = sorted((marks[0].elapsed_time(e0), marks[0].elapsed_time(e1)) for e0, e1, _ in evs)
+                tot, hi = 0.0, float("-inf")
+                for a_, b_ in iv:
+                    if a_ > hi:
+                        tot += b_ - a_
+                        hi = b_
+                    elif b_ > hi:
+                        tot += b_ - hi
+                        hi = b_
+                return tot
+
+            upd_ms = union_ms(upd_ev) / args.steps
+            upd_sum = sum(e0.elapsed_time(e1) for e0, e1, _ in upd_ev) / args.steps
+            upd_fl = sum(updater_flops(n, model.S) for _, _, n in upd_ev) / args.steps
+            enc_ms = union_ms(enc_ev) / args.steps
+            enc_sum = sum(e0.elapsed_time(e1) for e0, e1, _ in enc_ev) / args.steps
+            enc_fl = sum(n * encoder_flops(H, W, model.latent_dim) for _, _, n in enc_ev) / args.steps
+            x3 = 3.0 if prec == "bf16x3" else 1.0  # three bf16 MFMAs per product in the split-precision mode
+
+            def mfma(fl, t_ms, calls, t_sum):
+                tf = fl / (t_ms * 1e-3) / 1e12 if t_ms > 0 else float("nan")
+                return {"bound": "mfma", "achieved": tf, "peak": peak_tf, "unit": "TFLOP/s", "frac": tf * x3 / peak_tf,
+                        "flops_per_step": fl, "ms_per_step": t_ms, "ms_per_step_sum_of_calls": t_sum, "calls_per_step": calls,
+                        "timing": "in-situ wall (union of the calls' HIP-event intervals over all streams)"}
+
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": "corr_gather_dot_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                             # `achieved` / `frac` price the ALGORITHMIC bytes (SURVEY section 8d) over the average in-situ launch duration
+                             # as the HIP events measured it (all windows: two of three share HBM with the encoder stream; the event
+                             # pair's own cost included).  Derived figures, each under its own key: `frac_event_corrected`: the measured
+                             # event-pair overhead subtracted; `frac_alone_cold`: one launch alone on the chip behind a 512 MiB cache
+                             # flush; `frac_alone_warm`: 20 x back to back in one event pair (operands may stay cache-resident);
+                             # `frac_last_window`: the in-situ launches of the last window (no encoder stream), overhead subtracted
+                             "frac_event_corrected": (alg / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (full and ev_overhead_ms) else None,
+                             "frac_alone_cold": (alg / (alone_cold_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (alone_ms and alone_cold_ms) else None,
+                             "frac_alone_warm": (alg / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if alone_ms else None,
+                             "frac_last_window": (alg / (last_win_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if last_win_ms else None,
+                             "hbm_GBps_from_traffic": (traffic / (raw_ms * 1e-3) / 1e9) if (traffic and full) else None,
+                             "algorithmic_bytes_per_launch": alg, "bytes_per_unit": alg // (model.corr_n_levels * Nq * model.S),
+                             "avg_launch_ms": raw_ms, "avg_launch_ms_event_corrected": kern_ms, "event_pair_overhead_ms": ev_overhead_ms,
+                             "avg_launch_ms_alone_warm": alone_ms, "avg_launch_ms_alone_cold": alone_cold_ms if alone_ms else None,
+                             "launches_timed": len(full), "min_launch_ms": float(np.min([m for m, _ in full])) if full else None},
+                "roofline_mfma": {"updater": mfma(upd_fl, upd_ms, len(upd_ev) // args.steps, upd_sum),
+                                  "encoder": mfma(enc_fl, enc_ms, len(enc_ev) // args.steps, enc_sum)},
+            })
         if two_clips is not None:
             out["throughput_two_clips"] = two_clips
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, V, (H, W))
         print(json.dumps(out), flush=True)
     if world > 1 or os.environ.get("MVT_FORCE_SHARDED"):

@@ -7,7 +7,7 @@ root=$GRAFT_REPO_ROOT
 out=$root/gpurun_out/$name
 mkdir -p $out
 cd $root
-python3 bench.py --steps 20 --warmup 5 > $out/bench_bf16.json 2> $out/bench_bf16.err || exit 1
+python3 bench.py --full --steps 20 --warmup 5 > $out/bench_bf16.json 2> $out/bench_bf16.err || exit 1
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o t -- python3 $root/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-corr-calibration > $out/bench_under_rocprof.json 2> $out/trace.err || exit 1
 for c in FETCH_SIZE WRITE_SIZE; do
