@@ -442,6 +442,21 @@ int mvt_attention_bf16(const void* q, int ldq, long long q_gs, long long q_is, c
 #define MVT_ATTN_NSPLIT 4 /* key splits of that path */
 /* x[(n*S+s)*ld + 0:C] = v[n][0:C] for all s  (virtual-token broadcast, blocks.py:458-459). */
 int mvt_broadcast_rows(const float* v, float* x, int ld, int n, int S, int C, void* stream);
+/* Segmented forms of mvt_attention / mvt_attention_bf16: nseg independent attentions through one launch per kernel form.
+ * Segment s reads its queries from rows q_row0[s] + (group stride, item stride) of q (writes o at the same rows) and its keys
+ * from rows k_row0[s] + ... of k / v, with nq[s] queries and nk[s] keys per group; q_row0 / nq / k_row0 / nk are HOST arrays
+ * of nseg entries.  Every segment's output is bit-identical to the ungrouped call on that segment alone: each one takes the
+ * kernel form, key partition and key-split decision of that call.  The bf16 workspace (NULL: no key split) holds
+ * 4 * groups*heads*ceil(nq[s]/64) * 4352 floats for every segment that takes the key-split path; ws_floats is its size. */
+int mvt_attention_segmented(const float* q, int ldq, long long q_gs, long long q_is, const float* k, const float* v, int ldkv,
+                            long long k_gs, long long k_is, float* o, int ldo, int groups, int heads, int dh, int nseg,
+                            const long long* q_row0, const int* nq, const long long* k_row0, const int* nk, void* stream);
+int mvt_attention_bf16_segmented(const void* q, int ldq, long long q_gs, long long q_is, const void* k, const void* v, int ldkv,
+                                 long long k_gs, long long k_is, void* o, int ldo, int groups, int heads, int dh, int io_flags, int nseg,
+                                 const long long* q_row0, const int* nq, const long long* k_row0, const int* nk, float* workspace,
+                                 long long ws_floats, void* stream);
+/* x[(r*S+s)*ld + 0:C] = v[r % n][0:C] for r < reps*n, all s: the virtual tokens of `reps` independent query sets. */
+int mvt_broadcast_rows_repeat(const float* v, float* x, int ld, int n, int S, int C, int reps, void* stream);
 
 /* Track state of one sliding window (mvtracker.py:505-511, 645-655, 695): n tracks (sorted by query frame), the first p0 of
  * them carried over from the previous window (prev_coords [p0][S][3], prev_vis [p0][S] logits; window stride S/2).
@@ -449,6 +464,11 @@ int mvt_broadcast_rows(const float* v, float* x, int ld, int n, int S, int C, vo
  * initial visibility), ffeats [n][S][C].  Window slot s reads frame min(w + s, T - 1). */
 int mvt_window_prepare(const float* qxyz, const int* qt, const float* feat_init, const float* prev_coords, const float* prev_vis,
                        int n, int p0, int S, int C, int w, int T, float* coords, float* mask_vis, float* ffeats, void* stream);
+/* mvt_window_prepare with an explicit carry map (several independent query sets in one window, each with its own carried
+ * prefix): carry_src[tr] >= 0 is the row of prev_coords / prev_vis track tr continues from, -1 a track that enters here. */
+int mvt_window_prepare_mapped(const float* qxyz, const int* qt, const float* feat_init, const float* prev_coords, const float* prev_vis,
+                              const int* carry_src, int n, int S, int C, int w, int T, float* coords, float* mask_vis, float* ffeats,
+                              void* stream);
 /* Results of the window into the clip outputs in the caller's query order (mvtracker.py:692-693, 710-711): for s < min(S, T - w)
  * traj[(w+s)][order[i]] = coords[i][s], vis_logit = vis[i][s], vis_prob = sigmoid(vis[i][s]).  traj [T][N][3], vis_* [T][N],
  * order [n] int64. */
@@ -563,6 +583,18 @@ typedef struct mvt_token_inputs {
 } mvt_token_inputs;
 int mvt_updateformer_forward_tokens(const mvt_updater_weights* w, const mvt_token_inputs* tokens, int n, float* delta, int ldd,
                                     float* coords, float* ffeats, int* nan_flag, void* workspace, long long workspace_bytes, void* stream);
+/* The same two entries for G independent query sets (MVTracker.forward_grouped): the point tracks of set g are group_n[g] (HOST
+ * array, sum = n) consecutive tracks, each set has its own n_virtual virtual tracks (rows n*S + (g*n_virtual + j)*S + t) and
+ * attends only within itself (segmented space attentions).  fuse_attention bits 2, 4, 16 and 32 (in-kernel attentions without a
+ * set dimension) fall back to their separate launches when G > 1; with G = 1 the launch sequence is the ungrouped one.
+ * Workspace: mvt_updateformer_grouped_workspace_bytes(n, S, G) bytes. */
+long long mvt_updateformer_grouped_workspace_bytes(int n, int S, int G);
+int mvt_updateformer_forward_grouped(const mvt_updater_weights* w, const float* x, int ldx, int n, int G, const int* group_n, float* delta,
+                                     int ldd, float* coords, float* ffeats, int* nan_flag, void* workspace, long long workspace_bytes,
+                                     void* stream);
+int mvt_updateformer_forward_tokens_grouped(const mvt_updater_weights* w, const mvt_token_inputs* tokens, int n, int G, const int* group_n,
+                                            float* delta, int ldd, float* coords, float* ffeats, int* nan_flag, void* workspace,
+                                            long long workspace_bytes, void* stream);
 int mvt_token_input_proj_bf16(const float* coords, const float* fcorr, int Fc, const float* ffeats, int Cf, const float* mask_vis,
                               const float* pos, const float* time_embed, int n_tracks, int S, int E, const unsigned short* win,
                               const float* bin, const float* virtual_tokens, float* x, int ldx, const mvt_block_next* next, int n_next,

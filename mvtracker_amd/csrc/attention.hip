@@ -14,12 +14,13 @@
 
 namespace {
 
+// (the kernel bodies take their workgroup id: the segmented launches below run the same bodies per segment)
 template <int DH>
-__global__ __launch_bounds__(256) void attention_qlane_kernel(const float* __restrict__ q, int ldq, long long q_gs, long long q_is,
-                                                              const float* __restrict__ k, const float* __restrict__ v, int ldkv,
-                                                              long long k_gs, long long k_is, float* __restrict__ o, int ldo,
-                                                              int groups, int nq, int nk, int heads) {
-  const long long task = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void attention_qlane(const float* __restrict__ q, int ldq, long long q_gs, long long q_is,
+                                                const float* __restrict__ k, const float* __restrict__ v, int ldkv, long long k_gs,
+                                                long long k_is, float* __restrict__ o, int ldo, int groups, int nq, int nk, int heads,
+                                                long long bid) {
+  const long long task = bid * blockDim.x + threadIdx.x;
   const long long ntask = (long long)groups * heads * nq;
   if (task >= ntask) return;
   const int qi = (int)(task % nq);
@@ -78,13 +79,13 @@ __global__ __launch_bounds__(256) void attention_qlane_kernel(const float* __res
 }
 
 template <int DH>
-__global__ __launch_bounds__(256) void attention_klane_kernel(const float* __restrict__ q, int ldq, long long q_gs, long long q_is,
-                                                              const float* __restrict__ k, const float* __restrict__ v, int ldkv,
-                                                              long long k_gs, long long k_is, float* __restrict__ o, int ldo,
-                                                              int groups, int nq, int nk, int heads) {
+__device__ __forceinline__ void attention_klane(const float* __restrict__ q, int ldq, long long q_gs, long long q_is,
+                                                const float* __restrict__ k, const float* __restrict__ v, int ldkv, long long k_gs,
+                                                long long k_is, float* __restrict__ o, int ldo, int groups, int nq, int nk, int heads,
+                                                long long bid) {
   __shared__ float red[4][64 * (DH + 1)];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long task = (long long)blockIdx.x * 4 + wave;
+  const long long task = bid * 4 + wave;
   const long long ntask = (long long)groups * heads * nq;
   if (task >= ntask) return;
   const int qi = (int)(task % nq);
@@ -155,9 +156,10 @@ __global__ __launch_bounds__(256) void attention_klane_kernel(const float* __res
 // broadcast ds_read_b128, so the FMAs never wait on global latency.  KS > 1 splits the keys of one query chunk over
 // KS waves whose online-softmax states are merged through LDS (virtual<-point attention: 64 queries x 1024 keys).
 template <int DH, int KS>
-__global__ __launch_bounds__(KS == 1 ? 256 : KS * 64) void attention_ukeys_kernel(
-    const float* __restrict__ q, int ldq, long long q_gs, long long q_is, const float* __restrict__ k, const float* __restrict__ v,
-    int ldkv, long long k_gs, long long k_is, float* __restrict__ o, int ldo, int groups, int nq, int nk, int heads) {
+__device__ __forceinline__ void attention_ukeys(const float* __restrict__ q, int ldq, long long q_gs, long long q_is,
+                                                const float* __restrict__ k, const float* __restrict__ v, int ldkv, long long k_gs,
+                                                long long k_is, float* __restrict__ o, int ldo, int groups, int nq, int nk, int heads,
+                                                long long bid) {
   constexpr int NW = KS == 1 ? 4 : KS;         // waves per block
   constexpr int CH = 16;                       // keys per staged chunk
   constexpr int Q4 = DH / 4;                   // float4 per row
@@ -171,7 +173,7 @@ __global__ __launch_bounds__(KS == 1 ? 256 : KS * 64) void attention_ukeys_kerne
   float* sv = sk + CH * DH;
   const int chunks = (nq + 63) / 64;
   const long long nchunk = (long long)groups * heads * chunks;
-  const long long chunk_id = KS == 1 ? (long long)blockIdx.x * 4 + wave : (long long)blockIdx.x;
+  const long long chunk_id = KS == 1 ? bid * 4 + wave : bid;
   const bool chunk_ok = chunk_id < nchunk;  // KS == 1 only: trailing waves of the last block
   const long long cid = chunk_ok ? chunk_id : 0;
   const int qc = (int)(cid % chunks);
@@ -295,6 +297,53 @@ __global__ __launch_bounds__(KS == 1 ? 256 : KS * 64) void attention_ukeys_kerne
   }
 }
 
+#define ATTN_ARGS                                                                                                               \
+  const float *__restrict__ q, int ldq, long long q_gs, long long q_is, const float *__restrict__ k, const float *__restrict__ v, \
+      int ldkv, long long k_gs, long long k_is, float *__restrict__ o, int ldo, int groups
+template <int DH>
+__global__ __launch_bounds__(256) void attention_qlane_kernel(ATTN_ARGS, int nq, int nk, int heads) {
+  attention_qlane<DH>(q, ldq, q_gs, q_is, k, v, ldkv, k_gs, k_is, o, ldo, groups, nq, nk, heads, blockIdx.x);
+}
+template <int DH>
+__global__ __launch_bounds__(256) void attention_klane_kernel(ATTN_ARGS, int nq, int nk, int heads) {
+  attention_klane<DH>(q, ldq, q_gs, q_is, k, v, ldkv, k_gs, k_is, o, ldo, groups, nq, nk, heads, blockIdx.x);
+}
+template <int DH, int KS>
+__global__ __launch_bounds__(KS == 1 ? 256 : KS * 64) void attention_ukeys_kernel(ATTN_ARGS, int nq, int nk, int heads) {
+  attention_ukeys<DH, KS>(q, ldq, q_gs, q_is, k, v, ldkv, k_gs, k_is, o, ldo, groups, nq, nk, heads, blockIdx.x);
+}
+
+// Segmented forms: one launch over every segment of a form; the workgroup finds its segment and runs the ungrouped body on it.
+#define SEG_BODY(CALL)                                                                                                    \
+  const int s = mvt_seg_find(t, blockIdx.x);                                                                              \
+  CALL(q + t.qrow[s] * ldq, ldq, q_gs, q_is, k + t.krow[s] * ldkv, v + t.krow[s] * ldkv, ldkv, k_gs, k_is, o + t.qrow[s] * ldo, \
+       ldo, groups, t.nq[s], t.nk[s], heads, blockIdx.x - t.blk[s])
+template <int DH>
+__global__ __launch_bounds__(256) void attention_qlane_seg_kernel(ATTN_ARGS, int heads, mvt_seg_table t) {
+  SEG_BODY(attention_qlane<DH>);
+}
+template <int DH>
+__global__ __launch_bounds__(256) void attention_klane_seg_kernel(ATTN_ARGS, int heads, mvt_seg_table t) {
+  SEG_BODY(attention_klane<DH>);
+}
+template <int DH, int KS>
+__global__ __launch_bounds__(KS == 1 ? 256 : KS * 64) void attention_ukeys_seg_kernel(ATTN_ARGS, int heads, mvt_seg_table t) {
+  SEG_BODY((attention_ukeys<DH, KS>));
+}
+#undef SEG_BODY
+#undef ATTN_ARGS
+
+// the form of the ungrouped launch for (nq, nk): 0 ukeys KS 8, 1 ukeys KS 1, 2 qlane, 3 klane; workgroups of that launch
+int attention_form(int groups, int nq, int nk, int heads, long long* blocks) {
+  const long long ntask = (long long)groups * heads * nq, nchunk = (long long)groups * heads * ((nq + 63) / 64);
+  if (nq >= 64) {
+    *blocks = nk > 64 ? nchunk : mvt_cdiv(nchunk, 4);
+    return nk > 64 ? 0 : 1;
+  }
+  *blocks = nk <= 64 ? mvt_cdiv(ntask, 256) : mvt_cdiv(ntask, 4);
+  return nk <= 64 ? 2 : 3;
+}
+
 }  // namespace
 
 extern "C" int mvt_attention(const float* q, int ldq, long long q_gs, long long q_is, const float* k, const float* v, int ldkv,
@@ -347,5 +396,66 @@ extern "C" int mvt_attention(const float* q, int ldq, long long q_gs, long long 
     }
   }
 #undef LAUNCH
+  return mvt_launch_status();
+}
+
+extern "C" int mvt_attention_segmented(const float* q, int ldq, long long q_gs, long long q_is, const float* k, const float* v, int ldkv,
+                                       long long k_gs, long long k_is, float* o, int ldo, int groups, int heads, int dh, int nseg,
+                                       const long long* q_row0, const int* nq, const long long* k_row0, const int* nk, void* stream) {
+  MVT_REQUIRE(q && k && v && o && groups > 0 && heads > 0 && nseg > 0 && q_row0 && nq && k_row0 && nk);
+  MVT_REQUIRE(ldq % 4 == 0 && ldkv % 4 == 0 && ldo % 4 == 0 && ldq >= heads * dh && ldkv >= heads * dh && ldo >= heads * dh);
+  MVT_REQUIRE(((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)o % 16 == 0));
+  MVT_REQUIRE(dh == 32 || dh == 48 || dh == 64);
+  for (int s = 0; s < nseg; ++s) MVT_REQUIRE(nq[s] > 0 && nk[s] > 0 && q_row0[s] >= 0 && k_row0[s] >= 0);
+  // one launch per (form, run of up to MVT_SEG_MAX segments of that form)
+  for (int form = 0; form < 4; ++form) {
+    mvt_seg_table t;
+    t.n = 0;
+    t.blk[0] = 0;
+    for (int s = 0; s <= nseg; ++s) {
+      long long nb = 0;
+      if (s < nseg && attention_form(groups, nq[s], nk[s], heads, &nb) == form) {
+        t.nq[t.n] = nq[s];
+        t.nk[t.n] = nk[s];
+        t.qrow[t.n] = q_row0[s];
+        t.krow[t.n] = k_row0[s];
+        t.ws[t.n] = 0;
+        t.blk[t.n + 1] = t.blk[t.n] + nb;
+        ++t.n;
+      }
+      if (t.n == 0 || (t.n < MVT_SEG_MAX && s < nseg)) continue;
+      const unsigned blocks = (unsigned)t.blk[t.n];
+#define LAUNCH_SEG(KERN, THREADS)                                                                                                   \
+  hipLaunchKernelGGL(KERN, dim3(blocks), dim3(THREADS), 0, mvt_stream(stream), q, ldq, q_gs, q_is, k, v, ldkv, k_gs, k_is, o, ldo, \
+                     groups, heads, t)
+#define DISPATCH_DH(KERN, THREADS)                               \
+  switch (dh) {                                                  \
+    case 32: LAUNCH_SEG((KERN<32>), THREADS); break;             \
+    case 48: LAUNCH_SEG((KERN<48>), THREADS); break;             \
+    default: LAUNCH_SEG((KERN<64>), THREADS); break;             \
+  }
+      switch (form) {
+        case 0:
+          switch (dh) {
+            case 32: LAUNCH_SEG((attention_ukeys_seg_kernel<32, 8>), 512); break;
+            case 48: LAUNCH_SEG((attention_ukeys_seg_kernel<48, 8>), 512); break;
+            default: LAUNCH_SEG((attention_ukeys_seg_kernel<64, 8>), 512); break;
+          }
+          break;
+        case 1:
+          switch (dh) {
+            case 32: LAUNCH_SEG((attention_ukeys_seg_kernel<32, 1>), 256); break;
+            case 48: LAUNCH_SEG((attention_ukeys_seg_kernel<48, 1>), 256); break;
+            default: LAUNCH_SEG((attention_ukeys_seg_kernel<64, 1>), 256); break;
+          }
+          break;
+        case 2: DISPATCH_DH(attention_qlane_seg_kernel, 256); break;
+        default: DISPATCH_DH(attention_klane_seg_kernel, 256); break;
+      }
+#undef DISPATCH_DH
+#undef LAUNCH_SEG
+      t.n = 0;
+    }
+  }
   return mvt_launch_status();
 }

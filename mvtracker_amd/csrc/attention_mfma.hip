@@ -37,11 +37,12 @@ __device__ __forceinline__ bf16x8 load8(const float* base, long long off, int bf
 }
 
 // (BFIN: bf16 q / k / v tensors -- a compile-time flag: as a run-time one every load sat in its own branch with its own full wait)
+// (the body takes its workgroup id and grid: the segmented launches below run it per segment)
 template <int KS, bool BFIN>
-__global__ __launch_bounds__(KS == 1 ? 256 : KS * 64) void attention_mfma_kernel(
-    const float* __restrict__ q, int ldq, long long q_gs, long long q_is, const float* __restrict__ k, const float* __restrict__ v,
-    int ldkv, long long k_gs, long long k_is, float* __restrict__ o, int ldo, int groups, int nq, int nk, int heads, int bf_in_unused,
-    int bf_out, float* __restrict__ ws) {
+__device__ __forceinline__ void attention_mfma(const float* __restrict__ q, int ldq, long long q_gs, long long q_is,
+                                               const float* __restrict__ k, const float* __restrict__ v, int ldkv, long long k_gs,
+                                               long long k_is, float* __restrict__ o, int ldo, int groups, int nq, int nk, int heads,
+                                               int bf_out, float* __restrict__ ws, unsigned bx, unsigned by, unsigned gx, unsigned gy) {
   constexpr int bf_in = BFIN ? 1 : 0;
   // ws != null: the keys are additionally cut over gridDim.y workgroups; wave 0 leaves its (m, l, O) partial in ws and
   // attention_merge_kernel finishes the softmax (the 64 virtual x 1024 point attention is only 72 (frame, head) chunks)
@@ -62,15 +63,15 @@ __global__ __launch_bounds__(KS == 1 ? 256 : KS * 64) void attention_mfma_kernel
   // the frame's K / V rows -- sit on six different XCDs and each pulls those rows through the fabric into its own L2.  Remapped, XCD c
   // owns the chunk-major run [c, c+1) * total/8: whole frames (the same frames as in the block kernels that produced K / V's
   // consumers' inputs and that read the partial records next, block_fused.hip).
-  unsigned bxl = blockIdx.x, byl = blockIdx.y;
+  unsigned bxl = bx, byl = by;
 #ifndef MVT_ATTN_NO_XCD  // (A/B builds, tools/build_variant.sh)
   if (KS > 1 && ws) {
-    const unsigned total = gridDim.x * gridDim.y;
+    const unsigned total = gx * gy;
     if (total % 8 == 0) {
-      const unsigned L = blockIdx.x + gridDim.x * blockIdx.y;
+      const unsigned L = bx + gx * by;
       const unsigned V = (L % 8) * (total / 8) + L / 8;
-      bxl = V / gridDim.y;
-      byl = V % gridDim.y;
+      bxl = V / gy;
+      byl = V % gy;
     }
   }
 #endif
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(KS == 1 ? 256 : KS * 64) void attention_mfma_kernel
   const long long g = cid / ((long long)chunks * heads);
 
   const int nkb = (nk + 31) / 32;                       // key blocks
-  const int gper = ws ? (nkb + (int)gridDim.y - 1) / (int)gridDim.y : nkb;   // ... of this workgroup
+  const int gper = ws ? (nkb + (int)gy - 1) / (int)gy : nkb;   // ... of this workgroup
   const int g0 = ws ? (int)byl * gper : 0;
   const int g1 = g0 + gper < nkb ? g0 + gper : nkb;
   const int per = (gper + KS - 1) / KS;
@@ -318,11 +319,10 @@ __global__ __launch_bounds__(KS == 1 ? 256 : KS * 64) void attention_mfma_kernel
 }
 
 // Combine the per-workgroup partials of a key-split attention (fixed order: deterministic) and write the output.
-__global__ __launch_bounds__(256) void attention_merge_kernel(const float* __restrict__ ws, int nsplit, long long nchunk, long long q_gs,
-                                                              long long q_is, float* __restrict__ o, int ldo, int nq, int heads,
-                                                              int bf_out) {
+__device__ __forceinline__ void attention_merge(const float* __restrict__ ws, int nsplit, long long nchunk, long long q_gs, long long q_is,
+                                                float* __restrict__ o, int ldo, int nq, int heads, int bf_out, long long bid) {
   const int lane = threadIdx.x & 63;
-  const long long cid = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const long long cid = bid * 4 + (threadIdx.x >> 6);
   if (cid >= nchunk) return;
   const int r = lane & 31, h = lane >> 5;
   const int chunks = (nq + 63) / 64;
@@ -393,6 +393,49 @@ __global__ __launch_bounds__(256) void attention_merge_kernel(const float* __res
   }
 }
 
+#define ATTN_ARGS                                                                                                               \
+  const float *__restrict__ q, int ldq, long long q_gs, long long q_is, const float *__restrict__ k, const float *__restrict__ v, \
+      int ldkv, long long k_gs, long long k_is, float *__restrict__ o, int ldo, int groups
+template <int KS, bool BFIN>
+__global__ __launch_bounds__(KS == 1 ? 256 : KS * 64) void attention_mfma_kernel(ATTN_ARGS, int nq, int nk, int heads, int bf_in_unused,
+                                                                                int bf_out, float* __restrict__ ws) {
+  attention_mfma<KS, BFIN>(q, ldq, q_gs, q_is, k, v, ldkv, k_gs, k_is, o, ldo, groups, nq, nk, heads, bf_out, ws, blockIdx.x, blockIdx.y,
+                           gridDim.x, gridDim.y);
+}
+__global__ __launch_bounds__(256) void attention_merge_kernel(const float* __restrict__ ws, int nsplit, long long nchunk, long long q_gs,
+                                                              long long q_is, float* __restrict__ o, int ldo, int nq, int heads,
+                                                              int bf_out) {
+  attention_merge(ws, nsplit, nchunk, q_gs, q_is, o, ldo, nq, heads, bf_out, blockIdx.x);
+}
+
+// row r of a fp32 or bf16 activation tensor
+__device__ __forceinline__ const float* row_ptr(const float* base, long long r, int ld, int bf) {
+  return bf ? reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(base) + r * ld) : base + r * ld;
+}
+
+// Segmented forms (mvt_seg_table): the workgroup finds its segment and runs the ungrouped body on it -- workgroup ids and grid
+// width are the segment's own, so the key partition, the key-split records and even the XCD placement are those of the
+// ungrouped launch of that segment.
+template <int KS, bool BFIN>
+__global__ __launch_bounds__(KS == 1 ? 256 : KS * 64) void attention_mfma_seg_kernel(ATTN_ARGS, int heads, int bf_out,
+                                                                                    float* __restrict__ ws, mvt_seg_table t) {
+  const int s = mvt_seg_find(t, blockIdx.x);
+  const int bf = BFIN ? 1 : 0;
+  attention_mfma<KS, BFIN>(row_ptr(q, t.qrow[s], ldq, bf), ldq, q_gs, q_is, row_ptr(k, t.krow[s], ldkv, bf), row_ptr(v, t.krow[s], ldkv, bf),
+                           ldkv, k_gs, k_is, const_cast<float*>(row_ptr(o, t.qrow[s], ldo, bf_out)), ldo, groups, t.nq[s], t.nk[s], heads,
+                           bf_out, ws ? ws + t.ws[s] : nullptr, (unsigned)(blockIdx.x - t.blk[s]), blockIdx.y,
+                           (unsigned)(t.blk[s + 1] - t.blk[s]), gridDim.y);
+}
+__global__ __launch_bounds__(256) void attention_merge_seg_kernel(const float* __restrict__ ws, int nsplit, int groups, long long q_gs,
+                                                                  long long q_is, float* __restrict__ o, int ldo, int heads, int bf_out,
+                                                                  mvt_seg_table t) {
+  const int s = mvt_seg_find(t, blockIdx.x);
+  const long long nchunk = (long long)groups * heads * ((t.nq[s] + 63) / 64);
+  attention_merge(ws + t.ws[s], nsplit, nchunk, q_gs, q_is, const_cast<float*>(row_ptr(o, t.qrow[s], ldo, bf_out)), ldo, t.nq[s], heads,
+                  bf_out, blockIdx.x - t.blk[s]);
+}
+#undef ATTN_ARGS
+
 }  // namespace
 
 extern "C" int mvt_attention_bf16(const void* q, int ldq, long long q_gs, long long q_is, const void* k, const void* v,
@@ -438,5 +481,78 @@ extern "C" int mvt_attention_bf16(const void* q, int ldq, long long q_gs, long l
 #undef WS
 #undef LAUNCH
 #undef LAUNCH_T
+  return mvt_launch_status();
+}
+
+extern "C" int mvt_attention_bf16_segmented(const void* q, int ldq, long long q_gs, long long q_is, const void* k, const void* v, int ldkv,
+                                            long long k_gs, long long k_is, void* o, int ldo, int groups, int heads, int dh, int io_flags,
+                                            int nseg, const long long* q_row0, const int* nq, const long long* k_row0, const int* nk,
+                                            float* workspace, long long ws_floats, void* stream) {
+  MVT_REQUIRE((io_flags & ~(MVT_IO_IN_BF16 | MVT_IO_OUT_BF16)) == 0);
+  const int bf_in = io_flags & MVT_IO_IN_BF16 ? 1 : 0, bf_out = io_flags & MVT_IO_OUT_BF16 ? 1 : 0;
+  MVT_REQUIRE(!bf_in || (ldq % 8 == 0 && ldkv % 8 == 0));
+  MVT_REQUIRE(!bf_out || ldo % 8 == 0);
+  MVT_REQUIRE(q && k && v && o && groups > 0 && heads > 0 && dh == DH && nseg > 0 && q_row0 && nq && k_row0 && nk);
+  MVT_REQUIRE(ldq % 4 == 0 && ldkv % 4 == 0 && ldo % 4 == 0 && ldq >= heads * dh && ldkv >= heads * dh && ldo >= heads * dh);
+  MVT_REQUIRE(((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)o % 16 == 0));
+  MVT_REQUIRE(!workspace || ((uintptr_t)workspace % 16 == 0 && ws_floats >= 0));
+  constexpr int NSPLIT = MVT_ATTN_NSPLIT;
+  // the form of the ungrouped call with this segment's (nq, nk): 0 key split over NSPLIT workgroups (+ merge), 1 KS 4, 2 KS 1
+  auto form_of = [&](int s, long long* blocks) {
+    const long long nchunk = (long long)groups * heads * ((nq[s] + 63) / 64);
+    if (nk[s] >= 512 && nchunk < 256 && workspace && ((nk[s] + 31) / 32) % NSPLIT == 0) {
+      *blocks = nchunk;
+      return 0;
+    }
+    *blocks = nk[s] >= 512 && nchunk < 1024 ? nchunk : mvt_cdiv(nchunk, 4);
+    return nk[s] >= 512 && nchunk < 1024 ? 1 : 2;
+  };
+  long long ws_need = 0;
+  for (int s = 0; s < nseg; ++s) {
+    MVT_REQUIRE(nq[s] > 0 && nk[s] > 0 && q_row0[s] >= 0 && k_row0[s] >= 0);
+    long long nb;
+    if (form_of(s, &nb) == 0) ws_need += (long long)NSPLIT * nb * MVT_PART_FLOATS;
+  }
+  MVT_REQUIRE(ws_need <= ws_floats || ws_need == 0);
+  long long ws_next = 0;  // each key-split segment owns NSPLIT * nchunk partial records of the workspace
+  for (int form = 0; form < 3; ++form) {
+    mvt_seg_table t, tm;  // tm: the merge launch's workgroups (4 chunks each)
+    t.n = tm.n = 0;
+    t.blk[0] = tm.blk[0] = 0;
+    for (int s = 0; s <= nseg; ++s) {
+      long long nb = 0;
+      if (s < nseg && form_of(s, &nb) == form) {
+        const int i = t.n;
+        t.nq[i] = tm.nq[i] = nq[s];
+        t.nk[i] = tm.nk[i] = nk[s];
+        t.qrow[i] = tm.qrow[i] = q_row0[s];
+        t.krow[i] = tm.krow[i] = k_row0[s];
+        t.ws[i] = tm.ws[i] = form == 0 ? ws_next : 0;
+        if (form == 0) ws_next += (long long)NSPLIT * nb * MVT_PART_FLOATS;
+        t.blk[i + 1] = t.blk[i] + nb;
+        tm.blk[i + 1] = tm.blk[i] + mvt_cdiv(nb, 4);
+        t.n = tm.n = i + 1;
+      }
+      if (t.n == 0 || (t.n < MVT_SEG_MAX && s < nseg)) continue;
+      const unsigned blocks = (unsigned)t.blk[t.n];
+#define LAUNCH_SEG(KS, BF, GRID, THREADS, WSP)                                                                                  \
+  hipLaunchKernelGGL((attention_mfma_seg_kernel<KS, BF>), GRID, dim3(THREADS), 0, mvt_stream(stream), (const float*)q, ldq, q_gs, \
+                     q_is, (const float*)k, (const float*)v, ldkv, k_gs, k_is, (float*)o, ldo, groups, heads, bf_out, WSP, t)
+      if (form == 0) {
+        if (bf_in) LAUNCH_SEG(4, true, dim3(blocks, NSPLIT), 256, workspace);
+        else LAUNCH_SEG(4, false, dim3(blocks, NSPLIT), 256, workspace);
+        hipLaunchKernelGGL(attention_merge_seg_kernel, dim3((unsigned)tm.blk[tm.n]), dim3(256), 0, mvt_stream(stream), workspace, NSPLIT,
+                           groups, q_gs, q_is, (float*)o, ldo, heads, bf_out, tm);
+      } else if (form == 1) {
+        if (bf_in) LAUNCH_SEG(4, true, dim3(blocks), 256, nullptr);
+        else LAUNCH_SEG(4, false, dim3(blocks), 256, nullptr);
+      } else {
+        if (bf_in) LAUNCH_SEG(1, true, dim3(blocks), 256, nullptr);
+        else LAUNCH_SEG(1, false, dim3(blocks), 256, nullptr);
+      }
+#undef LAUNCH_SEG
+      t.n = tm.n = 0;
+    }
+  }
   return mvt_launch_status();
 }

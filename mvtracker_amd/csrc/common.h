@@ -75,6 +75,23 @@ __device__ __forceinline__ void store_act4(float* base, long long off, const f32
 #define MVT_PART_FLOATS (17 * 64 * 4)
 __device__ __forceinline__ long long mvt_part_off(long long rec, int quad, int lane) { return (rec * 17 + quad) * 256 + lane * 4; }
 
+// Segment table of the segmented attention launches (attention.hip, attention_mfma.hip), passed BY VALUE as a kernel argument:
+// segment s owns the linear workgroups [blk[s], blk[s+1]) of its launch, its queries start at row qrow[s] of q / o and its keys at
+// row krow[s] of k / v; ws[s] is its workspace offset (floats) on the key-split path.  Every segment of one launch takes the
+// same kernel form, so each workgroup runs exactly the arithmetic of the ungrouped launch with (nq, nk) = (nq[s], nk[s]).
+#define MVT_SEG_MAX 32
+struct mvt_seg_table {
+  int n;
+  int nq[MVT_SEG_MAX], nk[MVT_SEG_MAX];
+  long long qrow[MVT_SEG_MAX], krow[MVT_SEG_MAX], ws[MVT_SEG_MAX];
+  long long blk[MVT_SEG_MAX + 1];
+};
+__device__ __forceinline__ int mvt_seg_find(const mvt_seg_table& t, long long b) {
+  int s = 0;
+  while (s + 1 < t.n && b >= t.blk[s + 1]) ++s;
+  return s;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

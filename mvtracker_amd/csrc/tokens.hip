@@ -69,9 +69,9 @@ __global__ __launch_bounds__(256) void token_assemble_kernel(const float* __rest
 //                     window's LOGIT for carried tracks (:653-655), 10 for new ones (:511)
 //   ffeats [n][S][C]: the track's initial feature repeated over the window (:645)
 __global__ void window_prepare_kernel(const float* __restrict__ qxyz, const int* __restrict__ qt, const float* __restrict__ feat_init,
-                                      const float* __restrict__ prev_coords, const float* __restrict__ prev_vis, int n, int p0, int S,
-                                      int C, int w, int T, float* __restrict__ coords, float* __restrict__ mask_vis,
-                                      float* __restrict__ ffeats) {
+                                      const float* __restrict__ prev_coords, const float* __restrict__ prev_vis,
+                                      const int* __restrict__ carry_src, int n, int p0, int S, int C, int w, int T,
+                                      float* __restrict__ coords, float* __restrict__ mask_vis, float* __restrict__ ffeats) {
   const long long total = (long long)n * S * (C / 4);
   const int half = S / 2;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -82,18 +82,20 @@ __global__ void window_prepare_kernel(const float* __restrict__ qxyz, const int*
     *reinterpret_cast<f32x4*>(ffeats + row * C + cq * 4) = *reinterpret_cast<const f32x4*>(feat_init + (long long)tr * C + cq * 4);
     if (cq == 0) {
       const int sp = s < half ? half + s : S - 1;  // slot of the previous window this one continues from
+      // (carry_src: the row of the previous window's outputs this track continues from, -1 for a new track)
+      const int src = carry_src ? carry_src[tr] : (tr < p0 ? tr : -1);
       float vis = 10.0f;
-      if (tr < p0) {
-        vis = prev_vis[(long long)tr * S + sp];
+      if (src >= 0) {
+        vis = prev_vis[(long long)src * S + sp];
 #pragma unroll
-        for (int a = 0; a < 3; ++a) coords[row * 3 + a] = prev_coords[((long long)tr * S + sp) * 3 + a];
+        for (int a = 0; a < 3; ++a) coords[row * 3 + a] = prev_coords[((long long)src * S + sp) * 3 + a];
       } else {
 #pragma unroll
         for (int a = 0; a < 3; ++a) coords[row * 3 + a] = qxyz[(long long)tr * 3 + a];
       }
       const int S_local = T - w < S ? T - w : S;
       const int f = w + (s < S_local ? s : S_local - 1);
-      const bool on = f >= qt[tr] && !(tr < p0 && f < w + half);
+      const bool on = f >= qt[tr] && !(src >= 0 && f < w + half);
       mask_vis[row * 2] = on ? 1.0f : 0.0f;
       mask_vis[row * 2 + 1] = vis;
     }
@@ -211,6 +213,15 @@ __global__ void broadcast_rows_kernel(const float* __restrict__ v, float* __rest
   }
 }
 
+__global__ void broadcast_rows_repeat_kernel(const float* __restrict__ v, float* __restrict__ x, int ld, int n, int S, int C, int reps) {
+  const long long total = (long long)reps * n * S * C;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C);
+    const long long r = i / C;  // (rep * n + j) * S + s
+    x[r * ld + c] = v[((r / S) % n) * C + c];
+  }
+}
+
 inline unsigned grid_for(long long total) {
   long long g = mvt_cdiv(total, 256);
   return (unsigned)(g > 256 * 32 ? 256 * 32 : (g < 1 ? 1 : g));
@@ -241,7 +252,18 @@ extern "C" int mvt_window_prepare(const float* qxyz, const int* qt, const float*
   MVT_REQUIRE(qxyz && qt && feat_init && coords && mask_vis && ffeats && n > 0 && p0 >= 0 && p0 <= n && S >= 2 && C > 0 && C % 4 == 0);
   MVT_REQUIRE(w >= 0 && w < T && (p0 == 0 || (prev_coords && prev_vis)));
   hipLaunchKernelGGL(window_prepare_kernel, dim3(grid_for((long long)n * S * (C / 4))), dim3(256), 0, mvt_stream(stream), qxyz, qt,
-                     feat_init, prev_coords, prev_vis, n, p0, S, C, w, T, coords, mask_vis, ffeats);
+                     feat_init, prev_coords, prev_vis, nullptr, n, p0, S, C, w, T, coords, mask_vis, ffeats);
+  return mvt_launch_status();
+}
+
+extern "C" int mvt_window_prepare_mapped(const float* qxyz, const int* qt, const float* feat_init, const float* prev_coords,
+                                         const float* prev_vis, const int* carry_src, int n, int S, int C, int w, int T, float* coords,
+                                         float* mask_vis, float* ffeats, void* stream) {
+  MVT_REQUIRE(qxyz && qt && feat_init && carry_src && coords && mask_vis && ffeats && n > 0 && S >= 2 && C > 0 && C % 4 == 0);
+  MVT_REQUIRE(w >= 0 && w < T);
+  // (prev_coords / prev_vis may be NULL only if no track is carried: a device map cannot be checked here, the kernel would fault)
+  hipLaunchKernelGGL(window_prepare_kernel, dim3(grid_for((long long)n * S * (C / 4))), dim3(256), 0, mvt_stream(stream), qxyz, qt,
+                     feat_init, prev_coords, prev_vis, carry_src, n, 0, S, C, w, T, coords, mask_vis, ffeats);
   return mvt_launch_status();
 }
 
@@ -279,5 +301,12 @@ extern "C" int mvt_rowdot(const float* x, int ldx, const float* w, const float* 
 extern "C" int mvt_broadcast_rows(const float* v, float* x, int ld, int n, int S, int C, void* stream) {
   MVT_REQUIRE(v && x && n > 0 && S > 0 && C > 0 && ld >= C);
   hipLaunchKernelGGL(broadcast_rows_kernel, dim3(grid_for((long long)n * S * C)), dim3(256), 0, mvt_stream(stream), v, x, ld, n, S, C);
+  return mvt_launch_status();
+}
+
+extern "C" int mvt_broadcast_rows_repeat(const float* v, float* x, int ld, int n, int S, int C, int reps, void* stream) {
+  MVT_REQUIRE(v && x && n > 0 && S > 0 && C > 0 && reps > 0 && ld >= C);
+  hipLaunchKernelGGL(broadcast_rows_repeat_kernel, dim3(grid_for((long long)reps * n * S * C)), dim3(256), 0, mvt_stream(stream), v, x, ld,
+                     n, S, C, reps);
   return mvt_launch_status();
 }

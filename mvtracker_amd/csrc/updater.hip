@@ -14,14 +14,15 @@ namespace {
 inline long long align256(long long b) { return (b + 255) & ~255LL; }
 
 struct Layout {
-  long long tok, qkv_a, qkv_b, qp, att, split_ws, attn_ws, h1, h2, total;
+  long long tok, qkv_a, qkv_b, qp, att, split_ws, attn_ws, vrep, h1, h2, total;
   int ldh;
 };
 
 constexpr int H_ = 256, HEADS = 6, DH_ = 48, INNER = HEADS * DH_, NV = 64, MLP = 1024, OUT = 131;
 
-inline Layout layout(long long n, long long S) {
-  const long long Mp = n * S, Mv = (long long)NV * S, M = Mp + Mv;
+// G > 1: G independent query sets (mvt_updateformer_forward_tokens_grouped), each with its own NV virtual tracks
+inline Layout layout(long long n, long long S, long long G = 1) {
+  const long long Mp = n * S, Mv = G * NV * S, M = Mp + Mv;
   Layout L{};
   long long o = 0;
   auto take = [&](long long bytes) { const long long at = o; o += align256(bytes); return at; };
@@ -31,7 +32,8 @@ inline Layout layout(long long n, long long S) {
   L.qp = take(Mp * INNER * 2);
   L.att = take(M * INNER * 2);
   L.split_ws = take((MLP / 256 + 1) * Mv * H_ * 4);
-  L.attn_ws = take(4LL * S * HEADS * 1 * 64 * 68 * 4);  // key-split partials of the 64-query virtual<-point attention
+  L.attn_ws = take(G * 4LL * S * HEADS * 1 * 64 * 68 * 4);  // key-split partials of the 64-query virtual<-point attention (per set)
+  L.vrep = G > 1 ? take(G * NV * H_ * 4) : 0;               // the learned virtual tokens repeated for every set
   L.ldh = (OUT + 3) / 4 * 4;
   L.h1 = take(Mp * L.ldh * 4);
   L.h2 = take(Mp * L.ldh * 4);
@@ -56,15 +58,33 @@ extern "C" long long mvt_updateformer_workspace_bytes(int n, int S) {
   return layout(n, S).total;
 }
 
+extern "C" long long mvt_updateformer_grouped_workspace_bytes(int n, int S, int G) {
+  if (n <= 0 || S <= 0 || G <= 0) return -1;
+  return layout(n, S, G).total;
+}
+
 #define MVT_TRY(call)          \
   do {                         \
     const int rc_ = (call);    \
     if (rc_ != MVT_OK) return rc_; \
   } while (0)
 
-static int updater_run(const mvt_updater_weights* w, const float* x, int ldx, const mvt_token_inputs* ti, int n, float* delta, int ldd,
-                       float* coords, float* ffeats, int* nan_flag, void* workspace, long long workspace_bytes, void* stream) {
-  MVT_REQUIRE(w && (x || ti) && workspace && n > 0 && (delta || coords));
+// G, gn: the point tracks of G independent query sets laid out back to back (gn[g] tracks each, host array; G = 1: gn unused).
+// The sets meet only in the three space attentions, which run as segmented launches for G > 1; the block kernels whose in-kernel
+// attention has no set dimension (fuse_attention bits 2, 4, 16, 32) then run in their separate-launch forms.  G = 1 is the
+// ungrouped sequence, launch for launch.
+static int updater_run(const mvt_updater_weights* w, const float* x, int ldx, const mvt_token_inputs* ti, int n, int G, const int* gn,
+                       float* delta, int ldd, float* coords, float* ffeats, int* nan_flag, void* workspace, long long workspace_bytes,
+                       void* stream) {
+  MVT_REQUIRE(w && (x || ti) && workspace && n > 0 && (delta || coords) && G >= 1 && (G == 1 || gn));
+  if (G > 1) {
+    long long sum = 0;
+    for (int g = 0; g < G; ++g) {
+      MVT_REQUIRE(gn[g] > 0);
+      sum += gn[g];
+    }
+    MVT_REQUIRE(sum == n);
+  }
   if (!x) {
     MVT_REQUIRE(ti->coords && ti->fcorr && ti->ffeats && ti->mask_vis && ti->pos && ti->time_embed && w->input_frag.w);
     MVT_REQUIRE(3 * ti->E + 3 + ti->Fc + ti->Cf + 2 == w->token_dim);
@@ -75,7 +95,7 @@ static int updater_run(const mvt_updater_weights* w, const float* x, int ldx, co
   MVT_REQUIRE(w->hidden == H_ && w->heads == HEADS && w->dim_head == DH_ && w->n_virtual == NV && w->out_dim == OUT);
   MVT_REQUIRE(w->depth >= 1 && w->depth <= MVT_UPDATER_MAX_DEPTH && w->S >= 1 && w->virtual_tokens);
   const int S = w->S;
-  const Layout L = layout(n, S);
+  const Layout L = layout(n, S, G);
   MVT_REQUIRE(workspace_bytes >= L.total && ((uintptr_t)workspace % 256) == 0);
   MVT_REQUIRE(ldx % 4 == 0 && ldx >= w->token_dim && (!delta || ldd >= OUT));
   MVT_REQUIRE(w->input_transform.w && w->input_transform.N == H_ && w->input_transform.K == w->token_dim);
@@ -98,7 +118,7 @@ static int updater_run(const mvt_updater_weights* w, const float* x, int ldx, co
   float* attn_ws = (float*)(base + L.attn_ws);
   float* h1 = (float*)(base + L.h1);
   float* h2 = (float*)(base + L.h2);
-  const long long Mp = (long long)n * S, Mv = (long long)NV * S, M = Mp + Mv;
+  const long long Mp = (long long)n * S, Mv = (long long)G * NV * S, M = Mp + Mv;
   const int ld3 = 3 * INNER;
   const int BF = MVT_IO_IN_BF16 | MVT_IO_OUT_BF16;
   float* vt = tok + Mp * H_;
@@ -115,7 +135,40 @@ static int updater_run(const mvt_updater_weights* w, const float* x, int ldx, co
     at.kind = kind; at.S = S; at.n_keys = nkeys; at.heads = HEADS; at.dim_head = DH_; at.ldq = ldq; at.ldkv = ld3; at.q = q; at.k = k; at.v = v;
     return mvt_attn_block_fused_bf16(xr, H_, &at, b.out.w, b.out.b, b.fc1.w, b.fc1.b, b.fc2.w, b.fc2.b, MLP, nx, nn, rows, H_, ws, stream);
   };
-  const bool fuse_time = (w->fuse_attention & 1) && S <= 32, fuse_p2v = (w->fuse_attention & 2) != 0, fuse_vs = (w->fuse_attention & 4) != 0;
+  const bool grouped = G > 1;
+  const bool fuse_time = (w->fuse_attention & 1) && S <= 32, fuse_p2v = (w->fuse_attention & 2) && !grouped,
+             fuse_vs = (w->fuse_attention & 4) && !grouped;
+  // segment tables of the space attentions (G > 1): point rows of set g from row off_g * S, virtual rows from Mp + g * NV * S
+  // (relative to the point / virtual bases the calls below pass)
+  long long* prow = nullptr;
+  long long* vrow = nullptr;
+  int* nvs = nullptr;
+  struct Tables {
+    long long* a = nullptr;
+    int* b = nullptr;
+    ~Tables() { free(a); free(b); }
+  } tables;
+  if (grouped) {
+    tables.a = (long long*)malloc(sizeof(long long) * 2 * G);
+    tables.b = (int*)malloc(sizeof(int) * G);
+    if (!tables.a || !tables.b) return MVT_ERR_ARG;
+    prow = tables.a;
+    vrow = tables.a + G;
+    nvs = tables.b;
+    long long off = 0;
+    for (int g = 0; g < G; ++g) {
+      prow[g] = off * S;
+      vrow[g] = (long long)g * NV * S;
+      nvs[g] = NV;
+      off += gn[g];
+    }
+  }
+  const float* vtokens = w->virtual_tokens;
+  if (grouped) {  // [G * NV][H_]: the token kernels read the virtual token of virtual row r at (r - Mp) / S
+    float* vrep = (float*)(base + L.vrep);
+    MVT_TRY(mvt_broadcast_rows_repeat(w->virtual_tokens, vrep, H_, NV, 1, H_, G, stream));
+    vtokens = vrep;
+  }
   // bit 5: the virtual-self block's pass 2 runs inside the point<-virtual block (needs both attentions in their block kernels)
   // (the first workgroups of a frame also evaluate the next layer's time q|k|v of the virtual rows, 8 column blocks each: enough tiles)
   // (not in the small-M form: while 32-token tiles of the point<-virtual block fit one round of workgroups -- ceil(n / 32) * S <= 256,
@@ -123,7 +176,7 @@ static int updater_run(const mvt_updater_weights* w, const float* x, int ldx, co
   //  its own second launch: measured faster at 400 / 512 tracks, 958 -> 906 / 929 -> 882 us per call)
   static const bool small_m = !(getenv("MVT_FRAME_NMB1") && atoi(getenv("MVT_FRAME_NMB1")) == 0);
   const bool small_form = small_m && (long long)n * S >= 4096 && (long long)((n + 31) / 32) * S <= 256;
-  const bool fold_vs = (w->fuse_attention & 32) && fuse_p2v && fuse_vs && (long long)n * S >= 4096 && !small_form && MLP / 256 <= 4 &&
+  const bool fold_vs = (w->fuse_attention & 32) && !grouped && fuse_p2v && fuse_vs && (long long)n * S >= 4096 && !small_form && MLP / 256 <= 4 &&
                        8 * ((n + 63) / 64) >= (3 * INNER + 31) / 32;
 
   // tokens: input transform of the point rows, learned virtual tokens repeated over the S frames (blocks.py:456-459), and the
@@ -133,14 +186,15 @@ static int updater_run(const mvt_updater_weights* w, const float* x, int ldx, co
     if (!x) {  // token rows assembled inside the kernel: no token matrix at all
       MVT_REQUIRE(w->token_dim <= 592 && w->input_frag.K == 592);
       MVT_TRY(mvt_token_input_proj_bf16(ti->coords, ti->fcorr, ti->Fc, ti->ffeats, ti->Cf, ti->mask_vis, ti->pos, ti->time_embed, n, S, ti->E,
-                                        w->input_frag.w, w->input_frag.b, w->virtual_tokens, tok, H_, &nx, 1, M, H_, stream));
+                                        w->input_frag.w, w->input_frag.b, vtokens, tok, H_, &nx, 1, M, H_, stream));
     } else if (w->input_frag.w && w->token_dim <= 592 && w->input_frag.K == 592) {
-      MVT_TRY(mvt_input_proj_bf16(x, ldx, w->token_dim, Mp, w->input_frag.w, w->input_frag.b, w->virtual_tokens, S, tok, H_, &nx, 1, M, H_,
+      MVT_TRY(mvt_input_proj_bf16(x, ldx, w->token_dim, Mp, w->input_frag.w, w->input_frag.b, vtokens, S, tok, H_, &nx, 1, M, H_,
                                   stream));
     } else {
       MVT_TRY(mvt_gemm_bf16(x, ldx, w->input_transform.w, nullptr, w->input_transform.ldw, w->input_transform.b, nullptr, 0, tok, H_, (int)Mp,
                             H_, w->token_dim, MVT_ACT_NONE, 0, stream));
-      MVT_TRY(mvt_broadcast_rows(w->virtual_tokens, vt, H_, NV, S, H_, stream));
+      MVT_TRY(grouped ? mvt_broadcast_rows_repeat(w->virtual_tokens, vt, H_, NV, S, H_, G, stream)
+                      : mvt_broadcast_rows(w->virtual_tokens, vt, H_, NV, S, H_, stream));
       MVT_TRY(mvt_ln_proj_bf16(tok, H_, &nx, 1, M, H_, stream));
     }
   }
@@ -156,8 +210,8 @@ static int updater_run(const mvt_updater_weights* w, const float* x, int ldx, co
       if (fuse_time) {
         MVT_TRY(attn_block(tb, tok, M, MVT_ATTN_TIME, qkv, ld3, qkv + INNER, qkv + 2 * INNER, S, nx, 3, nullptr));
       } else {
-        MVT_TRY(mvt_attention_bf16(qkv, ld3, S, 1, qkv + INNER, qkv + 2 * INNER, ld3, S, 1, att, INNER, n + NV, S, S, HEADS, DH_, BF, nullptr,
-                                   stream));
+        MVT_TRY(mvt_attention_bf16(qkv, ld3, S, 1, qkv + INNER, qkv + 2 * INNER, ld3, S, 1, att, INNER, n + G * NV, S, S, HEADS, DH_, BF,
+                                   nullptr, stream));
         MVT_TRY(block(tb, tok, M, att, nx, 3, nullptr));
       }
     }
@@ -165,9 +219,13 @@ static int updater_run(const mvt_updater_weights* w, const float* x, int ldx, co
     unsigned short* qv = qkv + Mp * ld3;  // q|k|v rows of the virtual tokens
     unsigned short* av = att + Mp * INNER;
     // the key-split path of mvt_attention_bf16 needs >= 512 keys in 4 x whole 32-key blocks; otherwise the plain form
-    const bool parts = (w->fuse_attention & 16) && n >= 512 && ((n + 31) / 32) % MVT_ATTN_NSPLIT == 0;
-    MVT_TRY(mvt_attention_bf16(qv, ld3, 1, S, qkv + INNER, qkv + 2 * INNER, ld3, 1, S, av, INNER, S, NV, n, HEADS, DH_,
-                               BF | (parts ? MVT_ATTN_PARTIALS_ONLY : 0), attn_ws, stream));
+    const bool parts = (w->fuse_attention & 16) && !grouped && n >= 512 && ((n + 31) / 32) % MVT_ATTN_NSPLIT == 0;
+    if (grouped)
+      MVT_TRY(mvt_attention_bf16_segmented(qv, ld3, 1, S, qkv + INNER, qkv + 2 * INNER, ld3, 1, S, av, INNER, S, HEADS, DH_, BF, G, vrow, nvs,
+                                           prow, gn, attn_ws, G * 4LL * S * HEADS * 64 * 68, stream));
+    else
+      MVT_TRY(mvt_attention_bf16(qv, ld3, 1, S, qkv + INNER, qkv + 2 * INNER, ld3, 1, S, av, INNER, S, NV, n, HEADS, DH_,
+                                 BF | (parts ? MVT_ATTN_PARTIALS_ONLY : 0), attn_ws, stream));
     {
       const mvt_block_next nx = next_of(vs.qkv, qv, ld3, 0, 0);
       if (parts) {
@@ -197,7 +255,11 @@ static int updater_run(const mvt_updater_weights* w, const float* x, int ldx, co
         // (pass 1 reads the virtual q|k|v; the p2v k|v projection that overwrites k|v is written by pass 2, a later launch)
         MVT_TRY(attn_block(vs, vt, Mv, MVT_ATTN_FRAME, qv, ld3, qv + INNER, qv + 2 * INNER, NV, nx, nn, split_ws));
       } else {
-        MVT_TRY(mvt_attention_bf16(qv, ld3, 1, S, qv + INNER, qv + 2 * INNER, ld3, 1, S, av, INNER, S, NV, NV, HEADS, DH_, BF, nullptr, stream));
+        if (grouped)
+          MVT_TRY(mvt_attention_bf16_segmented(qv, ld3, 1, S, qv + INNER, qv + 2 * INNER, ld3, 1, S, av, INNER, S, HEADS, DH_, BF, G, vrow, nvs,
+                                               vrow, nvs, nullptr, 0, stream));
+        else
+          MVT_TRY(mvt_attention_bf16(qv, ld3, 1, S, qv + INNER, qv + 2 * INNER, ld3, 1, S, av, INNER, S, NV, NV, HEADS, DH_, BF, nullptr, stream));
         MVT_TRY(block(vs, vt, Mv, av, nx, nn, split_ws));
       }
     }
@@ -217,7 +279,11 @@ static int updater_run(const mvt_updater_weights* w, const float* x, int ldx, co
       } else if (fuse_p2v && Mp >= 4096) {
         MVT_TRY(attn_block(p2v, tok, Mp, MVT_ATTN_FRAME, qp, INNER, qv + INNER, qv + 2 * INNER, NV, &nx, last ? 0 : 1, nullptr));
       } else {
-        MVT_TRY(mvt_attention_bf16(qp, INNER, 1, S, qv + INNER, qv + 2 * INNER, ld3, 1, S, att, INNER, S, n, NV, HEADS, DH_, BF, nullptr, stream));
+        if (grouped)
+          MVT_TRY(mvt_attention_bf16_segmented(qp, INNER, 1, S, qv + INNER, qv + 2 * INNER, ld3, 1, S, att, INNER, S, HEADS, DH_, BF, G, prow, gn,
+                                               vrow, nvs, nullptr, 0, stream));
+        else
+          MVT_TRY(mvt_attention_bf16(qp, INNER, 1, S, qv + INNER, qv + 2 * INNER, ld3, 1, S, att, INNER, S, n, NV, HEADS, DH_, BF, nullptr, stream));
         MVT_TRY(block(p2v, tok, Mp, att, &nx, last ? 0 : 1, nullptr));
       }
     }
@@ -238,12 +304,26 @@ extern "C" int mvt_updateformer_forward(const mvt_updater_weights* w, const floa
                                         float* coords, float* ffeats, int* nan_flag, void* workspace, long long workspace_bytes,
                                         void* stream) {
   MVT_REQUIRE(x);
-  return updater_run(w, x, ldx, nullptr, n, delta, ldd, coords, ffeats, nan_flag, workspace, workspace_bytes, stream);
+  return updater_run(w, x, ldx, nullptr, n, 1, nullptr, delta, ldd, coords, ffeats, nan_flag, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mvt_updateformer_forward_tokens(const mvt_updater_weights* w, const mvt_token_inputs* tokens, int n, float* delta, int ldd,
                                                float* coords, float* ffeats, int* nan_flag, void* workspace, long long workspace_bytes,
                                                void* stream) {
   MVT_REQUIRE(tokens);
-  return updater_run(w, nullptr, 0, tokens, n, delta, ldd, coords, ffeats, nan_flag, workspace, workspace_bytes, stream);
+  return updater_run(w, nullptr, 0, tokens, n, 1, nullptr, delta, ldd, coords, ffeats, nan_flag, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mvt_updateformer_forward_grouped(const mvt_updater_weights* w, const float* x, int ldx, int n, int G, const int* group_n,
+                                                float* delta, int ldd, float* coords, float* ffeats, int* nan_flag, void* workspace,
+                                                long long workspace_bytes, void* stream) {
+  MVT_REQUIRE(x);
+  return updater_run(w, x, ldx, nullptr, n, G, group_n, delta, ldd, coords, ffeats, nan_flag, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mvt_updateformer_forward_tokens_grouped(const mvt_updater_weights* w, const mvt_token_inputs* tokens, int n, int G,
+                                                       const int* group_n, float* delta, int ldd, float* coords, float* ffeats, int* nan_flag,
+                                                       void* workspace, long long workspace_bytes, void* stream) {
+  MVT_REQUIRE(tokens);
+  return updater_run(w, nullptr, 0, tokens, n, G, group_n, delta, ldd, coords, ffeats, nan_flag, workspace, workspace_bytes, stream);
 }

@@ -77,6 +77,13 @@ SIGNATURES = {
     "mvt_attention": [P, I, LL, LL, P, P, I, LL, LL, P, I, I, I, I, I, I, P],
     "mvt_attention_bf16": [P, I, LL, LL, P, P, I, LL, LL, P, I, I, I, I, I, I, I, P, P],
     "mvt_broadcast_rows": [P, P, I, I, I, I, P],
+    "mvt_attention_segmented": [P, I, LL, LL, P, P, I, LL, LL, P, I, I, I, I, I, P, P, P, P, P],
+    "mvt_attention_bf16_segmented": [P, I, LL, LL, P, P, I, LL, LL, P, I, I, I, I, I, I, P, P, P, P, P, LL, P],
+    "mvt_broadcast_rows_repeat": [P, P, I, I, I, I, I, P],
+    "mvt_window_prepare_mapped": [P, P, P, P, P, P, I, I, I, I, I, P, P, P, P],
+    "mvt_updateformer_grouped_workspace_bytes": [I, I, I],
+    "mvt_updateformer_forward_grouped": [P, P, I, I, I, P, P, I, P, P, P, P, LL, P],
+    "mvt_updateformer_forward_tokens_grouped": [P, P, I, I, P, P, I, P, P, P, P, LL, P],
     "mvt_attn_block_fused_bf16": [P, I, P, P, P, P, P, P, P, I, P, I, LL, I, P, P],
     "mvt_window_prepare": [P, P, P, P, P, I, I, I, I, I, I, P, P, P, P],
     "mvt_window_store": [P, P, P, I, I, I, I, I, P, P, P, P],
@@ -90,7 +97,8 @@ SIGNATURES = {
     "mvt_token_input_proj_bf16": [P, P, I, P, I, P, P, P, I, I, I, P, P, P, P, I, P, I, LL, I, P],
     "mvt_update_head_bf16": [P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, LL, I, I, P, P],
 }
-_RET = {"mvt_build_arch": C.c_char_p, "mvt_encoder_workspace_bytes": C.c_longlong, "mvt_updateformer_workspace_bytes": C.c_longlong}
+_RET = {"mvt_build_arch": C.c_char_p, "mvt_encoder_workspace_bytes": C.c_longlong, "mvt_updateformer_workspace_bytes": C.c_longlong,
+        "mvt_updateformer_grouped_workspace_bytes": C.c_longlong}
 
 for _name, _args in SIGNATURES.items():
     _fn = getattr(_lib, _name)  # AttributeError here = header / library mismatch
@@ -491,6 +499,42 @@ def attention_bf16(q, ldq, q_gs, q_is, k, v, ldkv, k_gs, k_is, o, ldo, groups, n
           dh, _io(q, o), _ptr(ws), _stream())
 
 
+def _segments(q_row0, nq, k_row0, nk):
+    n = len(nq)
+    assert n > 0 and len(q_row0) == len(k_row0) == len(nk) == n
+    return (n, (C.c_longlong * n)(*map(int, q_row0)), (C.c_int * n)(*map(int, nq)), (C.c_longlong * n)(*map(int, k_row0)),
+            (C.c_int * n)(*map(int, nk)))
+
+
+def attention_segmented(q, ldq, q_gs, q_is, k, v, ldkv, k_gs, k_is, o, ldo, groups, heads, dh, q_row0, nq, k_row0, nk):
+    """``attention`` on independent segments in one launch per kernel form: segment s has nq[s] queries per group from row
+    q_row0[s] of q / o and nk[s] keys from row k_row0[s] of k / v (host lists); each segment's output equals ``attention`` on it."""
+    _call("mvt_attention_segmented", _ptr(q), ldq, q_gs, q_is, _ptr(k), _ptr(v), ldkv, k_gs, k_is, _ptr(o), ldo, groups, heads, dh,
+          *_segments(q_row0, nq, k_row0, nk), _stream())
+
+
+def attention_segmented_ws_floats(groups, nq, heads):
+    """Workspace of ``attention_bf16_segmented`` that lets every segment (queries per group ``nq``: a list) take its key split."""
+    return sum(attention_ws_floats(groups, n, heads) for n in nq)
+
+
+def attention_bf16_segmented(q, ldq, q_gs, q_is, k, v, ldkv, k_gs, k_is, o, ldo, groups, heads, dh, q_row0, nq, k_row0, nk, ws=None):
+    assert q.dtype == k.dtype == v.dtype
+    assert ws is None or (ws.dtype == torch.float32 and ws.is_contiguous())
+    _call("mvt_attention_bf16_segmented", _ptr(q), ldq, q_gs, q_is, _ptr(k), _ptr(v), ldkv, k_gs, k_is, _ptr(o), ldo, groups, heads, dh,
+          _io(q, o), *_segments(q_row0, nq, k_row0, nk), _ptr(ws), ws.numel() if ws is not None else 0, _stream())
+
+
+def broadcast_rows_repeat(v, x, ld, n, S, Cc, reps):
+    _call("mvt_broadcast_rows_repeat", _ptr(v), _ptr(x), ld, n, S, Cc, reps, _stream())
+
+
+def window_prepare_mapped(qxyz, qt, feat_init, prev_coords, prev_vis, carry_src, n, S, Cc, w, T, coords, mask_vis, ffeats):
+    assert qt.dtype == torch.int32 and carry_src.dtype == torch.int32 and carry_src.numel() >= n
+    _call("mvt_window_prepare_mapped", _ptr(_f32c(qxyz)), _ptr(qt), _ptr(_f32c(feat_init)), _ptr(prev_coords), _ptr(prev_vis),
+          _ptr(carry_src), n, S, Cc, w, T, _ptr(coords), _ptr(mask_vis), _ptr(ffeats), _stream())
+
+
 def window_prepare(qxyz, qt, feat_init, prev_coords, prev_vis, n, p0, S, Cc, w, T, coords, mask_vis, ffeats):
     assert qt.dtype == torch.int32
     _call("mvt_window_prepare", _ptr(_f32c(qxyz)), _ptr(qt), _ptr(_f32c(feat_init)), _ptr(prev_coords), _ptr(prev_vis), n, p0, S, Cc, w, T,
@@ -637,3 +681,26 @@ def encoder_forward(weights: EncoderWeights, x4, n, H, W, out_rows, ldo, workspa
     """BasicEncoder.forward as one library call (bf16 mode): x4 (n,H,W,4) fp32 -> out_rows (n,H/4,W/4,ldo) fp32 or bf16."""
     _call("mvt_encoder_forward", C.addressof(weights), _ptr(_f32c(x4)), n, H, W, _ptr(out_rows), ldo,
           1 if out_rows.dtype == torch.bfloat16 else 0, _ptr(workspace), workspace.numel(), _stream())
+
+
+def _group_n(group_n):
+    return len(group_n), (C.c_int * len(group_n))(*map(int, group_n))
+
+
+def updateformer_grouped_workspace_bytes(n, S, G) -> int:
+    return int(_lib.mvt_updateformer_grouped_workspace_bytes(n, S, G))
+
+
+def updateformer_forward_grouped(weights: UpdaterWeights, x, ldx, group_n, delta, ldd, workspace, coords=None, ffeats=None, nan_flag=None):
+    """``updateformer_forward`` on independent query sets of group_n[g] tracks each (host list), laid out back to back."""
+    _call("mvt_updateformer_forward_grouped", C.addressof(weights), _ptr(_f32c(x)), ldx, sum(group_n), *_group_n(group_n), _ptr(delta), ldd,
+          _ptr(coords), _ptr(ffeats), _ptr(nan_flag), _ptr(workspace), workspace.numel(), _stream())
+
+
+def updateformer_forward_tokens_grouped(weights: UpdaterWeights, coords, fcorr, Fc, ffeats, Cf, mask_vis, pos, time_embed, E, group_n, delta,
+                                        ldd, workspace, upd_coords=None, upd_ffeats=None, nan_flag=None):
+    """``updateformer_forward_tokens`` on independent query sets of group_n[g] tracks each (host list)."""
+    ti = TokenInputs(_ptr(_f32c(coords)), _ptr(_f32c(fcorr)), _ptr(_f32c(ffeats)), _ptr(_f32c(mask_vis)), _ptr(_f32c(pos)), _ptr(_f32c(time_embed)),
+                     Fc, Cf, E)
+    _call("mvt_updateformer_forward_tokens_grouped", C.addressof(weights), C.addressof(ti), sum(group_n), *_group_n(group_n), _ptr(delta), ldd,
+          _ptr(upd_coords), _ptr(upd_ffeats), _ptr(nan_flag), _ptr(workspace), workspace.numel(), _stream())

@@ -97,6 +97,9 @@ class EvaluationPredictor(torch.nn.Module):
         self.num_uniformly_sampled_pts = num_uniformly_sampled_pts
         self.n_iters = n_iters
         self.single_point_streams = 8  # HIP streams the per-query forwards of single_point mode are spread over
+        # single_point mode: consecutive queries per MVTracker.forward_grouped call (each keeps its own rows and softmax);
+        # 1 = one forward per query.  (An attribute, not a constructor argument: the constructor mirrors the reference's.)
+        self.single_point_group_size = 1
         self._stream_pool = {}
         self.model.eval()
 
@@ -260,18 +263,27 @@ class EvaluationPredictor(torch.nn.Module):
                                 o += k
             # The per-query forwards are independent (each has its own 64 virtual tracks, :254-275) and tiny -- a few hundred
             # tracks, pure launch-latency chains -- so they are issued round-robin on a few HIP streams and overlap on the GPU.
-            n_streams = max(1, min(self.single_point_streams, num_points)) if dev.type == "cuda" else 1
+            G = max(1, int(self.single_point_group_size))
+            if G > 1 and not hasattr(self.model, "forward_grouped"):
+                raise NotImplementedError("single_point_group_size > 1 needs a model with forward_grouped")
+            n_calls = (num_points + G - 1) // G
+            n_streams = max(1, min(self.single_point_streams, n_calls)) if dev.type == "cuda" else 1
             main = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
             streams = self._streams(dev, n_streams) if n_streams > 1 else []
             for s_ in streams:
                 s_.wait_stream(main)
-            for i in range(num_points):
-                ctx = torch.cuda.stream(streams[i % n_streams]) if streams else contextlib.nullcontext()
-                with ctx:  # (everything of query i, its input rows included, is enqueued on its own stream)
-                    q_i = torch.cat([query_points_3d[0, i:i + 1]] + local_rows[i] + [support], 0)[None]
-                    res = self.model(rgbs, depths=depths, query_points=q_i, **fwd)
-                    traj_e[:, :, i] = res["traj_e"][:, :, 0]
-                    vis_e[:, :, i] = res["vis_e"][:, :, 0]
+            for c in range(n_calls):
+                ctx = torch.cuda.stream(streams[c % n_streams]) if streams else contextlib.nullcontext()
+                with ctx:  # (everything of a call, its input rows included, is enqueued on its own stream)
+                    ids = range(c * G, min((c + 1) * G, num_points))
+                    qs = [torch.cat([query_points_3d[0, i:i + 1]] + local_rows[i] + [support], 0)[None] for i in ids]
+                    if G == 1:
+                        res_l = [self.model(rgbs, depths=depths, query_points=qs[0], **fwd)]
+                    else:  # G query sets through one launch sequence (MVTracker.forward_grouped)
+                        res_l = self.model.forward_grouped(rgbs, depths, qs, **fwd)  # (the same options as the per-query calls)
+                    for i, res in zip(ids, res_l):
+                        traj_e[:, :, i] = res["traj_e"][:, :, 0]
+                        vis_e[:, :, i] = res["vis_e"][:, :, 0]
                     nan_flags.append(getattr(self.model, "last_nan_flag", None))
             for s_ in streams:
                 main.wait_stream(s_)

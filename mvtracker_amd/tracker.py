@@ -27,6 +27,7 @@ import torch
 from torch import nn
 
 from . import hip
+from .grouped import grouped_layout
 
 log = logging.getLogger(__name__)
 
@@ -811,19 +812,46 @@ class MVTracker(nn.Module):
         self._ln_lin(pk, p + ".mlp.fc1", tok, rows, hbuf, 4 * h, xn, act=hip.ACT_GELU_TANH)
         self._lin(pk, p + ".mlp.fc2", hbuf, 4 * h, rows, tok, h, R=tok, ldr=h)
 
-    def _update_former(self, pk, x, ldx, n, delta, ldd, coords=None, ffeats=None, nan_flag=None):
+    def _space_attention(self, q, ldq, k, v, ldkv, o, ldo, nq, nk, seg, pattern, bf16=False, ws=None):
+        """One per-frame space attention (query / key row of item j in frame t: j*S + t).  ``seg`` None: one query set (nq, nk).
+        ``seg`` = track counts n_g of G independent query sets: point rows of set g are its tracks [off_g, off_g + n_g), virtual
+        rows (g*nv + j)*S + t; ``pattern`` names the form -- "v2p" (virtual <- point), "vs" (virtual self), "p2v" (point <- virtual)
+        -- and every set attends within itself only."""
+        S, H, dh, nv = self.S, self.num_heads, self.dim_head, self.nv
+        if seg is None:
+            if bf16:
+                hip.attention_bf16(q, ldq, 1, S, k, v, ldkv, 1, S, o, ldo, S, nq, nk, H, dh, **({"ws": ws} if ws is not None else {}))
+            else:
+                hip.attention(q, ldq, 1, S, k, v, ldkv, 1, S, o, ldo, S, nq, nk, H, dh)
+            return
+        pts = [(int(o_) * S, int(n_)) for o_, n_ in zip(np.cumsum([0] + list(seg[:-1])), seg)]
+        virt = [(g * nv * S, nv) for g in range(len(seg))]
+        qs, ks = {"v2p": (virt, pts), "vs": (virt, virt), "p2v": (pts, virt)}[pattern]
+        q0, nqs = zip(*qs)
+        k0, nks = zip(*ks)
+        if bf16:
+            hip.attention_bf16_segmented(q, ldq, 1, S, k, v, ldkv, 1, S, o, ldo, S, H, dh, q0, nqs, k0, nks, ws=ws)
+        else:
+            hip.attention_segmented(q, ldq, 1, S, k, v, ldkv, 1, S, o, ldo, S, H, dh, q0, nqs, k0, nks)
+
+    def _update_former(self, pk, x, ldx, n, delta, ldd, coords=None, ffeats=None, nan_flag=None, seg=None):
         """delta = updater(x).  With ``coords`` / ``ffeats`` (composite path only) the track / feature update of mvtracker.py:392-399
-        is applied inside the same library call and True is returned."""
-        if "updater_struct" in pk:  # the whole transformer as ONE library call (mvt_updateformer_forward)
-            nbytes = hip.updateformer_workspace_bytes(n, self.S)
-            ws = self._workspace(nbytes, x.device)
+        is applied inside the same library call and True is returned.  ``seg``: the track counts of independent query sets laid
+        out back to back in x (``forward_grouped``), each with its own 64 virtual tracks."""
+        if "updater_struct" in pk:  # the whole transformer as ONE library call (mvt_updateformer_forward[_grouped])
             fused = coords is not None and self.fuse_head
-            hip.updateformer_forward(pk["updater_struct"], x, ldx, n, delta, ldd, ws, coords if fused else None,
-                                     ffeats if fused else None, nan_flag if fused else None)
+            upd = (coords if fused else None, ffeats if fused else None, nan_flag if fused else None)
+            if seg is None:
+                ws = self._workspace(hip.updateformer_workspace_bytes(n, self.S), x.device)
+                hip.updateformer_forward(pk["updater_struct"], x, ldx, n, delta, ldd, ws, *upd)
+            else:
+                ws = self._workspace(hip.updateformer_grouped_workspace_bytes(n, self.S, len(seg)), x.device)
+                hip.updateformer_forward_grouped(pk["updater_struct"], x, ldx, seg, delta, ldd, ws, *upd)
             return fused
         if self.precision == "bf16" and self.hidden == 256 and self.num_heads * self.dim_head == 288 and self.fuse_blocks:
-            return self._update_former_fused(pk, x, ldx, n, delta, ldd)
-        S, h, nv, H, dh = self.S, self.hidden, self.nv, self.num_heads, self.dim_head
+            return self._update_former_fused(pk, x, ldx, n, delta, ldd, seg=seg)
+        S, h, H, dh = self.S, self.hidden, self.num_heads, self.dim_head
+        nv = self.nv * (1 if seg is None else len(seg))  # virtual tracks of all query sets
         inner = H * dh
         dev = x.device
         Mp, Mv = n * S, nv * S
@@ -835,7 +863,10 @@ class MVTracker(nn.Module):
         hbuf = torch.empty(M, 4 * h, device=dev)
         u = "updateformer."
         self._lin(pk, u + "input_transform", x, ldx, Mp, tok, h)
-        hip.broadcast_rows(pk["virtual"], tok[Mp:], h, nv, S, h)
+        if seg is None:
+            hip.broadcast_rows(pk["virtual"], tok[Mp:], h, nv, S, h)
+        else:
+            hip.broadcast_rows_repeat(pk["virtual"], tok[Mp:], h, self.nv, S, h, len(seg))
         pt, vt = tok[:Mp], tok[Mp:]
         for i in range(self.depth):
             # time attention over the S frames of every (point or virtual) track
@@ -848,23 +879,20 @@ class MVTracker(nn.Module):
             p = f"{u}space_virtual2point_blocks.{i}"
             self._ln_lin(pk, p + ".cross_attn.to_q", vt, Mv, qkv[Mp:], 3 * inner, xn[Mp:])
             self._ln_lin(pk, p + ".cross_attn.to_kv", pt, Mp, qkv[:Mp, inner:], 3 * inner, xn[:Mp], *pk[p + ".norm_context"], eps=1e-5)
-            hip.attention(qkv[Mp:], 3 * inner, 1, S, qkv[:Mp, inner:], qkv[:Mp, 2 * inner:], 3 * inner, 1, S, att[Mp:], inner, S, nv, n, H,
-                          dh)
+            self._space_attention(qkv[Mp:], 3 * inner, qkv[:Mp, inner:], qkv[:Mp, 2 * inner:], 3 * inner, att[Mp:], inner, nv, n, seg, "v2p")
             self._lin(pk, p + ".cross_attn.to_out", att[Mp:], inner, Mv, vt, h, R=vt, ldr=h)
             self._mlp_residual(pk, p, vt, Mv, xn[Mp:], hbuf[Mp:])
             # virtual self attention, per frame
             p = f"{u}space_virtual_blocks.{i}"
             self._ln_lin(pk, p + ".attn.qkv", vt, Mv, qkv[Mp:], 3 * inner, xn[Mp:])
-            hip.attention(qkv[Mp:], 3 * inner, 1, S, qkv[Mp:, inner:], qkv[Mp:, 2 * inner:], 3 * inner, 1, S, att[Mp:], inner, S, nv, nv, H,
-                          dh)
+            self._space_attention(qkv[Mp:], 3 * inner, qkv[Mp:, inner:], qkv[Mp:, 2 * inner:], 3 * inner, att[Mp:], inner, nv, nv, seg, "vs")
             self._lin(pk, p + ".attn.to_out", att[Mp:], inner, Mv, vt, h, R=vt, ldr=h)
             self._mlp_residual(pk, p, vt, Mv, xn[Mp:], hbuf[Mp:])
             # point <- virtual cross attention, per frame
             p = f"{u}space_point2virtual_blocks.{i}"
             self._ln_lin(pk, p + ".cross_attn.to_q", pt, Mp, qkv[:Mp], 3 * inner, xn[:Mp])
             self._ln_lin(pk, p + ".cross_attn.to_kv", vt, Mv, qkv[Mp:, inner:], 3 * inner, xn[Mp:], *pk[p + ".norm_context"], eps=1e-5)
-            hip.attention(qkv[:Mp], 3 * inner, 1, S, qkv[Mp:, inner:], qkv[Mp:, 2 * inner:], 3 * inner, 1, S, att[:Mp], inner, S, n, nv, H,
-                          dh)
+            self._space_attention(qkv[:Mp], 3 * inner, qkv[Mp:, inner:], qkv[Mp:, 2 * inner:], 3 * inner, att[:Mp], inner, n, nv, seg, "p2v")
             self._lin(pk, p + ".cross_attn.to_out", att[:Mp], inner, Mp, pt, h, R=pt, ldr=h)
             self._mlp_residual(pk, p, pt, Mp, xn[:Mp], hbuf[:Mp])
         od = self.out_dim
@@ -909,8 +937,10 @@ class MVTracker(nn.Module):
             d.update(lnw=ln[0], lnb=ln[1])
         return d
 
-    def _update_former_fused(self, pk, x, ldx, n, delta, ldd):
-        S, h, nv, H, dh = self.S, self.hidden, self.nv, self.num_heads, self.dim_head
+    def _update_former_fused(self, pk, x, ldx, n, delta, ldd, seg=None):
+        S, h, H, dh = self.S, self.hidden, self.num_heads, self.dim_head
+        G = 1 if seg is None else len(seg)
+        nv = self.nv * G  # virtual tracks of all query sets
         inner = H * dh
         dev = x.device
         Mp, Mv = n * S, nv * S
@@ -929,12 +959,15 @@ class MVTracker(nn.Module):
         qp = torch.empty(Mp, inner, device=dev, dtype=tdt)       # point <- virtual queries (computed right after the time block)
         att = torch.empty(M, inner, device=dev, dtype=tdt)
         ws = torch.empty(5 * Mv * h, device=dev) if 4 * h == 1024 else None  # split path of the virtual-track blocks
-        aws = torch.empty(hip.attention_ws_floats(S, nv, H), device=dev) if space_mfma else None  # key-split virtual <- point attention
+        # key-split virtual <- point attention (one region per query set)
+        aws = torch.empty(G * hip.attention_ws_floats(S, self.nv, H), device=dev) if space_mfma else None
         u = "updateformer."
-        space_attn = hip.attention_bf16 if space_mfma else hip.attention
         time_attn = hip.attention_bf16 if space_mfma else hip.attention  # 12 keys pad to one 32-key MFMA block: still 1.4x the VALU kernel
         self._lin(pk, u + "input_transform", x, ldx, Mp, tok, h)
-        hip.broadcast_rows(pk["virtual"], tok[Mp:], h, nv, S, h)
+        if seg is None:
+            hip.broadcast_rows(pk["virtual"], tok[Mp:], h, nv, S, h)
+        else:
+            hip.broadcast_rows_repeat(pk["virtual"], tok[Mp:], h, self.nv, S, h, G)
         pt, vt = tok[:Mp], tok[Mp:]
         if h == 256:  # LayerNorm + projection in one launch (the split path's second pass without a workspace)
             hip.ln_proj_bf16(tok, h, [self._next(pk, f"{u}time_blocks.0.attn.qkv", qkv, 3 * inner)], M, h)
@@ -954,18 +987,19 @@ class MVTracker(nn.Module):
                                self._next(pk, p2v + ".cross_attn.to_q", qp, inner, rows=(0, Mp)),
                                self._next(pk, v2p + ".cross_attn.to_q", qkv, 3 * inner, rows=(Mp, M))])
             # virtual <- point
-            space_attn(qkv[Mp:], 3 * inner, 1, S, qkv[:Mp, inner:], qkv[:Mp, 2 * inner:], 3 * inner, 1, S, att[Mp:], inner, S, nv, n, H,
-                       dh, **({"ws": aws} if space_mfma else {}))
+            self._space_attention(qkv[Mp:], 3 * inner, qkv[:Mp, inner:], qkv[:Mp, 2 * inner:], 3 * inner, att[Mp:], inner, nv, n, seg,
+                                  "v2p", bf16=space_mfma, ws=aws)
             self._fused_block(pk, v2p, "cross_attn", vt, Mv, att[Mp:], [self._next(pk, vs + ".attn.qkv", qkv[Mp:], 3 * inner)], ws=ws)
             # virtual self attention
-            space_attn(qkv[Mp:], 3 * inner, 1, S, qkv[Mp:, inner:], qkv[Mp:, 2 * inner:], 3 * inner, 1, S, att[Mp:], inner, S, nv, nv, H,
-                       dh)
+            self._space_attention(qkv[Mp:], 3 * inner, qkv[Mp:, inner:], qkv[Mp:, 2 * inner:], 3 * inner, att[Mp:], inner, nv, nv, seg, "vs",
+                                  bf16=space_mfma)
             nx = [self._next(pk, p2v + ".cross_attn.to_kv", qkv[Mp:, inner:], 3 * inner, pk[p2v + ".norm_context"], 1e-5)]
             if not last:  # the virtual rows are final for this layer: project the next layer's time q|k|v right here
                 nx.append(self._next(pk, nxt_qkv, qkv_nx[Mp:], 3 * inner))
             self._fused_block(pk, vs, "attn", vt, Mv, att[Mp:], nx, ws=ws)
             # point <- virtual
-            space_attn(qp, inner, 1, S, qkv[Mp:, inner:], qkv[Mp:, 2 * inner:], 3 * inner, 1, S, att[:Mp], inner, S, n, nv, H, dh)
+            self._space_attention(qp, inner, qkv[Mp:, inner:], qkv[Mp:, 2 * inner:], 3 * inner, att[:Mp], inner, n, nv, seg, "p2v",
+                                  bf16=space_mfma)
             self._fused_block(pk, p2v, "cross_attn", pt, Mp, att[:Mp], [] if last else [self._next(pk, nxt_qkv, qkv_nx[:Mp], 3 * inner)])
             qkv, qkv_nx = qkv_nx, qkv
         od = self.out_dim
@@ -989,6 +1023,29 @@ class MVTracker(nn.Module):
         self._update_former(pk, xp, ldx, n, delta, ldd)
         return delta[:, :self.out_dim].reshape(1, n, S, self.out_dim)
 
+    def update_former_grouped(self, xs):
+        """``update_former`` on G independent token sets xs[g] (1,N_g,S,D) in one launch sequence (test / parity entry): the sets
+        share every row-wise kernel and attend only within themselves.  Returns the list of (1,N_g,S,3+C) deltas."""
+        with hip.device_guard(xs[0]):
+            return self._update_former_grouped(xs)
+
+    def _update_former_grouped(self, xs):
+        seg = [int(x.shape[1]) for x in xs]
+        D = self.updateformer_input_dim
+        for x in xs:
+            assert x.shape[0] == 1 and x.shape[2] == self.S and x.shape[3] == D and x.shape[1] > 0
+        S, n = self.S, sum(seg)
+        dev = xs[0].device
+        pk = self._pack(dev)
+        ldx = _round_up(D, 4)
+        xp = torch.zeros(n * S, ldx, device=dev)
+        xp[:, :D] = torch.cat([x.reshape(-1, D) for x in xs], 0)
+        ldd = _round_up(self.out_dim, 4)
+        delta = torch.zeros(n * S, ldd, device=dev)
+        self._update_former(pk, xp, ldx, n, delta, ldd, seg=seg)
+        out = delta[:, :self.out_dim].reshape(n, S, self.out_dim)
+        return [o[None] for o in torch.split(out, seg, 0)]
+
     # ------------------------------------------------------------------ one window (mvtracker.py:244-410)
     @hip.guarded
     def refine_window(self, store, frame0, coords, vis_init, track_mask, feat_init, iters=4, nan_flag=None, trace=None):
@@ -1001,7 +1058,7 @@ class MVTracker(nn.Module):
         mask_vis = torch.stack([track_mask.float(), vis_init.float()], dim=2).contiguous()
         return self._refine(store, frame0, coords, ffeats, mask_vis, iters, nan_flag, trace)
 
-    def _refine(self, store, frame0, coords, ffeats, mask_vis, iters=4, nan_flag=None, trace=None, carry=None, pre_idx=None):
+    def _refine(self, store, frame0, coords, ffeats, mask_vis, iters=4, nan_flag=None, trace=None, carry=None, pre_idx=None, seg=None):
         """The refinement loop (mvtracker.py:350-408) on prepared state: coords (n,S,3) and ffeats (n,S,C) are updated IN PLACE,
         mask_vis (n,S,2) = (track mask, initial visibility logit).  Returns ([coords per traced iteration ..., final], vis).
         ``carry`` = (neighbour indices (L,n_prev,S,K) of the previous window's last iteration, p0): the first p0 tracks continue
@@ -1106,14 +1163,19 @@ class MVTracker(nn.Module):
                     and pk["updater_struct"].input_frag.w):
                 # everything after the correlation in ONE library call: token rows assembled inside the updater's first kernel,
                 # the transformer, flow head and track / feature update (no token matrix, no delta tensor in HBM)
-                ws = self._workspace(hip.updateformer_workspace_bytes(n, S), dev)
-                hip.updateformer_forward_tokens(pk["updater_struct"], coords, fcorr, Fc, ffeats, C, mask_vis, pos, pk["time_embed"], E, n, None, ldd,
-                                                ws, coords, ffeats, nan_flag)
+                if seg is None:
+                    ws = self._workspace(hip.updateformer_workspace_bytes(n, S), dev)
+                    hip.updateformer_forward_tokens(pk["updater_struct"], coords, fcorr, Fc, ffeats, C, mask_vis, pos, pk["time_embed"], E, n, None,
+                                                    ldd, ws, coords, ffeats, nan_flag)
+                else:  # independent query sets (forward_grouped)
+                    ws = self._workspace(hip.updateformer_grouped_workspace_bytes(n, S, len(seg)), dev)
+                    hip.updateformer_forward_tokens_grouped(pk["updater_struct"], coords, fcorr, Fc, ffeats, C, mask_vis, pos, pk["time_embed"], E,
+                                                            seg, None, ldd, ws, coords, ffeats, nan_flag)
                 continue
             hip.token_assemble(coords, fcorr, Fc, ffeats, C, mask_vis, pos, pk["time_embed"], n, S, E, x, ldx)
             # (the delta tensor itself only leaves the fused head for tracing)
-            updated = self._update_former(pk, x, ldx, n, delta if trace is not None else None, ldd, coords, ffeats, nan_flag) \
-                if "updater_struct" in pk and self.fuse_head else self._update_former(pk, x, ldx, n, delta, ldd)
+            updated = self._update_former(pk, x, ldx, n, delta if trace is not None else None, ldd, coords, ffeats, nan_flag, seg=seg) \
+                if "updater_struct" in pk and self.fuse_head else self._update_former(pk, x, ldx, n, delta, ldd, seg=seg)
             if trace is not None:
                 trace.setdefault("knn_idx", []).append(idx.clone())
                 trace.setdefault("fcorrs", []).append(fcorr.clone())
@@ -1365,6 +1427,116 @@ class MVTracker(nn.Module):
             "feat_init": feat_init[None, None].expand(1, S, -1, -1),
             "vis_e": vis_prob[None],
         }
+        return results
+
+    @torch.no_grad()
+    @hip.guarded
+    def forward_grouped(self, rgbs, depths, query_points_list, intrs, extrs, iters=4, frame_store=None, trace=None, is_train=False,
+                        save_debug_logs=False, save_rerun_logs=False, **kwargs):
+        """G independent ``forward`` calls through one launch sequence: query_points_list[g] (1,N_g,4) is a query set of its own
+        (its own windows, its own 64 virtual tracks, its own softmax in the space attentions).  Returns one result dict per group,
+        with the keys, shapes and dtypes of ``forward``'s.  Groups whose first windows coincide run in the same windows; the rows
+        of a window are the concatenation of every member group's active tracks (``grouped.grouped_layout``).  ``trace``: a list
+        that receives ``forward``'s per-window dicts in that layout, plus the window start, member groups and row offsets.  The
+        other options are ``forward``'s and are handled as there (no training; the reference's logging hooks are ignored)."""
+        if is_train:
+            raise NotImplementedError("inference only: the MI355X path has no backward")
+        if save_debug_logs or save_rerun_logs:
+            log.warning("save_debug_logs / save_rerun_logs are host-side visualisation hooks of the reference; ignored")
+        if not isinstance(query_points_list, (list, tuple)) or not query_points_list:
+            raise ValueError("query_points_list must be a non-empty list of (1, N_g, 4) tensors")
+        batch_size, num_views, num_frames, _, height, width = rgbs.shape
+        assert rgbs.shape == (batch_size, num_views, num_frames, 3, height, width)
+        assert depths.shape == (batch_size, num_views, num_frames, 1, height, width)
+        assert intrs.shape == (batch_size, num_views, num_frames, 3, 3)
+        assert extrs.shape == (batch_size, num_views, num_frames, 3, 4)
+        assert batch_size == 1, "Batch size > 1 is not supported yet"
+        for g, qp in enumerate(query_points_list):
+            if qp.dim() != 3 or qp.shape[0] != 1 or qp.shape[2] != 4:
+                raise ValueError(f"group {g}: query points must be (1, N_g, 4), got {tuple(qp.shape)}")
+            if qp.shape[1] == 0:
+                raise ValueError(f"group {g} has no queries")
+        hip.require_device(rgbs)
+        dev = rgbs.device
+        V, T, S, C = num_views, num_frames, self.S, self.latent_dim
+        f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
+        rgbs = rgbs[0].to(dev).contiguous() if rgbs.dtype == torch.uint8 else f32(rgbs[0])
+        depths, intrs, extrs = map(f32, (depths[0], intrs[0], extrs[0]))
+        qcat = torch.cat([f32(qp[0]) for qp in query_points_list], 0)  # caller rows
+        sizes = [int(qp.shape[1]) for qp in query_points_list]
+        qt_all = qcat[:, 0].long().cpu().numpy()  # the one host sync of the call (mvtracker.py:489, truncation toward zero)
+        lay = grouped_layout(np.split(qt_all, np.cumsum(sizes)[:-1]), S, T)
+        N = len(qt_all)
+        wins = lay["windows"]
+        # every index map of the call in ONE upload: sorted -> caller rows, then per window rows / carry map / un-sort map
+        parts = [lay["sorted_src"]] + [a for wd in wins for a in (wd["rows"], wd["carry"], wd["out"])]
+        idx_d = torch.from_numpy(np.concatenate(parts).astype(np.int64)).to(dev)
+        sorted_src_d = idx_d[:N]
+        qxyz = qcat[sorted_src_d, 1:].contiguous()  # sorted rows
+        qt_sd = torch.from_numpy(lay["sorted_qt"].astype(np.int32)).to(dev)
+        traj = torch.zeros(T, N, 3, device=dev)
+        vis_prob = torch.zeros(T, N, device=dev)
+        vis_logit = torch.zeros(T, N, device=dev)
+        feat_init = torch.zeros(N, C, device=dev)  # sorted rows (as forward's feat_init)
+        nan_flag = torch.zeros(1, device=dev, dtype=torch.int32)
+        if wins:
+            store = frame_store if frame_store is not None else self.build_frame_store(
+                rgbs, depths, intrs, extrs, t0=max(min(wd["w"] for wd in wins), 0))
+            for _, ev in store.get("pending", ()):  # feature blocks of a shared store still in flight
+                torch.cuda.current_stream(dev).wait_event(ev)
+            # feature init of every track that ever enters a window (:607-645): 1-NN in the level-0 cloud of its query frame,
+            # all groups at once, sorted by query frame (the searches are per query: batching them changes no result)
+            ent = np.concatenate([lay["base"][g] + np.arange(lay["active"][g]) for g in range(len(sizes))])
+            ent = ent[np.argsort(lay["sorted_qt"][ent], kind="stable")]
+            ent_d = torch.from_numpy(ent.astype(np.int64)).to(dev)
+            qx_e = qxyz[ent_d].contiguous()
+            fe = torch.empty(len(ent), C, device=dev)
+            P0 = store["P"][0]
+            ns = self._nseg(P0, 1)
+            qt_e = lay["sorted_qt"][ent]
+            a = 0
+            while a < len(ent):
+                t = int(qt_e[a])
+                b = int(np.searchsorted(qt_e, t, side="right"))
+                keys = torch.empty((b - a) * ns, device=dev, dtype=torch.int64)
+                hip.knn_scan(store["xyz"][0], P0, qx_e[a:b], b - a, 1, t, 0, T, 1, ns, keys, box=store["box"][0], grid=store["tile_grid"][0])
+                hip.knn1_gather(store["fvec"][0], P0, C, keys, b - a, ns, t, fe[a:b])
+                a = b
+            feat_init.index_copy_(0, ent_d, fe)
+        o = N
+        coords = vis = None
+        windows = []
+        for wd in wins:
+            n = int(wd["off"][-1])
+            rows_d, carry_d, out_d = idx_d[o:o + n], idx_d[o + n:o + 2 * n], idx_d[o + 2 * n:o + 3 * n]
+            o += 3 * n
+            if wd["new_tracks"]:
+                coords = vis = None
+            wc = torch.empty(n, S, 3, device=dev)
+            wf = torch.empty(n, S, C, device=dev)
+            wm = torch.empty(n, S, 2, device=dev)
+            hip.window_prepare_mapped(qxyz[rows_d].contiguous(), qt_sd[rows_d].contiguous(), feat_init[rows_d].contiguous(), coords, vis,
+                                      carry_d.to(torch.int32), n, S, C, wd["w"], T, wc, wm, wf)
+            wtrace = None
+            if trace is not None:
+                wtrace = dict(w=wd["w"], groups=list(wd["groups"]), group_offsets=wd["off"].tolist(), carried=wd["p0"].tolist())
+                trace.append(wtrace)
+            preds, vis = self._refine(store, wd["w"], wc, wf, wm, iters=iters, nan_flag=nan_flag, trace=wtrace,
+                                      seg=[int(c) for c in np.diff(wd["off"])])
+            coords = preds[-1]
+            hip.window_store(coords, vis, out_d, n, S, wd["w"], T, N, traj, vis_logit, vis_prob)  # caller rows
+            windows.append((wd["w"], n))
+        self.last_windows = windows
+        self.last_vis_logits = vis_logit[None]
+        self.last_nan_flag = nan_flag
+        results = []
+        for g in range(len(sizes)):
+            b0, b1 = int(lay["base"][g]), int(lay["base"][g + 1])
+            results.append({
+                "traj_e": traj[None, :, b0:b1],
+                "feat_init": feat_init[None, None, b0:b1].expand(1, S, -1, -1),
+                "vis_e": vis_prob[None, :, b0:b1],
+            })
         return results
 
     def check_finite(self):
