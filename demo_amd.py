@@ -56,6 +56,8 @@ def main():
     ap.add_argument("--grid-size", type=int, default=5)
     ap.add_argument("--n-iters", type=int, default=4)
     ap.add_argument("--interp-shape", type=int, nargs=2, default=None, metavar=("H", "W"), help="resize like the evaluator (e.g. 384 512)")
+    ap.add_argument("--backward-tracking", action="store_true",
+                    help="also track every query before its frame (a time-reversed pass over the same frame store)")
     ap.add_argument("--save-npz", help="result file (tracks_3d, visibilities, query_points, camera data)")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
@@ -67,7 +69,8 @@ def main():
     dev = torch.device(args.device)
     torch.cuda.set_device(dev)
     predictor = load_mvtracker(checkpoint=args.checkpoint, device=dev, interp_shape=tuple(args.interp_shape) if args.interp_shape else None,
-                               grid_size=args.grid_size, n_iters=args.n_iters, single_point=args.single_point)
+                               grid_size=args.grid_size, n_iters=args.n_iters, single_point=args.single_point,
+                               backward_tracking=args.backward_tracking)
     model = predictor.model
     if args.checkpoint is None:
         print("no --checkpoint: seeded random weights (results are meaningless as tracks, the pipeline is the real one)")

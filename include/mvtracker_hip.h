@@ -298,7 +298,8 @@ int mvt_unproject(const float* depth_s, const float* kinv, const float* einv, fl
  * 800-846; feature init 1-NN, mvtracker.py:627-643).
  * --------------------------------------------------------------------------------------------- */
 /* Exact brute-force kNN.  For every (query n, slot s): candidates are the P points of frame
- * frame_of_slot = min(frame0 + s*frame_step, T-1) of xyz [T][P][4]; query = coords[(n*S+s)*3..].
+ * frame_of_slot = clamp(frame0 + s*frame_step, 0, T-1) of xyz [T][P][4] (frame_step may be negative:
+ * the time-reversed pass of backward tracking runs its slots downwards and repeats frame 0); query = coords[(n*S+s)*3..].
  * d2 = fma(dz,dz,fma(dy,dy,dx*dx)), neighbours ascending by (d2, index).  The candidate range
  * is cut into nseg segments scanned by different waves; keys [N][S][nseg][K] receive
  * (d2 bits << 32 | index) per segment, ascending (KEY_MAX = ~0 pads a segment that holds fewer than K
@@ -474,6 +475,16 @@ int mvt_window_prepare_mapped(const float* qxyz, const int* qt, const float* fea
  * order [n] int64. */
 int mvt_window_store(const float* coords, const float* vis, const long long* order, int n, int S, int w, int T, int N, float* traj,
                      float* vis_logit, float* vis_prob, void* stream);
+/* The window state and result store of the time-reversed pass (backward tracking).  wr is the window start in REVERSED time:
+ * slot s is frame max(T-1-wr - s, 0) of the clip; the n tracks are sorted by DESCENDING query frame and qt [n] holds the query
+ * frames themselves.  mvt_window_prepare_reversed is mvt_window_prepare on the time-flipped clip (track mask frame <= qt, carried
+ * half excluded, slots past the clip's start repeat frame 0).  mvt_window_store_reversed writes slot s < min(S, T - wr) to frame
+ * T-1-wr - s ONLY where that frame is < qt[i]: frames from the query frame on are the forward pass's and are never touched. */
+int mvt_window_prepare_reversed(const float* qxyz, const int* qt, const float* feat_init, const float* prev_coords,
+                                const float* prev_vis, int n, int p0, int S, int C, int wr, int T, float* coords, float* mask_vis,
+                                float* ffeats, void* stream);
+int mvt_window_store_reversed(const float* coords, const float* vis, const long long* order, const int* qt, int n, int S, int wr, int T,
+                              int N, float* traj, float* vis_logit, float* vis_prob, void* stream);
 
 /* Per-track evaluation metrics (mvtracker/evaluation/metrics.py:10-58, 61-171, 327-330; query_mode "first"): one row of
  * 11 + 2K floats per track -- movement, visible frames, occlusion accuracy (all / gt-occluded / gt-visible), average Jaccard,

@@ -102,6 +102,14 @@ __device__ __forceinline__ unsigned long long rank_sort(const unsigned long long
   return lane < cnt ? (((unsigned long long)phi << 32) | plo) : KEY_MAX;
 }
 
+// Store frame of window slot s: frame0 + s * frame_step clamped to the clip.  frame_step > 0 is the reference's window (slots past the
+// clip repeat the last frame, mvtracker.py:598-604); frame_step < 0 is the time-reversed pass of backward tracking, whose slots
+// run downwards from frame0 and repeat frame 0 past the clip's start.
+__device__ __forceinline__ int store_frame(int frame0, int s, int frame_step, int T) {
+  const int f = frame0 + s * frame_step;
+  return f < 0 ? 0 : (f < T - 1 ? f : T - 1);
+}
+
 // Candidate tiles.  The scan visits the cloud 64 points (one wave load) at a time:
 //   linear tiles (grid_w == 0): tile t = points [64 t, 64 t + 64);
 //   patch tiles  (grid_w  > 0): the cloud is V images of grid_h x grid_w points in raster order (both multiples of 8) and
@@ -212,8 +220,7 @@ __device__ __forceinline__ void knn_scan_body(unsigned long long* lds, const flo
   const int seg = (int)(task - tq * (unsigned)nseg);
   const int s = (int)(tq / (unsigned)qgroups);
   const int qg = (int)(tq - (unsigned)s * (unsigned)qgroups);
-  int frame = frame0 + s * frame_step;
-  frame = frame < T - 1 ? frame : T - 1;
+  const int frame = store_frame(frame0, s, frame_step, T);
   const float* cand = xyz + (long long)frame * P * 4;
   const int ntiles = (int)((P + 63) >> 6);
   const int tper = (ntiles + nseg - 1) / nseg;
@@ -506,8 +513,7 @@ __global__ __launch_bounds__(256) void corr_gather_dot_kernel(CorrLevels lv, con
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);  // n * S + s
   if (row >= (long long)N * S) return;
   const int s = (int)(row % S);
-  int frame = frame0 + s * frame_step;
-  frame = frame < T - 1 ? frame : T - 1;
+  const int frame = store_frame(frame0, s, frame_step, T);
   const long long P = lv.P[level];
   const float* __restrict__ xyz = lv.xyz[level];
   const float* __restrict__ fvec = lv.fvec[level];
@@ -590,8 +596,7 @@ __global__ __launch_bounds__(256) void corr_gather_dot_opts_kernel(CorrLevels lv
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);  // n * S + s
   if (row >= (long long)N * S) return;
   const int s = (int)(row % S);
-  int frame = frame0 + s * frame_step;
-  frame = frame < T - 1 ? frame : T - 1;
+  const int frame = store_frame(frame0, s, frame_step, T);
   const long long P = lv.P[level];
   const float* __restrict__ xyz = lv.xyz[level];
   const float* __restrict__ fvec = lv.fvec[level];
@@ -871,7 +876,7 @@ static int knn_scan_launch(const float* xyz, long long P, const float* coords, i
                            const float* tile_box, int grid_w, int grid_h, int* idx_direct, const float* group_box, void* stream) {
   MVT_REQUIRE(!seed_idx || (seed_k >= K && seed_k <= 64 && seed_cw >= 0));
   MVT_REQUIRE(!seed_idx || seed_cw == 0 || (seed_ch > 0 && seed_fw >= 2 * seed_cw && seed_fh >= 2 * seed_ch));
-  MVT_REQUIRE(xyz && coords && (keys || idx_direct) && N > 0 && S > 0 && T > 0 && frame0 >= 0 && frame0 < T && frame_step >= 0);
+  MVT_REQUIRE(xyz && coords && (keys || idx_direct) && N > 0 && S > 0 && T > 0 && frame0 >= 0 && frame0 < T);
   MVT_REQUIRE(K >= 1 && K <= 16 && nseg >= 1 && nseg * K <= 64 && P < (1LL << 31) && P >= K);
   MVT_REQUIRE((grid_w == 0 && grid_h == 0) || (grid_w > 0 && grid_h > 0 && grid_w % 8 == 0 && grid_h % 8 == 0 && P % ((long long)grid_w * grid_h) == 0));
   const long long ntiles = (P + 63) / 64, tper = (ntiles + nseg - 1) / nseg;
@@ -909,7 +914,7 @@ static int knn_check_level(const mvt_knn_level& L, int K) {
 
 extern "C" int mvt_knn_scan_levels(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
                                    int T, int K, int seed_k, void* stream) {
-  MVT_REQUIRE(levels >= 1 && levels <= 8 && lv && coords && N > 0 && S > 0 && T > 0 && frame0 >= 0 && frame0 < T && frame_step >= 0);
+  MVT_REQUIRE(levels >= 1 && levels <= 8 && lv && coords && N > 0 && S > 0 && T > 0 && frame0 >= 0 && frame0 < T);
   MVT_REQUIRE(K >= 1 && K <= 16 && (seed_k == 0 || (seed_k >= K && seed_k <= 64)));
   KnnLevels a{};
   int max_nseg = 1;
@@ -956,7 +961,7 @@ extern "C" int mvt_knn_merge_levels(int levels, const mvt_knn_level* lv, int N, 
 
 extern "C" int mvt_knn_search_levels(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
                                      int T, int K, int seed_k, void* stream) {
-  MVT_REQUIRE(levels >= 1 && levels <= 8 && lv && coords && N > 0 && S > 0 && T > 0 && frame0 >= 0 && frame0 < T && frame_step >= 0);
+  MVT_REQUIRE(levels >= 1 && levels <= 8 && lv && coords && N > 0 && S > 0 && T > 0 && frame0 >= 0 && frame0 < T);
   MVT_REQUIRE(K >= 1 && K <= 16 && (seed_k == 0 || (seed_k >= K && seed_k <= 64)));
   KnnLevels a{};
   for (int l = 0; l < levels; ++l) {
@@ -998,7 +1003,7 @@ extern "C" int mvt_corr_gather_dot(int levels, const float* const* xyz, const vo
                                    int frame0, int frame_step, int T, int K, float* out, int ldo, int o_off, void* stream) {
   MVT_REQUIRE(levels >= 1 && levels <= 8 && xyz && fvec && P && idx && targets && coords && out);
   MVT_REQUIRE((fvec_bf16 == 0 || fvec_bf16 == 1));
-  MVT_REQUIRE(N > 0 && S > 0 && T > 0 && frame0 >= 0 && frame0 < T && frame_step >= 0 && K >= 1 && K <= 16);
+  MVT_REQUIRE(N > 0 && S > 0 && T > 0 && frame0 >= 0 && frame0 < T && K >= 1 && K <= 16);
   MVT_REQUIRE(o_off >= 0 && ldo >= o_off + levels * 4 * K);
   CorrLevels lv{};
   for (int l = 0; l < levels; ++l) {
@@ -1109,7 +1114,7 @@ extern "C" int mvt_corr_gather_dot_opts(int levels, const float* const* xyz, con
                                         void* stream) {
   MVT_REQUIRE(levels >= 1 && levels <= 8 && xyz && fvec && P && idx && targets && coords && out);
   MVT_REQUIRE((fvec_bf16 == 0 || fvec_bf16 == 1) && (add_offset == 0 || add_offset == 1) && (add_xyz == 0 || add_xyz == 1));
-  MVT_REQUIRE(N > 0 && S > 0 && T > 0 && frame0 >= 0 && frame0 < T && frame_step >= 0 && K >= 1 && K <= 16);
+  MVT_REQUIRE(N > 0 && S > 0 && T > 0 && frame0 >= 0 && frame0 < T && K >= 1 && K <= 16);
   const int lpr = fvec_bf16 ? C / 8 : C / 4;  // lanes per feature row
   MVT_REQUIRE(groups >= 1 && (groups & (groups - 1)) == 0 && lpr >= 1 && groups <= lpr && lpr % groups == 0);
   const int OW = groups + 3 * add_offset + 3 * add_xyz;

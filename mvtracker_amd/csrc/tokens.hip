@@ -122,6 +122,66 @@ __global__ void window_store_kernel(const float* __restrict__ coords, const floa
   }
 }
 
+// The two kernels above for the time-reversed pass of backward tracking: the window starts at wr in REVERSED time (frame T-1-wr of
+// the clip) and slot s reads frame max(T-1-wr - s, 0), the tracks are sorted by descending query frame and qt holds the query frames
+// themselves.  This is window_prepare_kernel on the flipped clip written in the clip's own frame numbers: the mask is
+// (frame <= query frame) minus what earlier reversed windows covered, slots past the clip's start repeat frame 0.
+__global__ void window_prepare_reversed_kernel(const float* __restrict__ qxyz, const int* __restrict__ qt,
+                                               const float* __restrict__ feat_init, const float* __restrict__ prev_coords,
+                                               const float* __restrict__ prev_vis, int n, int p0, int S, int C, int wr, int T,
+                                               float* __restrict__ coords, float* __restrict__ mask_vis, float* __restrict__ ffeats) {
+  const long long total = (long long)n * S * (C / 4);
+  const int half = S / 2;
+  const int f0 = T - 1 - wr;  // the clip frame of slot 0
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int cq = (int)(i % (C / 4));
+    const long long row = i / (C / 4);  // tr * S + s
+    const int s = (int)(row % S);
+    const int tr = (int)(row / S);
+    *reinterpret_cast<f32x4*>(ffeats + row * C + cq * 4) = *reinterpret_cast<const f32x4*>(feat_init + (long long)tr * C + cq * 4);
+    if (cq == 0) {
+      const int sp = s < half ? half + s : S - 1;
+      const bool carried = tr < p0;
+      float vis = 10.0f;
+      if (carried) {
+        vis = prev_vis[(long long)tr * S + sp];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) coords[row * 3 + a] = prev_coords[((long long)tr * S + sp) * 3 + a];
+      } else {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) coords[row * 3 + a] = qxyz[(long long)tr * 3 + a];
+      }
+      const int S_local = T - wr < S ? T - wr : S;
+      const int f = f0 - (s < S_local ? s : S_local - 1);
+      const bool on = f <= qt[tr] && !(carried && f > f0 - half);
+      mask_vis[row * 2] = on ? 1.0f : 0.0f;
+      mask_vis[row * 2 + 1] = vis;
+    }
+  }
+}
+
+// Results of one reversed window: slot s is frame T-1-wr - s, and a row is written ONLY where that frame lies before the track's
+// query frame -- the frames from the query frame on belong to the forward pass, so the merge of the two passes is this predicate.
+__global__ void window_store_reversed_kernel(const float* __restrict__ coords, const float* __restrict__ vis,
+                                             const long long* __restrict__ order, const int* __restrict__ qt, int n, int S, int wr, int T,
+                                             int N, float* __restrict__ traj, float* __restrict__ vis_logit, float* __restrict__ vis_prob) {
+  const int S_local = T - wr < S ? T - wr : S;
+  const long long total = (long long)n * S_local;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int s = (int)(i % S_local);
+    const int tr = (int)(i / S_local);
+    const int f = T - 1 - wr - s;
+    if (f >= qt[tr]) continue;
+    const long long src = (long long)tr * S + s;
+    const long long dst = (long long)f * N + order[tr];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) traj[dst * 3 + a] = coords[src * 3 + a];
+    const float lg = vis[src];
+    vis_logit[dst] = lg;
+    vis_prob[dst] = 1.0f / (1.0f + expf(-lg));
+  }
+}
+
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w,
                                                         const float* __restrict__ b, float* __restrict__ y, int ldy, long long rows, int C,
                                                         float eps) {
@@ -272,6 +332,24 @@ extern "C" int mvt_window_store(const float* coords, const float* vis, const lon
   MVT_REQUIRE(coords && vis && order && traj && vis_logit && vis_prob && n > 0 && n <= N && S > 0 && w >= 0 && w < T);
   hipLaunchKernelGGL(window_store_kernel, dim3(grid_for((long long)n * S)), dim3(256), 0, mvt_stream(stream), coords, vis, order, n, S, w, T,
                      N, traj, vis_logit, vis_prob);
+  return mvt_launch_status();
+}
+
+extern "C" int mvt_window_prepare_reversed(const float* qxyz, const int* qt, const float* feat_init, const float* prev_coords,
+                                           const float* prev_vis, int n, int p0, int S, int C, int wr, int T, float* coords,
+                                           float* mask_vis, float* ffeats, void* stream) {
+  MVT_REQUIRE(qxyz && qt && feat_init && coords && mask_vis && ffeats && n > 0 && p0 >= 0 && p0 <= n && S >= 2 && C > 0 && C % 4 == 0);
+  MVT_REQUIRE(wr >= 0 && wr < T && (p0 == 0 || (prev_coords && prev_vis)));
+  hipLaunchKernelGGL(window_prepare_reversed_kernel, dim3(grid_for((long long)n * S * (C / 4))), dim3(256), 0, mvt_stream(stream), qxyz,
+                     qt, feat_init, prev_coords, prev_vis, n, p0, S, C, wr, T, coords, mask_vis, ffeats);
+  return mvt_launch_status();
+}
+
+extern "C" int mvt_window_store_reversed(const float* coords, const float* vis, const long long* order, const int* qt, int n, int S,
+                                         int wr, int T, int N, float* traj, float* vis_logit, float* vis_prob, void* stream) {
+  MVT_REQUIRE(coords && vis && order && qt && traj && vis_logit && vis_prob && n > 0 && n <= N && S > 0 && wr >= 0 && wr < T);
+  hipLaunchKernelGGL(window_store_reversed_kernel, dim3(grid_for((long long)n * S)), dim3(256), 0, mvt_stream(stream), coords, vis, order,
+                     qt, n, S, wr, T, N, traj, vis_logit, vis_prob);
   return mvt_launch_status();
 }
 

@@ -87,6 +87,8 @@ SIGNATURES = {
     "mvt_attn_block_fused_bf16": [P, I, P, P, P, P, P, P, P, I, P, I, LL, I, P, P],
     "mvt_window_prepare": [P, P, P, P, P, I, I, I, I, I, I, P, P, P, P],
     "mvt_window_store": [P, P, P, I, I, I, I, I, P, P, P, P],
+    "mvt_window_prepare_reversed": [P, P, P, P, P, I, I, I, I, I, I, P, P, P, P],
+    "mvt_window_store_reversed": [P, P, P, P, I, I, I, I, I, P, P, P, P],
     "mvt_track_metrics": [P, P, P, P, P, I, I, I, P, I, F, P, I, P],
     "mvt_encoder_workspace_bytes": [I, I, I, I],
     "mvt_encoder_forward": [P, P, I, I, I, P, I, I, P, LL, P],
@@ -544,6 +546,20 @@ def window_prepare(qxyz, qt, feat_init, prev_coords, prev_vis, n, p0, S, Cc, w, 
 def window_store(coords, vis, order, n, S, w, T, N, traj, vis_logit, vis_prob):
     assert order.dtype == torch.int64
     _call("mvt_window_store", _ptr(coords), _ptr(vis), _ptr(order), n, S, w, T, N, _ptr(traj), _ptr(vis_logit), _ptr(vis_prob), _stream())
+
+
+def window_prepare_reversed(qxyz, qt, feat_init, prev_coords, prev_vis, n, p0, S, Cc, wr, T, coords, mask_vis, ffeats):
+    """``window_prepare`` of the time-reversed pass: ``wr`` is the window start in reversed time, ``qt`` the query frames themselves."""
+    assert qt.dtype == torch.int32
+    _call("mvt_window_prepare_reversed", _ptr(_f32c(qxyz)), _ptr(qt), _ptr(_f32c(feat_init)), _ptr(prev_coords), _ptr(prev_vis), n, p0, S,
+          Cc, wr, T, _ptr(coords), _ptr(mask_vis), _ptr(ffeats), _stream())
+
+
+def window_store_reversed(coords, vis, order, qt, n, S, wr, T, N, traj, vis_logit, vis_prob):
+    """``window_store`` of the time-reversed pass: slot s goes to frame T-1-wr-s, only where that frame is before the row's query frame."""
+    assert order.dtype == torch.int64 and qt.dtype == torch.int32
+    _call("mvt_window_store_reversed", _ptr(coords), _ptr(vis), _ptr(order), _ptr(qt), n, S, wr, T, N, _ptr(traj), _ptr(vis_logit),
+          _ptr(vis_prob), _stream())
 
 
 def broadcast_rows(v, x, ld, n, S, Cc):

@@ -79,16 +79,21 @@ class ShardedTracker:
 
     @torch.no_grad()
     @hip.guarded
-    def __call__(self, rgbs, depths, query_points, intrs, extrs, iters=4, gather_output=True):
+    def __call__(self, rgbs, depths, query_points, intrs, extrs, iters=4, gather_output=True, backward_tracking=False):
         world, rank = self._world()
         m = self.model
+        # (backward_tracking is MVTracker.forward's option: the shards are independent forwards over the shared store, which then
+        #  has to hold the frames before the first query frame too -- no new collective)
+        opts = dict(backward_tracking=True) if backward_tracking else {}
         if world == 1 and not (os.environ.get("MVT_FORCE_SHARDED") and dist.is_available() and dist.is_initialized()):
-            return m(rgbs, depths, query_points, intrs, extrs, iters=iters)
+            return m(rgbs, depths, query_points, intrs, extrs, iters=iters, **opts)
         _, V, T, _, H, W = rgbs.shape
         N = query_points.shape[1]
         a, b = self.shard_bounds(N, world, rank)
         assert b > a, "fewer queries than ranks"
         t0 = int(query_points[0, :, 0].long().min().item())  # global first frame: identical on every rank
+        if backward_tracking:
+            t0 = min(t0, 0)  # the reversed pass reads the store down to frame 0
         store = None
         if t0 < T - m.S // 2:
             f32 = lambda t: t.to(torch.float32).contiguous()
@@ -147,7 +152,7 @@ class ShardedTracker:
                 exchange_block(first_end, T)
                 m.fill_frame_features(store, r0, first_end, T, level0=level0)
         self.last_store = store
-        res = m(rgbs, depths, query_points[:, a:b], intrs, extrs, iters=iters, frame_store=store)
+        res = m(rgbs, depths, query_points[:, a:b], intrs, extrs, iters=iters, frame_store=store, **opts)
         if not gather_output:
             # (the caller owns the deferred NaN check -- and with more than one rank it must be check_finite_collective(): a rank
             #  that raised on model.check_finite() alone would leave its peers blocked in their next collective)

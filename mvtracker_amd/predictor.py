@@ -83,6 +83,7 @@ class EvaluationPredictor(torch.nn.Module):
             sift_size: int = 0,
             num_uniformly_sampled_pts: int = 0,
             n_iters: int = 6,
+            backward_tracking: bool = False,
     ) -> None:
         super().__init__()
         self.model = multiview_model
@@ -96,6 +97,9 @@ class EvaluationPredictor(torch.nn.Module):
         self.sift_size = sift_size
         self.num_uniformly_sampled_pts = num_uniformly_sampled_pts
         self.n_iters = n_iters
+        # also track every query BEFORE its frame (MVTracker.forward(backward_tracking=True): a time-reversed pass over the same
+        # frame store); not in the reference's constructor, off by default
+        self.backward_tracking = bool(backward_tracking)
         self.single_point_streams = 8  # HIP streams the per-query forwards of single_point mode are spread over
         # single_point mode: consecutive queries per MVTracker.forward_grouped call (each keeps its own rows and softmax);
         # 1 = one forward per query.  (An attribute, not a constructor argument: the constructor mirrors the reference's.)
@@ -210,6 +214,11 @@ class EvaluationPredictor(torch.nn.Module):
         nan_flags = []
         fwd = dict(intrs=intrs, extrs=extrs, iters=self.n_iters, save_debug_logs=save_debug_logs,
                    debug_logs_path=debug_logs_path, query_points_view=query_points_view, **kwargs)
+        if self.backward_tracking:
+            if self.single_point and int(self.single_point_group_size) > 1:
+                raise NotImplementedError("backward_tracking with single_point_group_size > 1: forward_grouped has no backward tracking "
+                                          "(use group size 1)")
+            fwd["backward_tracking"] = True
         if self.single_point:  # :191-339, one forward per query with its local grids
             traj_e = torch.zeros(1, T, num_points, 3, device=dev)
             vis_e = torch.zeros(1, T, num_points, device=dev)
@@ -220,7 +229,8 @@ class EvaluationPredictor(torch.nn.Module):
             # frames >= its own first query frame only, so one store from the earliest query frame serves them all.
             if hasattr(self.model, "build_frame_store"):
                 f32 = lambda t_: t_.to(torch.float32).contiguous()
-                t_first = 0 if (self.grid_size > 0 or not qt) else max(0, min(qt))  # (the global support grid starts at frame 0)
+                # (the global support grid starts at frame 0; backward tracking reads every frame before a query's too)
+                t_first = 0 if (self.grid_size > 0 or self.backward_tracking or not qt) else max(0, min(qt))
                 r0 = rgbs[0].contiguous() if rgbs.dtype == torch.uint8 else f32(rgbs[0])
                 fwd["frame_store"] = self.model.build_frame_store(r0, f32(depths[0]), f32(intrs[0]), f32(extrs[0]),
                                                                   t0=t_first)

@@ -27,6 +27,7 @@ import torch
 from torch import nn
 
 from . import hip
+from .backward import reversed_layout, window_prefixes
 from .grouped import grouped_layout
 
 log = logging.getLogger(__name__)
@@ -657,11 +658,13 @@ class MVTracker(nn.Module):
             self._side[key] = torch.cuda.Stream(device=dev)
         return self._side[key]
 
-    def _encode_on_side_stream(self, store, rgbs, firsts, pending):
+    def _encode_on_side_stream(self, store, rgbs, firsts, pending, end=None):
         """Encode the S/2-frame blocks starting at ``firsts`` on the second HIP stream (ordered after everything enqueued on the
-        caller's stream so far); ``pending`` receives (first frame, event) per block."""
+        caller's stream so far); ``pending`` receives (first frame, event) per block.  ``end``: the blocks stop at this frame
+        (default: the clip's end)."""
         dev = rgbs.device
-        T, S = rgbs.shape[1], self.S
+        S = self.S
+        T = rgbs.shape[1] if end is None else min(end, rgbs.shape[1])
         # (the later blocks stay on ONE stream, in order: alternating them between two streams as encode_images does for the chunks
         #  of the first block measured +0.5 ms -- beside the updater their concurrency only adds contention)
         streams = [self._side_stream(dev)]
@@ -670,7 +673,7 @@ class MVTracker(nn.Module):
         self._handover(dev)
         # these blocks run BESIDE the refinement windows: short-lived workgroups only, unless the encoder bounds the call anyway
         V = rgbs.shape[0]
-        first_block = max(1, min(T, S)) * V
+        first_block = max(1, min(rgbs.shape[1], S)) * V
         side_images = sum(min(T, a + S // 2) - a for a in firsts) * V
         big = self.wide_conv_shared == "1" or (self.wide_conv_shared == "auto" and side_images > 2 * first_block)
         for i, a in enumerate(firsts):
@@ -773,6 +776,7 @@ class MVTracker(nn.Module):
         # orders itself after store["geo_event"], not after the encoder.  ``geometry``: already enqueued by the caller (store_geometry).
         store = dict(geometry) if geometry is not None else self.store_geometry(depths, intrs, extrs)
         store["fvec"] = fv
+        store["feat_t0"] = t0  # features exist for frames [t0, T) (backward tracking needs t0 == 0)
         self.fill_frame_features(store, rgbs, t0, t1, level0, after_first_chunk=(lambda: after_geometry(store)) if after_geometry else None)
         return store
 
@@ -1058,11 +1062,14 @@ class MVTracker(nn.Module):
         mask_vis = torch.stack([track_mask.float(), vis_init.float()], dim=2).contiguous()
         return self._refine(store, frame0, coords, ffeats, mask_vis, iters, nan_flag, trace)
 
-    def _refine(self, store, frame0, coords, ffeats, mask_vis, iters=4, nan_flag=None, trace=None, carry=None, pre_idx=None, seg=None):
+    def _refine(self, store, frame0, coords, ffeats, mask_vis, iters=4, nan_flag=None, trace=None, carry=None, pre_idx=None, seg=None,
+                frame_step=1):
         """The refinement loop (mvtracker.py:350-408) on prepared state: coords (n,S,3) and ffeats (n,S,C) are updated IN PLACE,
         mask_vis (n,S,2) = (track mask, initial visibility logit).  Returns ([coords per traced iteration ..., final], vis).
         ``carry`` = (neighbour indices (L,n_prev,S,K) of the previous window's last iteration, p0): the first p0 tracks continue
-        from that window, so its neighbours seed (bound) this window's first exact scan.  ``self._last_idx`` holds this window's."""
+        from that window, so its neighbours seed (bound) this window's first exact scan.  ``self._last_idx`` holds this window's.
+        ``frame_step``: slot s reads store frame clamp(frame0 + s * frame_step, 0, T-1); -1 is the time-reversed pass of backward
+        tracking (the seeding above works in slot space and is the same in both directions)."""
         S, C, K, L, E = self.S, self.latent_dim, self.corr_neighbors, self.corr_n_levels, self.flow_embed_dim
         n = coords.shape[0]
         dev = coords.device
@@ -1096,9 +1103,9 @@ class MVTracker(nn.Module):
             if it > 0:
                 # every level is seeded by its own previous neighbours: the four scans are independent -> one launch
                 if self.knn_one_launch:
-                    hip.knn_search_levels(levels, coords, n, S, frame0, 1, T, K, seed_k=K)
+                    hip.knn_search_levels(levels, coords, n, S, frame0, frame_step, T, K, seed_k=K)
                 else:
-                    hip.knn_scan_levels(levels, coords, n, S, frame0, 1, T, K, seed_k=K)
+                    hip.knn_scan_levels(levels, coords, n, S, frame0, frame_step, T, K, seed_k=K)
                     hip.knn_merge_levels(levels, n, S, K)
             else:
                 n0 = 0
@@ -1116,9 +1123,9 @@ class MVTracker(nn.Module):
                     seed_t = prev_idx[:, :n0].index_select(2, slot).contiguous()
                     lv0 = [dict(lv, keys=keys[l_][:n0 * S * nsegs[l_] * K], seed_idx=seed_t[l_], idx_out=idx[l_][:n0]) for l_, lv in enumerate(levels)]
                     if self.knn_one_launch:
-                        hip.knn_search_levels(lv0, coords, n0, S, frame0, 1, T, K, seed_k=K)
+                        hip.knn_search_levels(lv0, coords, n0, S, frame0, frame_step, T, K, seed_k=K)
                     else:
-                        hip.knn_scan_levels(lv0, coords, n0, S, frame0, 1, T, K, seed_k=K)
+                        hip.knn_scan_levels(lv0, coords, n0, S, frame0, frame_step, T, K, seed_k=K)
                         hip.knn_merge_levels(lv0, n0, S, K)
                 # rows [n1, n) were searched ahead of time (``pre_idx``: the tracks that enter at this window, i.e. everything behind the
                 # carried ones); rows [n0, n1) still need their first, unseeded search -- empty unless the carried tracks were not seeded
@@ -1131,7 +1138,7 @@ class MVTracker(nn.Module):
                     # nearest full tile) -- 262 us against four dependent coarse-to-fine launches of ~100 us each
                     m = n1 - n0
                     lv1 = [dict(lv, seed_idx=None, idx_out=idx[l_][n0:n1]) for l_, lv in enumerate(levels)]
-                    hip.knn_search_levels(lv1, coords[n0:n1], m, S, frame0, 1, T, K, seed_k=0)
+                    hip.knn_search_levels(lv1, coords[n0:n1], m, S, frame0, frame_step, T, K, seed_k=0)
                 else:  # new tracks: coarse to fine, level l+1's neighbours bound level l's first scan
                     m = n1 - n0
                     for lvl in reversed(range(L)):
@@ -1141,19 +1148,19 @@ class MVTracker(nn.Module):
                             seed = dict(seed_idx=idx[lvl + 1][n0:n1], seed_k=K,
                                         seed_dims=(grid[lvl + 1][1], grid[lvl + 1][0], grid[lvl][1], grid[lvl][0]))
                         if self.knn_one_launch:
-                            hip.knn_search(store["xyz"][lvl], P, coords[n0:n1], m, S, frame0, 1, T, K, idx[lvl][n0:n1], store["box"][lvl],
+                            hip.knn_search(store["xyz"][lvl], P, coords[n0:n1], m, S, frame0, frame_step, T, K, idx[lvl][n0:n1], store["box"][lvl],
                                            grid=store["tile_grid"][lvl], gbox=store["gbox"][lvl], **seed)
                             continue
                         kl = keys[lvl][n0 * S * nsegs[lvl] * K:n1 * S * nsegs[lvl] * K]
-                        hip.knn_scan(store["xyz"][lvl], P, coords[n0:n1], m, S, frame0, 1, T, K, nsegs[lvl], kl, box=store["box"][lvl],
+                        hip.knn_scan(store["xyz"][lvl], P, coords[n0:n1], m, S, frame0, frame_step, T, K, nsegs[lvl], kl, box=store["box"][lvl],
                                      grid=store["tile_grid"][lvl], **seed)
                         hip.knn_merge(kl, m, S, K, nsegs[lvl], P, idx[lvl][n0:n1])
             if default_corr:
                 hip.corr_gather_dot(store["xyz"], store["fvec"], store["P"], [idx[lvl] for lvl in range(L)], C, ffeats, coords, n, S, frame0,
-                                    1, T, K, fcorr, Fc, 0)
+                                    frame_step, T, K, fcorr, Fc, 0)
             else:  # the reference's non-default correlation layouts (grouped dots, no offsets, neighbour coordinates)
                 hip.corr_gather_dot_opts(store["xyz"], store["fvec"], store["P"], [idx[lvl] for lvl in range(L)], C, ffeats, coords, n, S,
-                                         frame0, 1, T, K, self.corr_n_groups, self.corr_add_neighbor_offset, self.corr_add_neighbor_xyz,
+                                         frame0, frame_step, T, K, self.corr_n_groups, self.corr_add_neighbor_offset, self.corr_add_neighbor_xyz,
                                          fcorr, Fc, 0)
             hook = getattr(self, "_after_first_corr", None)
             if hook is not None:  # (forward: the later frame blocks' encoder starts on the second stream now)
@@ -1216,8 +1223,12 @@ class MVTracker(nn.Module):
             save_rerun_logs_output_rrd_path: Optional[str] = None,
             frame_store: Optional[dict] = None,
             trace: Optional[list] = None,
+            backward_tracking: bool = False,
             **kwargs,
     ):
+        """``backward_tracking``: also fill the frames BEFORE each query's frame, from a time-reversed pass over the same frame store
+        (``mvtracker_amd.backward``).  Frames from the query frame on are the same bits with the option on or off.
+        The reversed pass's windows are left in ``last_windows_backward`` as (start in reversed time, active tracks)."""
         if is_train:
             raise NotImplementedError("inference only: the MI355X path has no backward")
         if save_debug_logs or save_rerun_logs:
@@ -1262,7 +1273,25 @@ class MVTracker(nn.Module):
         # (through a cached PINNED staging buffer, asynchronously: from pageable memory each copy is a host-blocking staged transfer --
         #  ~60 us of idle GPU apiece in the kernel trace.  The buffer may be rewritten by the next call: its host sync above comes
         #  after these copies in stream order)
-        order_d, qt_sd = self._upload_small(dev, order.astype(np.int64), qt_s.astype(np.int32))
+        # backward tracking: the reversed pass's rows and windows, known on the host from here on (their index arrays ride in the same
+        # upload); ``back`` stays None when no reversed window runs, and the call is then the plain forward
+        back = reversed_layout(qt, S, T) if backward_tracking else None
+        if back is not None and not back["windows"]:
+            back = None
+        small = [order.astype(np.int64), qt_s.astype(np.int32)]
+        fix_rows = np.zeros(0, dtype=np.int64)
+        if back is not None:
+            # rows of feat_init (sorted by query frame) that only the reversed pass reaches take that pass's feature row
+            fwd = window_prefixes(qt_s, S, T)
+            inv_b = np.empty(N, dtype=np.int64)
+            inv_b[back["order"]] = np.arange(N)
+            tail = np.arange(fwd[-1][1] if fwd else 0, N)
+            fix_rows = tail[inv_b[order[tail]] < back["active"]]
+            small += [back["order"].astype(np.int64), back["sorted_qt"].astype(np.int32)]
+            if len(fix_rows):
+                small += [fix_rows, inv_b[order[fix_rows]]]
+        small_d = self._upload_small(dev, *small)
+        order_d, qt_sd = small_d[:2]
         # (N,3) query points sorted by start frame -- enqueued HERE, ahead of the geometry: the searches issued on the second stream
         # order themselves after the geometry event only, and they read these rows)
         qxyz = query_points[order_d, 1:].contiguous()
@@ -1334,12 +1363,31 @@ class MVTracker(nn.Module):
                 ev.record(side)
             pre["event"] = ev
 
+        # backward tracking reads the frames before the first forward window too: first frames of the S/2-frame blocks of
+        # [0, w) still to encode, and (first frame, event) of those in flight on the second stream
+        early = list(range(0, max(w, 0), S // 2)) if back is not None and frame_store is None else []
+        pending_back = []
+        store = None
+
+        def encode_early():
+            """The frames only the reversed pass reads, on the second stream BEHIND the forward pass's blocks (hand-over H3)."""
+            if early:
+                firsts = list(early)
+                del early[:]
+                self._encode_on_side_stream(store, rgbs, firsts, pending_back, end=max(w, 0))
+
+        if back is not None and frame_store is not None and frame_store.get("feat_t0", 0) > 0:
+            raise ValueError(f"backward_tracking needs a frame store with features from frame 0 on (queries up to frame {int(qt.max())} are "
+                             f"tracked back to the clip's start), but the supplied frame_store was built from frame "
+                             f"{frame_store['feat_t0']}: build it with t0=0")
         if w < T - S // 2:
             if frame_store is not None:
                 store = frame_store
                 pending = list(frame_store.get("pending", ()))  # (first frame, event) of feature blocks still in flight
             elif not self.overlap_encoder or max(w, 0) + S >= T or dev.type != "cuda":
-                store = self.build_frame_store(rgbs, depths, intrs, extrs, t0=max(w, 0), after_geometry=presearch, geometry=geometry)
+                store = self.build_frame_store(rgbs, depths, intrs, extrs, t0=0 if back is not None else max(w, 0), after_geometry=presearch,
+                                               geometry=geometry)
+                del early[:]
             else:
                 # The first window needs frames [w, w+S).  The remaining frames are encoded on a second HIP stream while
                 # the updater of the earlier windows runs: its kernels over the 64 virtual tracks fill a fraction of the
@@ -1353,10 +1401,14 @@ class MVTracker(nn.Module):
                     # start in the same instant as the second stream's first convolutions
                     if self.side_after_corr:
                         chunks_now = side_chunks
-                        self._after_first_corr = lambda: self._encode_on_side_stream(store, rgbs, chunks_now, pending)
+                        self._after_first_corr = lambda: (self._encode_on_side_stream(store, rgbs, chunks_now, pending), encode_early())
                     else:
                         self._encode_on_side_stream(store, rgbs, side_chunks, pending)
+                        encode_early()
                     side_chunks = []
+        elif back is not None:  # no forward window (every query within the clip's last S/2 frames): the reversed pass still needs a store
+            store = frame_store if frame_store is not None else self.build_frame_store(rgbs, depths, intrs, extrs, t0=0, geometry=geometry)
+            del early[:]
         sd_ = make_state()
         traj, vis_prob, vis_logit = sd_["traj"], sd_["vis_prob"], sd_["vis_logit"]
         feat_init, nan_flag = sd_["feat_init"], sd_["nan_flag"]
@@ -1419,7 +1471,52 @@ class MVTracker(nn.Module):
             hook()
         for _, ev in pending:  # frames no window consumed: still join the side stream before the inputs are released
             torch.cuda.current_stream(dev).wait_event(ev)  # hand-over H7: the caller's inputs (read by the second stream) are released
+        windows_b = []
+        if back is not None:
+            # ---- the time-reversed pass (one stream): the same window loop on the same store, slots running downwards from frame
+            # T-1-wr.  Its store kernel writes only frames before each row's query frame, which IS the merge of the two passes.
+            encode_early()  # (only the deferred-encoder variant gets here with blocks left)
+            for _, ev in pending_back + list(store.get("pending", ()) if frame_store is not None else ()):
+                torch.cuda.current_stream(dev).wait_event(ev)  # hand-over H5 for the early frames
+            if pending_back:
+                self._handover(dev)
+            order_bd, qt_bd = small_d[2:4]
+            nb = back["active"]
+            qxyz_b = query_points[order_bd, 1:].contiguous()
+            feat_b = torch.zeros(N, C, device=dev)
+            P0 = store["P"][0]
+            ns = self._nseg(P0, 1)
+            neg_qt = -back["sorted_qt"][:nb]  # (ascending)
+            a = 0
+            while a < nb:  # feature init of the reversed pass's rows (:607-645): the same query frame, the same 1-NN
+                t = -int(neg_qt[a])
+                b = int(np.searchsorted(neg_qt, -t, side="right"))
+                keys = torch.empty((b - a) * ns, device=dev, dtype=torch.int64)
+                hip.knn_scan(store["xyz"][0], P0, qxyz_b[a:b], b - a, 1, t, 0, T, 1, ns, keys, box=store["box"][0], grid=store["tile_grid"][0])
+                hip.knn1_gather(store["fvec"][0], P0, C, keys, b - a, ns, t, feat_b[a:b])
+                a = b
+            if len(fix_rows):
+                feat_init.index_copy_(0, small_d[4], feat_b.index_select(0, small_d[5]))
+            p0 = 0
+            coords = vis = prev_idx = None
+            for (wr, p1), f0 in zip(back["windows"], back["frame0"]):
+                wc = torch.empty(p1, S, 3, device=dev)
+                wf = torch.empty(p1, S, C, device=dev)
+                wm = torch.empty(p1, S, 2, device=dev)
+                hip.window_prepare_reversed(qxyz_b, qt_bd, feat_b, coords, vis, p1, p0, S, C, wr, T, wc, wm, wf)
+                wtrace = None
+                if trace is not None:
+                    wtrace = dict(reversed_window=wr)
+                    trace.append(wtrace)
+                preds, vis = self._refine(store, f0, wc, wf, wm, iters=iters, nan_flag=nan_flag, trace=wtrace,
+                                          carry=(prev_idx, p0) if p0 > 0 else None, frame_step=-1)
+                prev_idx = self._last_idx
+                coords = preds[-1]
+                hip.window_store_reversed(coords, vis, order_bd, qt_bd, p1, S, wr, T, N, traj, vis_logit, vis_prob)
+                windows_b.append((wr, p1))
+                p0 = p1
         self.last_windows = windows
+        self.last_windows_backward = windows_b
         self.last_vis_logits = vis_logit[None]
         self.last_nan_flag = nan_flag
         results = {
@@ -1432,7 +1529,7 @@ class MVTracker(nn.Module):
     @torch.no_grad()
     @hip.guarded
     def forward_grouped(self, rgbs, depths, query_points_list, intrs, extrs, iters=4, frame_store=None, trace=None, is_train=False,
-                        save_debug_logs=False, save_rerun_logs=False, **kwargs):
+                        save_debug_logs=False, save_rerun_logs=False, backward_tracking=False, **kwargs):
         """G independent ``forward`` calls through one launch sequence: query_points_list[g] (1,N_g,4) is a query set of its own
         (its own windows, its own 64 virtual tracks, its own softmax in the space attentions).  Returns one result dict per group,
         with the keys, shapes and dtypes of ``forward``'s.  Groups whose first windows coincide run in the same windows; the rows
@@ -1441,6 +1538,9 @@ class MVTracker(nn.Module):
         other options are ``forward``'s and are handled as there (no training; the reference's logging hooks are ignored)."""
         if is_train:
             raise NotImplementedError("inference only: the MI355X path has no backward")
+        if backward_tracking:
+            raise NotImplementedError("forward_grouped has no backward_tracking (per-set directions inside one launch sequence are not "
+                                      "built): call forward(..., backward_tracking=True) per query set")
         if save_debug_logs or save_rerun_logs:
             log.warning("save_debug_logs / save_rerun_logs are host-side visualisation hooks of the reference; ignored")
         if not isinstance(query_points_list, (list, tuple)) or not query_points_list:
