@@ -494,11 +494,17 @@ def attention_ws_floats(groups, nq, heads):
     return 4 * groups * heads * ((nq + 63) // 64) * 64 * 68
 
 
-def attention_bf16(q, ldq, q_gs, q_is, k, v, ldkv, k_gs, k_is, o, ldo, groups, nq, nk, heads, dh, ws=None):
+ATTN_PARTIALS_ONLY = 8  # MVT_ATTN_PARTIALS_ONLY
+ATTN_NSPLIT = 4         # MVT_ATTN_NSPLIT
+
+
+def attention_bf16(q, ldq, q_gs, q_is, k, v, ldkv, k_gs, k_is, o, ldo, groups, nq, nk, heads, dh, ws=None, partials_only=False):
+    """``partials_only``: stop after the key-split partials in ``ws`` (MVT_ATTN_PARTIALS_ONLY; ``o`` is not written) -- the
+    library refuses it unless the key-split form is the one this call takes."""
     assert q.dtype == k.dtype == v.dtype
     assert ws is None or (ws.dtype == torch.float32 and ws.numel() >= attention_ws_floats(groups, nq, heads))
     _call("mvt_attention_bf16", _ptr(q), ldq, q_gs, q_is, _ptr(k), _ptr(v), ldkv, k_gs, k_is, _ptr(o), ldo, groups, nq, nk, heads,
-          dh, _io(q, o), _ptr(ws), _stream())
+          dh, _io(q, o) | (ATTN_PARTIALS_ONLY if partials_only else 0), _ptr(ws), _stream())
 
 
 def _segments(q_row0, nq, k_row0, nk):
@@ -623,7 +629,7 @@ def update_head_bf16(tok, ldt, w0, b0, w2, b2, w4, b4, gn_w, gn_b, wu, bu, coord
           _ptr(bu), _ptr(coords), _ptr(ffeats), _ptr(delta), ldd, rows, hidden, out_dim, _ptr(nan_flag), _stream())
 
 
-ATTN_TIME, ATTN_FRAME = 1, 2
+ATTN_TIME, ATTN_FRAME, ATTN_PARTIALS = 1, 2, 3
 
 
 class BlockAttn(C.Structure):
@@ -633,10 +639,14 @@ class BlockAttn(C.Structure):
                 ("defer_pass2", C.c_int), ("ctx", C.c_void_p)]  # (the context form is only driven by the composite updater call)
 
 
-def attn_block_fused_bf16(x, ldx, kind, S, q, ldq, k, v, ldkv, n_keys, wo, bo, w1, b1, w2, b2, H, nexts, M, Cc, ws=None):
-    """``block_fused_bf16`` with the preceding attention inside the kernel (bf16 q / k / v; 6 heads x 48)."""
-    assert q.dtype == k.dtype == v.dtype == torch.bfloat16
-    at = BlockAttn(kind, S, n_keys, 6, 48, ldq, ldkv, _ptr(q), _ptr(k), _ptr(v), None, 0)
+def attn_block_fused_bf16(x, ldx, kind, S, q, ldq, k, v, ldkv, n_keys, wo, bo, w1, b1, w2, b2, H, nexts, M, Cc, ws=None, partials=None,
+                          n_splits=0, defer_pass2=False):
+    """``block_fused_bf16`` with the preceding attention inside the kernel (bf16 q / k / v; 6 heads x 48).
+    ``ATTN_PARTIALS``: q / k / v are None and ``partials`` is the workspace that ``attention_bf16(..., partials_only=True)``
+    left (``n_splits`` = ATTN_NSPLIT states per chunk).  ``defer_pass2``: split-path forms launch pass 1 only."""
+    assert kind == ATTN_PARTIALS or q.dtype == k.dtype == v.dtype == torch.bfloat16
+    assert partials is None or partials.dtype == torch.float32
+    at = BlockAttn(kind, S, n_keys, 6, 48, ldq, ldkv, _ptr(q), _ptr(k), _ptr(v), _ptr(partials), n_splits, 1 if defer_pass2 else 0, None)
     arr = (BlockNext * max(1, len(nexts)))()
     for i, nx in enumerate(nexts):
         arr[i] = BlockNext(_ptr(nx["w"]), _ptr(nx["b"]), _ptr(nx.get("lnw")), _ptr(nx.get("lnb")), _ptr(nx["y"]), nx["ldw"], nx["N"],
