@@ -60,6 +60,17 @@ def _round_up(a: int, b: int) -> int:
     return (a + b - 1) // b * b
 
 
+def _f32(t, dev):
+    return t.to(device=dev, dtype=torch.float32).contiguous()
+
+
+def _call_outputs(dev, T, N, C):
+    """Device-side results of one tracking call: trajectories and visibilities (un-sorted by the window store kernels, zero
+    where no window writes), the initial feature rows in sorted order, the deferred NaN flag."""
+    return dict(traj=torch.zeros(T, N, 3, device=dev), vis_prob=torch.zeros(T, N, device=dev), vis_logit=torch.zeros(T, N, device=dev),
+                feat_init=torch.zeros(N, C, device=dev), nan_flag=torch.zeros(1, device=dev, dtype=torch.int32))
+
+
 class _Shifted:
     """View of a tensor whose row ``i`` is ``base[i - shift]`` (slice access only)."""
 
@@ -166,20 +177,16 @@ class MVTracker(nn.Module):
         # latency-bound correlation gather -- of CU slots), "1" always, "auto": when the encoder, not the windows, bounds the call
         # (the second stream has more than twice the images of the first block; BASELINE config C5: -6 % per step)
         self.wide_conv_shared = os.environ.get("MVT_CONV_BIG_SHARED", "auto")
-        self._shared_gpu = False  # set around the encoder calls issued beside the windows
-        self.side_after_corr = os.environ.get("MVT_SIDE_AFTER_CORR", "1") != "0"  # second-stream encoder starts behind the first correlation
+        self._shared_gpu = False  # set around the encoder calls issued beside the windows (``_beside_windows``)
         # MVT_SYNC_DEBUG=1: synchronise the whole device at every cross-stream hand-over of a call ("hand-over
         # table"): if results change with it, an event / wait_stream is missing somewhere (tests: bit-identical with and without)
         self.sync_debug = os.environ.get("MVT_SYNC_DEBUG", "0") != "0"
-        self.defer_encoder = os.environ.get("MVT_ENC_DEFER", "0") != "0"  # one block of later frames per window on the side stream (A/B: no gain at C3)
-        self.knn_one_launch = os.environ.get("MVT_KNN_ONE_LAUNCH", "1") != "0"  # seeded scans: one wave per (track, frame), no merge launch
         self.composite_encoder = os.environ.get("MVT_COMPOSITE_ENCODER", "1") != "0"  # the CNN as one library call (bf16 mode)
         self.fuse_tokens = os.environ.get("MVT_FUSE_TOKENS", "1") != "0"  # ... with the token rows assembled inside that launch
         self.fuse_input = os.environ.get("MVT_FUSE_INPUT", "1") != "0"  # input transform + virtual tokens + first q|k|v in one launch
         self.fuse_head = os.environ.get("MVT_FUSE_HEAD", "1") != "0"  # flow head + track / feature update in one kernel
         self.fuse_norm = True  # InstanceNorm statistics from the conv epilogue + normalise-on-load (bf16 / bf16x3 convs)
         self.fold_downsample = os.environ.get("MVT_FOLD_DOWNSAMPLE", "1") != "0"  # strided blocks: conv1 + downsample[0] in one launch
-        self.fuse_ln = False
         d = self.updateformer_input_dim
         self._time_embed_host = self._make_time_embed(self.S, d)
 
@@ -658,6 +665,16 @@ class MVTracker(nn.Module):
             self._side[key] = torch.cuda.Stream(device=dev)
         return self._side[key]
 
+    @contextlib.contextmanager
+    def _beside_windows(self, short_workgroups=True):
+        """Encoder calls issued inside run BESIDE the refinement windows: short-lived workgroups only (MVT_IO_SHORT_WG, the
+        ``encoder_struct_shared`` weights; bit-identical results) unless ``short_workgroups`` is off (``wide_conv_shared``)."""
+        self._shared_gpu = short_workgroups
+        try:
+            yield
+        finally:
+            self._shared_gpu = False
+
     def _encode_on_side_stream(self, store, rgbs, firsts, pending, end=None):
         """Encode the S/2-frame blocks starting at ``firsts`` on the second HIP stream (ordered after everything enqueued on the
         caller's stream so far); ``pending`` receives (first frame, event) per block.  ``end``: the blocks stop at this frame
@@ -679,11 +696,8 @@ class MVTracker(nn.Module):
         for i, a in enumerate(firsts):
             st = streams[i % len(streams)]
             with torch.cuda.stream(st):
-                self._shared_gpu = not big
-                try:
+                with self._beside_windows(short_workgroups=not big):
                     self.fill_frame_features(store, rgbs, a, min(T, a + S // 2))
-                finally:
-                    self._shared_gpu = False
                 ev = torch.cuda.Event()
                 ev.record(st)
                 pending.append((a, ev))
@@ -797,13 +811,9 @@ class MVTracker(nn.Module):
             hip.gemm(A, lda, wp, wp.shape[1], b, R, ldr, out, ldc, M, n, k, act)
 
     def _ln_lin(self, pk, name, x, rows, out, ldc, scratch, ln_w=None, ln_b=None, eps=1e-6, act=hip.ACT_NONE):
-        """out = act(LayerNorm(x) @ W^T + b).  mvt_ln_gemm_bf16 (LayerNorm inside the GEMM's A loader) exists but measured
-        slower than the separate 7 us LayerNorm pass + GEMM (every column tile recomputes the row statistics), so it is off."""
+        """out = act(LayerNorm(x) @ W^T + b).  (mvt_ln_gemm_bf16, LayerNorm inside the GEMM's A loader, measured slower than
+        the separate 7 us LayerNorm pass + GEMM -- every column tile recomputes the row statistics -- and is not used here.)"""
         h = self.hidden
-        wp, b, n, k = pk[name]
-        if isinstance(wp, tuple) and self.fuse_ln:
-            hip.ln_gemm_bf16(x, h, ln_w, ln_b, eps, wp[0], wp[1], wp[0].shape[1], b, None, 0, out, ldc, rows, n, k, act)
-            return
         hip.layernorm(x, h, ln_w, ln_b, scratch, h, rows, h, eps)
         self._lin(pk, name, scratch, h, rows, out, ldc, act)
 
@@ -1060,16 +1070,18 @@ class MVTracker(nn.Module):
         coords = coords.contiguous().clone()
         ffeats = feat_init.contiguous().clone()
         mask_vis = torch.stack([track_mask.float(), vis_init.float()], dim=2).contiguous()
-        return self._refine(store, frame0, coords, ffeats, mask_vis, iters, nan_flag, trace)
+        return self._refine(store, frame0, coords, ffeats, mask_vis, iters, nan_flag, trace)[:2]
 
     def _refine(self, store, frame0, coords, ffeats, mask_vis, iters=4, nan_flag=None, trace=None, carry=None, pre_idx=None, seg=None,
-                frame_step=1):
+                frame_step=1, after_first_corr=None):
         """The refinement loop (mvtracker.py:350-408) on prepared state: coords (n,S,3) and ffeats (n,S,C) are updated IN PLACE,
-        mask_vis (n,S,2) = (track mask, initial visibility logit).  Returns ([coords per traced iteration ..., final], vis).
-        ``carry`` = (neighbour indices (L,n_prev,S,K) of the previous window's last iteration, p0): the first p0 tracks continue
-        from that window, so its neighbours seed (bound) this window's first exact scan.  ``self._last_idx`` holds this window's.
+        mask_vis (n,S,2) = (track mask, initial visibility logit).  Returns ([coords per traced iteration ..., final], vis,
+        neighbour indices (L,n,S,K) of the last iteration).
+        ``carry`` = (those indices of the previous window, p0): the first p0 tracks continue from that window, so its neighbours
+        seed (bound) this window's first exact scan.
         ``frame_step``: slot s reads store frame clamp(frame0 + s * frame_step, 0, T-1); -1 is the time-reversed pass of backward
-        tracking (the seeding above works in slot space and is the same in both directions)."""
+        tracking (the seeding above works in slot space and is the same in both directions).
+        ``after_first_corr``: host callback, called once right behind the first correlation launch (``_plan_frame_store``)."""
         S, C, K, L, E = self.S, self.latent_dim, self.corr_neighbors, self.corr_n_levels, self.flow_embed_dim
         n = coords.shape[0]
         dev = coords.device
@@ -1086,27 +1098,20 @@ class MVTracker(nn.Module):
         ldd = _round_up(self.out_dim, 4)
         delta = torch.empty(n * S, ldd, device=dev)  # (out_dim columns are written and read; the pad column is never read)
         dn = torch.empty(n * S, C, device=dev)
-        nsegs = [self._nseg(store["P"][lvl], K) for lvl in range(L)]
-        keys = [torch.empty(n * S * nsegs[lvl] * K, device=dev, dtype=torch.int64) for lvl in range(L)]
         # neighbour indices of every level: returned for tracing AND used to seed (prune) the next exact scan
         # (``pre_idx``: the same buffer with the NEW tracks' rows of the first iteration already searched -- forward runs those
         #  unseeded searches, which depend on the query points and the geometry only, on the second stream beside the encoder)
         idx = pre_idx if pre_idx is not None else torch.empty(L, n, S, K, device=dev, dtype=torch.int32)
         assert tuple(idx.shape) == (L, n, S, K)
-        grid = [tuple(store["xyz"][lvl].shape[2:4]) for lvl in range(L)]  # per-view (h, w) of each level
         preds = []
         if trace is not None:  # the state every iteration's search / correlation starts from (teacher-forced parity checks)
             trace["coords_in"], trace["ffeats_in"] = coords.clone(), ffeats.clone()
-        levels = [dict(xyz=store["xyz"][lvl], P=store["P"][lvl], keys=keys[lvl], nseg=nsegs[lvl], seed_idx=idx[lvl], box=store["box"][lvl],
+        levels =[dict(xyz=store["xyz"][lvl], P=store["P"][lvl], seed_idx=idx[lvl], box=store["box"][lvl],
                        grid=store["tile_grid"][lvl], idx_out=idx[lvl], gbox=store["gbox"][lvl]) for lvl in range(L)]
         for it in range(iters):
             if it > 0:
                 # every level is seeded by its own previous neighbours: the four scans are independent -> one launch
-                if self.knn_one_launch:
-                    hip.knn_search_levels(levels, coords, n, S, frame0, frame_step, T, K, seed_k=K)
-                else:
-                    hip.knn_scan_levels(levels, coords, n, S, frame0, frame_step, T, K, seed_k=K)
-                    hip.knn_merge_levels(levels, n, S, K)
+                hip.knn_search_levels(levels, coords, n, S, frame0, frame_step, T, K, seed_k=K)
             else:
                 n0 = 0
                 if carry is not None and carry[1] > 0 and self.seed_across_windows:
@@ -1121,40 +1126,17 @@ class MVTracker(nn.Module):
                     if slot is None:
                         slot = self._slot_cache[(S, dev)] = torch.tensor([min(s_ + S // 2, S - 1) for s_ in range(S)], device=dev)
                     seed_t = prev_idx[:, :n0].index_select(2, slot).contiguous()
-                    lv0 = [dict(lv, keys=keys[l_][:n0 * S * nsegs[l_] * K], seed_idx=seed_t[l_], idx_out=idx[l_][:n0]) for l_, lv in enumerate(levels)]
-                    if self.knn_one_launch:
-                        hip.knn_search_levels(lv0, coords, n0, S, frame0, frame_step, T, K, seed_k=K)
-                    else:
-                        hip.knn_scan_levels(lv0, coords, n0, S, frame0, frame_step, T, K, seed_k=K)
-                        hip.knn_merge_levels(lv0, n0, S, K)
+                    lv0 = [dict(lv, seed_idx=seed_t[l_], idx_out=idx[l_][:n0]) for l_, lv in enumerate(levels)]
+                    hip.knn_search_levels(lv0, coords, n0, S, frame0, frame_step, T, K, seed_k=K)
                 # rows [n1, n) were searched ahead of time (``pre_idx``: the tracks that enter at this window, i.e. everything behind the
                 # carried ones); rows [n0, n1) still need their first, unseeded search -- empty unless the carried tracks were not seeded
                 # from the previous window (``seed_across_windows`` off)
                 n1 = n if pre_idx is None else (carry[1] if carry is not None else 0)
-                if n0 >= n1:
-                    pass
-                elif self.knn_one_launch and all(b is not None for b in store["box"]):
+                if n0 < n1:
                     # new tracks: all four levels in ONE unseeded launch (every search starts from the farthest-corner bound of the
                     # nearest full tile) -- 262 us against four dependent coarse-to-fine launches of ~100 us each
-                    m = n1 - n0
                     lv1 = [dict(lv, seed_idx=None, idx_out=idx[l_][n0:n1]) for l_, lv in enumerate(levels)]
-                    hip.knn_search_levels(lv1, coords[n0:n1], m, S, frame0, frame_step, T, K, seed_k=0)
-                else:  # new tracks: coarse to fine, level l+1's neighbours bound level l's first scan
-                    m = n1 - n0
-                    for lvl in reversed(range(L)):
-                        P = store["P"][lvl]
-                        seed = {}
-                        if lvl + 1 < L and grid[lvl][0] >= 2 * grid[lvl + 1][0] and grid[lvl][1] >= 2 * grid[lvl + 1][1]:
-                            seed = dict(seed_idx=idx[lvl + 1][n0:n1], seed_k=K,
-                                        seed_dims=(grid[lvl + 1][1], grid[lvl + 1][0], grid[lvl][1], grid[lvl][0]))
-                        if self.knn_one_launch:
-                            hip.knn_search(store["xyz"][lvl], P, coords[n0:n1], m, S, frame0, frame_step, T, K, idx[lvl][n0:n1], store["box"][lvl],
-                                           grid=store["tile_grid"][lvl], gbox=store["gbox"][lvl], **seed)
-                            continue
-                        kl = keys[lvl][n0 * S * nsegs[lvl] * K:n1 * S * nsegs[lvl] * K]
-                        hip.knn_scan(store["xyz"][lvl], P, coords[n0:n1], m, S, frame0, frame_step, T, K, nsegs[lvl], kl, box=store["box"][lvl],
-                                     grid=store["tile_grid"][lvl], **seed)
-                        hip.knn_merge(kl, m, S, K, nsegs[lvl], P, idx[lvl][n0:n1])
+                    hip.knn_search_levels(lv1, coords[n0:n1], n1 - n0, S, frame0, frame_step, T, K, seed_k=0)
             if default_corr:
                 hip.corr_gather_dot(store["xyz"], store["fvec"], store["P"], [idx[lvl] for lvl in range(L)], C, ffeats, coords, n, S, frame0,
                                     frame_step, T, K, fcorr, Fc, 0)
@@ -1162,10 +1144,8 @@ class MVTracker(nn.Module):
                 hip.corr_gather_dot_opts(store["xyz"], store["fvec"], store["P"], [idx[lvl] for lvl in range(L)], C, ffeats, coords, n, S,
                                          frame0, frame_step, T, K, self.corr_n_groups, self.corr_add_neighbor_offset, self.corr_add_neighbor_xyz,
                                          fcorr, Fc, 0)
-            hook = getattr(self, "_after_first_corr", None)
-            if hook is not None:  # (forward: the later frame blocks' encoder starts on the second stream now)
-                self._after_first_corr = None
-                hook()
+            if it == 0 and after_first_corr is not None:  # (forward: the later frame blocks' encoder starts on the second stream now)
+                after_first_corr()
             if (trace is None and "updater_struct" in pk and self.fuse_head and self.fuse_input and self.fuse_tokens
                     and pk["updater_struct"].input_frag.w):
                 # everything after the correlation in ONE library call: token rows assembled inside the updater's first kernel,
@@ -1201,10 +1181,180 @@ class MVTracker(nn.Module):
         hip.rowdot(ffeats, C, *pk["vis"], vis, n * S, C)
         if trace is not None:
             trace["ffeats"] = ffeats
-        self._last_idx = idx
-        return preds, vis
+        return preds, vis, idx
 
     # ------------------------------------------------------------------ forward (mvtracker.py:412-732)
+    def _normalise_inputs(self, rgbs, depths, intrs, extrs, is_train, logging_hooks):
+        """What ``forward`` and ``forward_grouped`` check and convert alike: inference only, the reference's logging hooks ignored,
+        batch size 1.  Returns the clip without its batch dimension on the device: depths / intrs / extrs fp32 and contiguous, rgbs
+        fp32 or uint8."""
+        if is_train:
+            raise NotImplementedError("inference only: the MI355X path has no backward")
+        if logging_hooks:
+            log.warning("save_debug_logs / save_rerun_logs are host-side visualisation hooks of the reference; ignored")
+        batch_size, num_views, num_frames, _, height, width = rgbs.shape
+        assert rgbs.shape == (batch_size, num_views, num_frames, 3, height, width)
+        assert depths.shape == (batch_size, num_views, num_frames, 1, height, width)
+        assert intrs.shape == (batch_size, num_views, num_frames, 3, 3)
+        assert extrs.shape == (batch_size, num_views, num_frames, 3, 4)
+        assert batch_size == 1, "Batch size > 1 is not supported yet"
+        hip.require_device(rgbs)
+        dev = rgbs.device
+        # (uint8 frames -- the sample files' storage type -- stay uint8: the encoder's first kernel converts them)
+        rgbs = rgbs[0].to(dev).contiguous() if rgbs.dtype == torch.uint8 else _f32(rgbs[0], dev)
+        return rgbs, _f32(depths[0], dev), _f32(intrs[0], dev), _f32(extrs[0], dev)
+
+    def _feat_init_scan(self, store, frames, qxyz, a0, a1, keys_for=None):
+        """Scan half of the feature init (mvtracker.py:607-645: 1-NN in the level-0 cloud of each row's query frame) for rows
+        [a0, a1) of ``qxyz`` (device).  ``frames`` (host) holds the rows' query frames, equal frames in runs: one ``knn_scan`` with
+        K = 1 per run.  Yields (a, b, frame, keys) run by run, so that a consumer can gather right behind each scan.  ``keys_for``:
+        the stream that will consume the keys, when they are allocated under another one."""
+        P0 = store["P"][0]
+        ns = self._nseg(P0, 1)
+        cuts = [a0, *(a0 + 1 + np.flatnonzero(np.diff(frames[a0:a1]))).tolist(), a1] if a1 > a0 else [a0]
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            t = int(frames[a])
+            keys = torch.empty((b - a) * ns, device=qxyz.device, dtype=torch.int64)
+            hip.knn_scan(store["xyz"][0], P0, qxyz[a:b], b - a, 1, t, 0, store["T"], 1, ns, keys, box=store["box"][0],
+                         grid=store["tile_grid"][0])
+            if keys_for is not None:
+                keys.record_stream(keys_for)
+            yield a, b, t, keys
+
+    def _feat_init_gather(self, store, groups, feat):
+        """Gather half of the feature init: the feature row of each scanned key into rows [a, b) of ``feat``."""
+        P0 = store["P"][0]
+        ns = self._nseg(P0, 1)
+        for a, b, t, keys in groups:
+            hip.knn1_gather(store["fvec"][0], P0, self.latent_dim, keys, b - a, ns, t, feat[a:b])
+
+    def _feat_init(self, store, frames, qxyz, a0, a1, feat):
+        self._feat_init_gather(store, self._feat_init_scan(store, frames, qxyz, a0, a1), feat)
+
+    def _presearch(self, st, windows, frames, qxyz, pre):
+        """Everything of the call that needs the point clouds but no features: the first, UNSEEDED neighbour search of the tracks
+        that enter at each window (their coordinates are the query points, mvtracker.py:505-511) and the 1-NN scans of the
+        feature init (:607-645).  Issued on the second stream between the geometry and the encoder of the first window's frames,
+        so these searches (~0.4 ms at C3, latency-bound gathers) run beside the convolutions instead of after them.
+        Fills ``pre``: window start -> (neighbour buffer with the new tracks' first search done, 1-NN keys per query-frame run,
+        the searched coordinates), and "event" -> what the main stream waits for before it uses any of them."""
+        dev = qxyz.device
+        if dev.type != "cuda" or not self.presearch:
+            return
+        S, K, L, T = self.S, self.corr_neighbors, self.corr_n_levels, st["T"]
+        side = self._side_stream(dev)
+        main_s = torch.cuda.current_stream(dev)
+        # hand-over H4: point clouds / tile boxes / sorted query rows (all enqueued on the caller's stream BEFORE the geometry event)
+        side.wait_stream(main_s) if "geo_event" not in st else side.wait_event(st["geo_event"])
+        self._handover(dev)
+        with torch.cuda.stream(side):
+            q0 = 0
+            for ww, q1 in windows:
+                if q1 > q0:
+                    m = q1 - q0
+                    idxb = torch.empty(L, q1, S, K, device=dev, dtype=torch.int32)
+                    c0 = qxyz[q0:q1, None, :].expand(m, S, 3).contiguous()
+                    lv = [dict(xyz=st["xyz"][l], P=st["P"][l], seed_idx=None, box=st["box"][l], grid=st["tile_grid"][l],
+                               idx_out=idxb[l][q0:], gbox=st["gbox"][l]) for l in range(L)]
+                    hip.knn_search_levels(lv, c0, m, S, ww, 1, T, K, seed_k=0)
+                    # (keys allocated under the second stream, consumed on the caller's)
+                    groups = list(self._feat_init_scan(st, frames, qxyz, q0, q1, keys_for=main_s))
+                    idxb.record_stream(main_s)
+                    pre[ww] = (idxb, groups, c0)
+                q0 = q1
+            ev = torch.cuda.Event()
+            ev.record(side)
+        pre["event"] = ev
+
+    def _plan_frame_store(self, rgbs, depths, intrs, extrs, geometry, frame_store, windows, backward, after_first_chunk):
+        """Where the call's frame features come from: a supplied store, the whole clip encoded up front, or the first window's
+        frames now and the rest on the second stream.  Returns (store, pending, pending_back, start_side_encoder): (first frame,
+        event) of the feature blocks in flight that the forward windows / only the reversed pass read, and the host callback that
+        starts the second stream's encoder (None when there is none to start).  ``after_first_chunk(store)`` is called as soon as
+        the first encoder chunk of a store built here has been enqueued."""
+        S, T = self.S, rgbs.shape[1]
+        if frame_store is not None:
+            # (first frame, event) of feature blocks still in flight
+            return frame_store, list(frame_store.get("pending", ())) if windows else [], [], None
+        if not windows:  # every query within the clip's last S/2 frames: only a reversed pass needs a store
+            return (self.build_frame_store(rgbs, depths, intrs, extrs, t0=0, geometry=geometry) if backward else None), [], [], None
+        w = max(windows[0][0], 0)
+        if not self.overlap_encoder or w + S >= T or rgbs.device.type != "cuda":
+            store = self.build_frame_store(rgbs, depths, intrs, extrs, t0=0 if backward else w, after_geometry=after_first_chunk,
+                                           geometry=geometry)
+            return store, [], [], None
+        # The first window needs frames [w, w+S).  The remaining frames are encoded on a second HIP stream while
+        # the updater of the earlier windows runs: its kernels over the 64 virtual tracks fill a fraction of the
+        # CUs, the encoder's convolutions take the rest.
+        ready = w + S
+        store = self.build_frame_store(rgbs, depths, intrs, extrs, t0=w, t1=ready, after_geometry=after_first_chunk, geometry=geometry)
+        later = list(range(ready, T, S // 2))  # first frames of the S/2-frame blocks still to encode
+        # backward tracking reads the frames before the first forward window too: first frames of the S/2-frame blocks of [0, w)
+        early = list(range(0, w, S // 2)) if backward else []
+        pending, pending_back = [], []
+
+        def start_side_encoder():
+            # started by the first window BEHIND its first correlation launch (``_refine`` calls it): the first kernels
+            # of that window -- feature init, window state, the first correlation gather -- are latency-bound and otherwise
+            # start in the same instant as the second stream's first convolutions
+            self._encode_on_side_stream(store, rgbs, later, pending)
+            if early:  # the frames only the reversed pass reads, BEHIND the forward pass's blocks (hand-over H3)
+                self._encode_on_side_stream(store, rgbs, early, pending_back, end=w)
+
+        return store, pending, pending_back, start_side_encoder
+
+    def _run_windows(self, store, windows, frame0s, frame_step, prepare, rows, store_out, unsort, out, iters, trace,
+                     enter_frames=None, pre=None, pending=(), after_first_corr=None):
+        """One pass of the reference's window loop (mvtracker.py:537-695) over ``windows`` = [(start, active prefix), ...], slot s
+        of window i reading store frame clamp(frame0s[i] + s * frame_step, 0, T-1).  ``prepare`` / ``store_out``: the library's
+        window-state and result-store entry of the pass, ``rows`` = (query xyz, query frames, initial feature rows) in the pass's
+        sorted order on the device, ``unsort`` = what ``store_out`` takes to put window rows back into the caller's.  ``out``: the
+        call's result tensors.  Forward pass only: ``enter_frames`` (host query frames: the feature rows of the tracks that enter
+        a window are initialised there), ``pre`` (``_presearch``), ``pending`` ((first frame, event) of the feature blocks in
+        flight on the second stream, in frame order), ``after_first_corr`` (``_refine``, first window).  Returns the windows run."""
+        S, C = self.S, self.latent_dim
+        qxyz, qt_d, feat = rows
+        dev = qxyz.device
+        T, N = out["traj"].shape[:2]
+        pre = {} if pre is None else pre
+        done = []
+        p0 = 0
+        coords = vis = prev_idx = None
+        for (w, p1), f0 in zip(windows, frame0s):  # mvtracker.py:537; p1 = number of queries with t < w+S (:538-540)
+            assert p1 > 0
+            while pending and pending[0][0] < w + S:  # the frames this window reads must have left the encoder
+                torch.cuda.current_stream(dev).wait_event(pending.pop(0)[1])  # hand-over H5: feature rows encoded on the second stream
+                self._handover(dev)
+            if "event" in pre:  # the searches issued ahead of time on the second stream
+                torch.cuda.current_stream(dev).wait_event(pre.pop("event"))  # hand-over H6: neighbour buffers / 1-NN keys (record_stream'd)
+                self._handover(dev)
+            pre_w = pre.get(w)
+            if p1 > p0 and enter_frames is not None:
+                if pre_w is not None:  # feature init from the 1-NN keys scanned ahead of time
+                    self._feat_init_gather(store, pre_w[1], feat)
+                else:
+                    self._feat_init(store, enter_frames, qxyz, p0, p1, feat)
+            # window state in one launch: carry-over of coords / visibility LOGITS from the previous window (:648-655), track mask
+            # (:505-507, :695; the repeat-last-frame padding of :598-604 is a clamped frame index), features repeated over S (:645)
+            wc = torch.empty(p1, S, 3, device=dev)
+            wf = torch.empty(p1, S, C, device=dev)
+            wm = torch.empty(p1, S, 2, device=dev)
+            prepare(qxyz, qt_d, feat, coords, vis, p1, p0, S, C, w, T, wc, wm, wf)
+            wtrace = None
+            if trace is not None:
+                wtrace = {} if frame_step > 0 else dict(reversed_window=w)
+                trace.append(wtrace)
+            preds, vis, prev_idx = self._refine(store, f0, wc, wf, wm, iters=iters, nan_flag=out["nan_flag"], trace=wtrace,
+                                                carry=(prev_idx, p0) if p0 > 0 else None, pre_idx=pre_w[0] if pre_w is not None else None,
+                                                frame_step=frame_step, after_first_corr=after_first_corr)
+            after_first_corr = None
+            coords = preds[-1]
+            # :692-693, un-sorted (:710-711); the reversed pass writes only frames before each row's query frame
+            store_out(coords, vis, *unsort, p1, S, w, T, N, out["traj"], out["vis_logit"], out["vis_prob"])
+            done.append((w, p1))
+            p0 = p1
+        return done
+
     @torch.no_grad()
     @hip.guarded
     def forward(
@@ -1229,27 +1379,14 @@ class MVTracker(nn.Module):
         """``backward_tracking``: also fill the frames BEFORE each query's frame, from a time-reversed pass over the same frame store
         (``mvtracker_amd.backward``).  Frames from the query frame on are the same bits with the option on or off.
         The reversed pass's windows are left in ``last_windows_backward`` as (start in reversed time, active tracks)."""
-        if is_train:
-            raise NotImplementedError("inference only: the MI355X path has no backward")
-        if save_debug_logs or save_rerun_logs:
-            log.warning("save_debug_logs / save_rerun_logs are host-side visualisation hooks of the reference; ignored")
-        batch_size, num_views, num_frames, _, height, width = rgbs.shape
-        _, num_points, _ = query_points.shape
-        assert rgbs.shape == (batch_size, num_views, num_frames, 3, height, width)
-        assert depths.shape == (batch_size, num_views, num_frames, 1, height, width)
-        assert query_points.shape == (batch_size, num_points, 4)
-        assert intrs.shape == (batch_size, num_views, num_frames, 3, 3)
-        assert extrs.shape == (batch_size, num_views, num_frames, 3, 4)
-        assert batch_size == 1, "Batch size > 1 is not supported yet"
-        hip.require_device(rgbs)
+        rgbs, depths, intrs, extrs = self._normalise_inputs(rgbs, depths, intrs, extrs, is_train, save_debug_logs or save_rerun_logs)
+        N = query_points.shape[1]
+        assert query_points.shape == (1, N, 4)
         dev = rgbs.device
-        V, T, S, C, N = num_views, num_frames, self.S, self.latent_dim, num_points
-        f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
-        # (uint8 frames -- the sample files' storage type -- stay uint8: the encoder's first kernel converts them)
-        rgbs = rgbs[0].to(dev).contiguous() if rgbs.dtype == torch.uint8 else f32(rgbs[0])
-        depths, intrs, extrs, query_points = map(f32, (depths[0], intrs[0], extrs[0], query_points[0]))
+        T, S, C = rgbs.shape[1], self.S, self.latent_dim
+        query_points = _f32(query_points[0], dev)
 
-        # the one host sync of the call: integer query frames (mvtracker.py:489, truncation toward zero).  The read-back is
+        # ---- the one host sync of the call: integer query frames (mvtracker.py:489, truncation toward zero).  The read-back is
         # asynchronous (pinned buffer + event) and the query-independent geometry kernels are enqueued BEHIND it before the host
         # waits: in back-to-back calls the host wakes up when the previous call's last kernel ends, and the GPU then has the
         # geometry to run while the host enqueues the first encoder block (the kernel trace showed ~0.3 ms of idle GPU there)
@@ -1266,13 +1403,11 @@ class MVTracker(nn.Module):
             qt = qt_pin.numpy().copy()
         else:
             qt = qt_dev.cpu().numpy()
+
+        # ---- host layout: sort order, the windows of both passes, one small upload
         order = np.argsort(qt, kind="stable")  # mvtracker.py:514 (order among equal t is unobservable)
         qt_s = qt[order]
-        # (the two tiny host-to-device copies go first, while the GPU is idle anyway: from pageable memory they block the host until
-        #  the stream has drained, which after the first encoder chunk would be milliseconds)
-        # (through a cached PINNED staging buffer, asynchronously: from pageable memory each copy is a host-blocking staged transfer --
-        #  ~60 us of idle GPU apiece in the kernel trace.  The buffer may be rewritten by the next call: its host sync above comes
-        #  after these copies in stream order)
+        fwd = window_prefixes(qt_s, S, T)  # the reference's loop (:537-540) as [(window start, active prefix), ...]
         # backward tracking: the reversed pass's rows and windows, known on the host from here on (their index arrays ride in the same
         # upload); ``back`` stays None when no reversed window runs, and the call is then the plain forward
         back = reversed_layout(qt, S, T) if backward_tracking else None
@@ -1282,7 +1417,6 @@ class MVTracker(nn.Module):
         fix_rows = np.zeros(0, dtype=np.int64)
         if back is not None:
             # rows of feat_init (sorted by query frame) that only the reversed pass reaches take that pass's feature row
-            fwd = window_prefixes(qt_s, S, T)
             inv_b = np.empty(N, dtype=np.int64)
             inv_b[back["order"]] = np.arange(N)
             tail = np.arange(fwd[-1][1] if fwd else 0, N)
@@ -1290,241 +1424,76 @@ class MVTracker(nn.Module):
             small += [back["order"].astype(np.int64), back["sorted_qt"].astype(np.int32)]
             if len(fix_rows):
                 small += [fix_rows, inv_b[order[fix_rows]]]
+        # (the tiny host-to-device copies go first, while the GPU is idle anyway, through a cached PINNED staging buffer,
+        #  asynchronously: from pageable memory each copy is a host-blocking staged transfer that waits until the stream has drained
+        #  -- ~60 us of idle GPU apiece in the kernel trace, milliseconds after the first encoder chunk.  The buffer may be rewritten
+        #  by the next call: its host sync above comes after these copies in stream order)
         small_d = self._upload_small(dev, *small)
         order_d, qt_sd = small_d[:2]
-        # (N,3) query points sorted by start frame -- enqueued HERE, ahead of the geometry: the searches issued on the second stream
-        # order themselves after the geometry event only, and they read these rows)
+        # (N,3) query points sorted by start frame -- enqueued HERE, ahead of the geometry event: the searches issued on the second
+        # stream order themselves after that event only, and they read these rows
         qxyz = query_points[order_d, 1:].contiguous()
         if geometry is not None:
             # hand-over H4: the searches issued on the second stream order themselves after this event -- it has to come AFTER the
             # gather above (the geometry itself was enqueued, and its own event recorded, before the host sync)
             geometry["geo_event"] = torch.cuda.Event()
             geometry["geo_event"].record(torch.cuda.current_stream(dev))
-        state = []
 
-        def make_state():
-            """Device-side bookkeeping of the call.  Created AFTER the first encoder chunk has been enqueued (see ``presearch``):
-            the GPU idles from the host sync above until the first kernels arrive, so nothing that can wait goes before them."""
-            if not state:
-                state.append(dict(
-                    traj=torch.zeros(T, N, 3, device=dev),        # clip outputs in the caller's query order (window_store un-sorts)
-                    vis_prob=torch.zeros(T, N, device=dev), vis_logit=torch.zeros(T, N, device=dev),
-                    feat_init=torch.zeros(N, C, device=dev), nan_flag=torch.zeros(1, device=dev, dtype=torch.int32)))
-            return state[0]
-
-        w = int(qt_s.min())
-        windows = []
-        pending = []  # (first frame, event): feature chunks being encoded on the side stream
-        side_chunks = []  # first frames of the blocks the side stream has not been given yet
-        pre = {}  # window start -> (neighbour buffer with the new tracks' first search done, 1-NN keys per query-frame group)
-
-        def presearch(st):
-            """Everything of the call that needs the point clouds but no features: the first, UNSEEDED neighbour search of the tracks
-            that enter at each window (their coordinates are the query points, mvtracker.py:505-511) and the 1-NN scans of the
-            feature init (:607-645).  Issued on the second stream between the geometry and the encoder of the first window's frames,
-            so these searches (~0.4 ms at C3, latency-bound gathers) run beside the convolutions instead of after them."""
-            make_state()
-            if dev.type != "cuda" or not self.presearch or not self.knn_one_launch or any(b is None for b in st["box"]):
-                return
-            K, L = self.corr_neighbors, self.corr_n_levels
-            side = self._side_stream(dev)
-            main_s = torch.cuda.current_stream(dev)
-            # hand-over H4: point clouds / tile boxes / sorted query rows (all enqueued on the caller's stream BEFORE the geometry event)
-            side.wait_stream(main_s) if "geo_event" not in st else side.wait_event(st["geo_event"])
-            self._handover(dev)
-            with torch.cuda.stream(side):
-                ww, q0 = w, 0
-                P0 = st["P"][0]
-                ns = self._nseg(P0, 1)
-                while ww < T - S // 2:
-                    q1 = int(np.searchsorted(qt_s, ww + S, side="left"))
-                    if q1 > q0:
-                        m = q1 - q0
-                        idxb = torch.empty(L, q1, S, K, device=dev, dtype=torch.int32)
-                        c0 = qxyz[q0:q1, None, :].expand(m, S, 3).contiguous()
-                        lv = [dict(xyz=st["xyz"][l], P=st["P"][l], seed_idx=None, box=st["box"][l], grid=st["tile_grid"][l],
-                                   idx_out=idxb[l][q0:], gbox=st["gbox"][l]) for l in range(L)]
-                        hip.knn_search_levels(lv, c0, m, S, ww, 1, T, K, seed_k=0)
-                        groups = []
-                        a = q0
-                        while a < q1:
-                            t = int(qt_s[a])
-                            b = min(int(np.searchsorted(qt_s, t, side="right")), q1)
-                            keys = torch.empty((b - a) * ns, device=dev, dtype=torch.int64)
-                            hip.knn_scan(st["xyz"][0], P0, qxyz[a:b], b - a, 1, t, 0, T, 1, ns, keys, box=st["box"][0], grid=st["tile_grid"][0])
-                            groups.append((a, b, t, keys))
-                            keys.record_stream(main_s)  # (allocated under the second stream, consumed on the caller's)
-                            a = b
-                        idxb.record_stream(main_s)
-                        pre[ww] = (idxb, groups, c0)
-                    ww += S // 2
-                    q0 = q1
-                ev = torch.cuda.Event()
-                ev.record(side)
-            pre["event"] = ev
-
-        # backward tracking reads the frames before the first forward window too: first frames of the S/2-frame blocks of
-        # [0, w) still to encode, and (first frame, event) of those in flight on the second stream
-        early = list(range(0, max(w, 0), S // 2)) if back is not None and frame_store is None else []
-        pending_back = []
-        store = None
-
-        def encode_early():
-            """The frames only the reversed pass reads, on the second stream BEHIND the forward pass's blocks (hand-over H3)."""
-            if early:
-                firsts = list(early)
-                del early[:]
-                self._encode_on_side_stream(store, rgbs, firsts, pending_back, end=max(w, 0))
-
+        # ---- frame-store plan
         if back is not None and frame_store is not None and frame_store.get("feat_t0", 0) > 0:
             raise ValueError(f"backward_tracking needs a frame store with features from frame 0 on (queries up to frame {int(qt.max())} are "
                              f"tracked back to the clip's start), but the supplied frame_store was built from frame "
                              f"{frame_store['feat_t0']}: build it with t0=0")
-        if w < T - S // 2:
-            if frame_store is not None:
-                store = frame_store
-                pending = list(frame_store.get("pending", ()))  # (first frame, event) of feature blocks still in flight
-            elif not self.overlap_encoder or max(w, 0) + S >= T or dev.type != "cuda":
-                store = self.build_frame_store(rgbs, depths, intrs, extrs, t0=0 if back is not None else max(w, 0), after_geometry=presearch,
-                                               geometry=geometry)
-                del early[:]
-            else:
-                # The first window needs frames [w, w+S).  The remaining frames are encoded on a second HIP stream while
-                # the updater of the earlier windows runs: its kernels over the 64 virtual tracks fill a fraction of the
-                # CUs, the encoder's convolutions take the rest.
-                ready = max(w, 0) + S
-                store = self.build_frame_store(rgbs, depths, intrs, extrs, t0=max(w, 0), t1=ready, after_geometry=presearch, geometry=geometry)
-                side_chunks = list(range(ready, T, S // 2))  # first frames of the S/2-frame blocks still to encode
-                if not self.defer_encoder:
-                    # started by the first window BEHIND its first correlation launch (``_refine`` calls the hook): the first kernels
-                    # of that window -- feature init, window state, the first correlation gather -- are latency-bound and otherwise
-                    # start in the same instant as the second stream's first convolutions
-                    if self.side_after_corr:
-                        chunks_now = side_chunks
-                        self._after_first_corr = lambda: (self._encode_on_side_stream(store, rgbs, chunks_now, pending), encode_early())
-                    else:
-                        self._encode_on_side_stream(store, rgbs, side_chunks, pending)
-                        encode_early()
-                    side_chunks = []
-        elif back is not None:  # no forward window (every query within the clip's last S/2 frames): the reversed pass still needs a store
-            store = frame_store if frame_store is not None else self.build_frame_store(rgbs, depths, intrs, extrs, t0=0, geometry=geometry)
-            del early[:]
-        sd_ = make_state()
-        traj, vis_prob, vis_logit = sd_["traj"], sd_["vis_prob"], sd_["vis_logit"]
-        feat_init, nan_flag = sd_["feat_init"], sd_["nan_flag"]
-        p0 = 0
-        coords = vis = prev_idx = None
-        while w < T - S // 2:  # mvtracker.py:537
-            p1 = int(np.searchsorted(qt_s, w + S, side="left"))  # number of queries with t < w+S (:538-540)
-            assert p1 > 0
-            while pending and pending[0][0] < w + S:  # the frames this window reads must have left the encoder
-                torch.cuda.current_stream(dev).wait_event(pending.pop(0)[1])  # hand-over H5: feature rows encoded on the second stream
-                self._handover(dev)
-            if side_chunks:
-                # one block of later frames per window: block j is what window j + 1 will read, so it is encoded WHILE window j is
-                # refined -- its convolutions fill the CUs the 64 virtual tracks' kernels leave idle -- instead of all blocks
-                # piling onto the first window (which then runs at half speed while the last windows run alone)
-                self._encode_on_side_stream(store, rgbs, [side_chunks.pop(0)], pending)
-            if "event" in pre:  # the searches issued ahead of time on the second stream
-                torch.cuda.current_stream(dev).wait_event(pre.pop("event"))  # hand-over H6: neighbour buffers / 1-NN keys (record_stream'd)
-                self._handover(dev)
-            pre_w = pre.get(w)
-            if p1 > p0 and pre_w is not None:  # feature init from the 1-NN keys scanned ahead of time
-                P0 = store["P"][0]
-                ns = self._nseg(P0, 1)
-                for (a, b, t, keys) in pre_w[1]:
-                    hip.knn1_gather(store["fvec"][0], P0, C, keys, b - a, ns, t, feat_init[a:b])
-            elif p1 > p0:  # feature init: 1-NN in the fused level-0 cloud of the query frame (:607-645)
-                P0 = store["P"][0]
-                ns = self._nseg(P0, 1)
-                a = p0
-                while a < p1:
-                    t = int(qt_s[a])
-                    b = int(np.searchsorted(qt_s, t, side="right"))
-                    b = min(b, p1)
-                    keys = torch.empty((b - a) * ns, device=dev, dtype=torch.int64)
-                    hip.knn_scan(store["xyz"][0], P0, qxyz[a:b], b - a, 1, t, 0, T, 1, ns, keys, box=store["box"][0],
-                                 grid=store["tile_grid"][0])
-                    hip.knn1_gather(store["fvec"][0], P0, C, keys, b - a, ns, t, feat_init[a:b])
-                    a = b
-            # window state in one launch: carry-over of coords / visibility LOGITS from the previous window (:648-655), track mask
-            # (:505-507, :695; the repeat-last-frame padding of :598-604 is a clamped frame index), features repeated over S (:645)
-            wc = torch.empty(p1, S, 3, device=dev)
-            wf = torch.empty(p1, S, C, device=dev)
-            wm = torch.empty(p1, S, 2, device=dev)
-            hip.window_prepare(qxyz, qt_sd, feat_init, coords, vis, p1, p0, S, C, w, T, wc, wm, wf)
-            wtrace = None
-            if trace is not None:
-                wtrace = {}
-                trace.append(wtrace)
-            preds, vis = self._refine(store, w, wc, wf, wm, iters=iters, nan_flag=nan_flag, trace=wtrace,
-                                      carry=(prev_idx, p0) if p0 > 0 else None, pre_idx=pre_w[0] if pre_w is not None else None)
-            prev_idx = self._last_idx
-            coords = preds[-1]
-            hip.window_store(coords, vis, order_d, p1, S, w, T, N, traj, vis_logit, vis_prob)  # :692-693, un-sorted (:710-711)
-            windows.append((w, p1))
-            w += S // 2
-            p0 = p1
-        hook = getattr(self, "_after_first_corr", None)
-        if hook is not None:  # (no window ran: cannot happen while w < T - S/2, kept for safety)
-            self._after_first_corr = None
-            hook()
+        out, pre = {}, {}
+
+        def after_first_chunk(st):
+            # Device-side bookkeeping of the call, created AFTER the first encoder chunk has been enqueued: the GPU idles from the
+            # host sync above until the first kernels arrive, so nothing that can wait goes before them
+            out.update(_call_outputs(dev, T, N, C))
+            self._presearch(st, fwd, qt_s, qxyz, pre)
+
+        store, pending, pending_back, start_side_encoder = self._plan_frame_store(rgbs, depths, intrs, extrs, geometry, frame_store, fwd,
+                                                                                  back is not None, after_first_chunk)
+        if not out:  # (no store was built behind an encoder chunk)
+            out.update(_call_outputs(dev, T, N, C))
+        if start_side_encoder is not None and iters < 1:  # (no correlation launch to start it behind)
+            start_side_encoder()
+            start_side_encoder = None
+
+        # ---- forward pass
+        windows = self._run_windows(store, fwd, [w for w, _ in fwd], 1, hip.window_prepare, (qxyz, qt_sd, out["feat_init"]),
+                                    hip.window_store, (order_d,), out, iters, trace, enter_frames=qt_s, pre=pre, pending=pending,
+                                    after_first_corr=start_side_encoder)
         for _, ev in pending:  # frames no window consumed: still join the side stream before the inputs are released
             torch.cuda.current_stream(dev).wait_event(ev)  # hand-over H7: the caller's inputs (read by the second stream) are released
+
+        # ---- the time-reversed pass (one stream): the same window loop on the same store, slots running downwards from frame
+        # T-1-wr.  Its store kernel writes only frames before each row's query frame, which IS the merge of the two passes.
         windows_b = []
         if back is not None:
-            # ---- the time-reversed pass (one stream): the same window loop on the same store, slots running downwards from frame
-            # T-1-wr.  Its store kernel writes only frames before each row's query frame, which IS the merge of the two passes.
-            encode_early()  # (only the deferred-encoder variant gets here with blocks left)
             for _, ev in pending_back + list(store.get("pending", ()) if frame_store is not None else ()):
                 torch.cuda.current_stream(dev).wait_event(ev)  # hand-over H5 for the early frames
             if pending_back:
                 self._handover(dev)
             order_bd, qt_bd = small_d[2:4]
-            nb = back["active"]
             qxyz_b = query_points[order_bd, 1:].contiguous()
             feat_b = torch.zeros(N, C, device=dev)
-            P0 = store["P"][0]
-            ns = self._nseg(P0, 1)
-            neg_qt = -back["sorted_qt"][:nb]  # (ascending)
-            a = 0
-            while a < nb:  # feature init of the reversed pass's rows (:607-645): the same query frame, the same 1-NN
-                t = -int(neg_qt[a])
-                b = int(np.searchsorted(neg_qt, -t, side="right"))
-                keys = torch.empty((b - a) * ns, device=dev, dtype=torch.int64)
-                hip.knn_scan(store["xyz"][0], P0, qxyz_b[a:b], b - a, 1, t, 0, T, 1, ns, keys, box=store["box"][0], grid=store["tile_grid"][0])
-                hip.knn1_gather(store["fvec"][0], P0, C, keys, b - a, ns, t, feat_b[a:b])
-                a = b
+            # feature init of the reversed pass's rows (:607-645): the same query frame, the same 1-NN
+            self._feat_init(store, back["sorted_qt"], qxyz_b, 0, back["active"], feat_b)
             if len(fix_rows):
-                feat_init.index_copy_(0, small_d[4], feat_b.index_select(0, small_d[5]))
-            p0 = 0
-            coords = vis = prev_idx = None
-            for (wr, p1), f0 in zip(back["windows"], back["frame0"]):
-                wc = torch.empty(p1, S, 3, device=dev)
-                wf = torch.empty(p1, S, C, device=dev)
-                wm = torch.empty(p1, S, 2, device=dev)
-                hip.window_prepare_reversed(qxyz_b, qt_bd, feat_b, coords, vis, p1, p0, S, C, wr, T, wc, wm, wf)
-                wtrace = None
-                if trace is not None:
-                    wtrace = dict(reversed_window=wr)
-                    trace.append(wtrace)
-                preds, vis = self._refine(store, f0, wc, wf, wm, iters=iters, nan_flag=nan_flag, trace=wtrace,
-                                          carry=(prev_idx, p0) if p0 > 0 else None, frame_step=-1)
-                prev_idx = self._last_idx
-                coords = preds[-1]
-                hip.window_store_reversed(coords, vis, order_bd, qt_bd, p1, S, wr, T, N, traj, vis_logit, vis_prob)
-                windows_b.append((wr, p1))
-                p0 = p1
+                out["feat_init"].index_copy_(0, small_d[4], feat_b.index_select(0, small_d[5]))
+            windows_b = self._run_windows(store, back["windows"], back["frame0"], -1, hip.window_prepare_reversed, (qxyz_b, qt_bd, feat_b),
+                                          hip.window_store_reversed, (order_bd, qt_bd), out, iters, trace)
+
         self.last_windows = windows
         self.last_windows_backward = windows_b
-        self.last_vis_logits = vis_logit[None]
-        self.last_nan_flag = nan_flag
-        results = {
-            "traj_e": traj[None],
-            "feat_init": feat_init[None, None].expand(1, S, -1, -1),
-            "vis_e": vis_prob[None],
+        self.last_vis_logits = out["vis_logit"][None]
+        self.last_nan_flag = out["nan_flag"]
+        return {
+            "traj_e": out["traj"][None],
+            "feat_init": out["feat_init"][None, None].expand(1, S, -1, -1),
+            "vis_e": out["vis_prob"][None],
         }
-        return results
 
     @torch.no_grad()
     @hip.guarded
@@ -1536,33 +1505,20 @@ class MVTracker(nn.Module):
         of a window are the concatenation of every member group's active tracks (``grouped.grouped_layout``).  ``trace``: a list
         that receives ``forward``'s per-window dicts in that layout, plus the window start, member groups and row offsets.  The
         other options are ``forward``'s and are handled as there (no training; the reference's logging hooks are ignored)."""
-        if is_train:
-            raise NotImplementedError("inference only: the MI355X path has no backward")
         if backward_tracking:
             raise NotImplementedError("forward_grouped has no backward_tracking (per-set directions inside one launch sequence are not "
                                       "built): call forward(..., backward_tracking=True) per query set")
-        if save_debug_logs or save_rerun_logs:
-            log.warning("save_debug_logs / save_rerun_logs are host-side visualisation hooks of the reference; ignored")
         if not isinstance(query_points_list, (list, tuple)) or not query_points_list:
             raise ValueError("query_points_list must be a non-empty list of (1, N_g, 4) tensors")
-        batch_size, num_views, num_frames, _, height, width = rgbs.shape
-        assert rgbs.shape == (batch_size, num_views, num_frames, 3, height, width)
-        assert depths.shape == (batch_size, num_views, num_frames, 1, height, width)
-        assert intrs.shape == (batch_size, num_views, num_frames, 3, 3)
-        assert extrs.shape == (batch_size, num_views, num_frames, 3, 4)
-        assert batch_size == 1, "Batch size > 1 is not supported yet"
         for g, qp in enumerate(query_points_list):
             if qp.dim() != 3 or qp.shape[0] != 1 or qp.shape[2] != 4:
                 raise ValueError(f"group {g}: query points must be (1, N_g, 4), got {tuple(qp.shape)}")
             if qp.shape[1] == 0:
                 raise ValueError(f"group {g} has no queries")
-        hip.require_device(rgbs)
+        rgbs, depths, intrs, extrs = self._normalise_inputs(rgbs, depths, intrs, extrs, is_train, save_debug_logs or save_rerun_logs)
         dev = rgbs.device
-        V, T, S, C = num_views, num_frames, self.S, self.latent_dim
-        f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
-        rgbs = rgbs[0].to(dev).contiguous() if rgbs.dtype == torch.uint8 else f32(rgbs[0])
-        depths, intrs, extrs = map(f32, (depths[0], intrs[0], extrs[0]))
-        qcat = torch.cat([f32(qp[0]) for qp in query_points_list], 0)  # caller rows
+        T, S, C = rgbs.shape[1], self.S, self.latent_dim
+        qcat = torch.cat([_f32(qp[0], dev) for qp in query_points_list], 0)  # caller rows
         sizes = [int(qp.shape[1]) for qp in query_points_list]
         qt_all = qcat[:, 0].long().cpu().numpy()  # the one host sync of the call (mvtracker.py:489, truncation toward zero)
         lay = grouped_layout(np.split(qt_all, np.cumsum(sizes)[:-1]), S, T)
@@ -1574,11 +1530,8 @@ class MVTracker(nn.Module):
         sorted_src_d = idx_d[:N]
         qxyz = qcat[sorted_src_d, 1:].contiguous()  # sorted rows
         qt_sd = torch.from_numpy(lay["sorted_qt"].astype(np.int32)).to(dev)
-        traj = torch.zeros(T, N, 3, device=dev)
-        vis_prob = torch.zeros(T, N, device=dev)
-        vis_logit = torch.zeros(T, N, device=dev)
-        feat_init = torch.zeros(N, C, device=dev)  # sorted rows (as forward's feat_init)
-        nan_flag = torch.zeros(1, device=dev, dtype=torch.int32)
+        out = _call_outputs(dev, T, N, C)  # (feat_init in sorted rows, as forward's)
+        traj, vis_prob, vis_logit, feat_init, nan_flag = (out[k] for k in ("traj", "vis_prob", "vis_logit", "feat_init", "nan_flag"))
         if wins:
             store = frame_store if frame_store is not None else self.build_frame_store(
                 rgbs, depths, intrs, extrs, t0=max(min(wd["w"] for wd in wins), 0))
@@ -1591,17 +1544,7 @@ class MVTracker(nn.Module):
             ent_d = torch.from_numpy(ent.astype(np.int64)).to(dev)
             qx_e = qxyz[ent_d].contiguous()
             fe = torch.empty(len(ent), C, device=dev)
-            P0 = store["P"][0]
-            ns = self._nseg(P0, 1)
-            qt_e = lay["sorted_qt"][ent]
-            a = 0
-            while a < len(ent):
-                t = int(qt_e[a])
-                b = int(np.searchsorted(qt_e, t, side="right"))
-                keys = torch.empty((b - a) * ns, device=dev, dtype=torch.int64)
-                hip.knn_scan(store["xyz"][0], P0, qx_e[a:b], b - a, 1, t, 0, T, 1, ns, keys, box=store["box"][0], grid=store["tile_grid"][0])
-                hip.knn1_gather(store["fvec"][0], P0, C, keys, b - a, ns, t, fe[a:b])
-                a = b
+            self._feat_init(store, lay["sorted_qt"][ent], qx_e, 0, len(ent), fe)
             feat_init.index_copy_(0, ent_d, fe)
         o = N
         coords = vis = None
@@ -1621,8 +1564,8 @@ class MVTracker(nn.Module):
             if trace is not None:
                 wtrace = dict(w=wd["w"], groups=list(wd["groups"]), group_offsets=wd["off"].tolist(), carried=wd["p0"].tolist())
                 trace.append(wtrace)
-            preds, vis = self._refine(store, wd["w"], wc, wf, wm, iters=iters, nan_flag=nan_flag, trace=wtrace,
-                                      seg=[int(c) for c in np.diff(wd["off"])])
+            preds, vis, _ = self._refine(store, wd["w"], wc, wf, wm, iters=iters, nan_flag=nan_flag, trace=wtrace,
+                                         seg=[int(c) for c in np.diff(wd["off"])])
             coords = preds[-1]
             hip.window_store(coords, vis, out_d, n, S, wd["w"], T, N, traj, vis_logit, vis_prob)  # caller rows
             windows.append((wd["w"], n))
