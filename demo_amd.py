@@ -58,6 +58,10 @@ def main():
     ap.add_argument("--interp-shape", type=int, nargs=2, default=None, metavar=("H", "W"), help="resize like the evaluator (e.g. 384 512)")
     ap.add_argument("--backward-tracking", action="store_true",
                     help="also track every query before its frame (a time-reversed pass over the same frame store)")
+    ap.add_argument("--streaming", action="store_true",
+                    help="feed the clip block by block through a streaming session (EvaluationPredictor.open_stream): the same result, "
+                         "from a ring frame store whose size does not depend on the clip length")
+    ap.add_argument("--block-frames", type=int, default=6, metavar="B", help="frames per pushed block with --streaming")
     ap.add_argument("--save-npz", help="result file (tracks_3d, visibilities, query_points, camera data)")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
@@ -92,6 +96,16 @@ def main():
     V, T = s["rgbs"].shape[1:3]
     print(f"clip: {V} views x {T} frames x {tuple(s['rgbs'].shape[-2:])}, {s['query_points_3d'].shape[1]} queries, precision {args.precision}")
     call = lambda: predictor(rgbs=s["rgbs"], depths=s["depths"], intrs=s["intrs"], extrs=s["extrs"], query_points_3d=s["query_points_3d"])
+    if args.streaming:
+        if args.block_frames < 1:
+            raise SystemExit("--block-frames must be at least 1")
+
+        def call():
+            st = predictor.open_stream(s["query_points_3d"])
+            outs = [st.push(*(s[k][:, :, t:t + args.block_frames] for k in ("rgbs", "depths", "intrs", "extrs")))
+                    for t in range(0, T, args.block_frames)]
+            outs.append(st.finish())
+            return {k: torch.cat([o[k] for o in outs], 1) for k in ("traj_e", "vis_e")}
     call()  # warm-up (weight packing, allocator)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -99,7 +113,7 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     n = s["query_points_3d"].shape[1]
-    print(f"predictor call: {1e3 * dt:.1f} ms = {T / dt:.1f} frames/s = {n * T / dt:.0f} query-points*frames/s; "
+    print(f"{'streaming session' if args.streaming else 'predictor call'}: {1e3 * dt:.1f} ms = {T / dt:.1f} frames/s = {n * T / dt:.0f} query-points*frames/s; "
           f"{int(out['vis_e'].sum())} of {out['vis_e'].numel()} track points visible; NaN guard {'TRIPPED' if predictor.last_nan else 'clean'}")
     if args.save_npz:
         sample_io.save_result(args.save_npz, out["traj_e"], out["vis_e"], s, temporal_stride=args.temporal_stride,

@@ -382,6 +382,33 @@ int mvt_corr_gather_dot_opts(int levels, const float* const* xyz, const void* co
 int mvt_knn1_gather(const void* fvec, int fvec_bf16, long long P, int C, const unsigned long long* keys, int n, int nseg,
                     int frame, float* feat_out, int* idx_out, void* stream);
 
+/* Ring forms of the entries above that map a window slot to a store frame (streaming: device memory independent of the clip
+ * length).  The store tensors -- xyz [R][P][4], fvec [R][P][C], tile_box / group_box [R][..][8] -- hold R frame slots; frame f
+ * lives in slot (f - base) mod R and frames [lo, hi] are resident (base <= lo <= hi, hi - lo < R).  Slot s of a window reads frame
+ *   clamp(frame0 + s*frame_step, lo, hi)
+ * (hi = the last frame received: the repeat-last-frame padding at the clip's end), frame0 itself must be resident.  Everything else
+ * -- arguments, results, tie rules -- is the linear entry's: on the same frames the two forms give the same bits. */
+int mvt_knn_scan_ring(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int base, int R,
+                      int lo, int hi, int K, int nseg, unsigned long long* keys, const int* seed_idx, int seed_k, int seed_cw,
+                      int seed_ch, int seed_fw, int seed_fh, const float* tile_box, int grid_w, int grid_h, void* stream);
+int mvt_knn_search_ring(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int base, int R,
+                        int lo, int hi, int K, const int* seed_idx, int seed_k, int seed_cw, int seed_ch, int seed_fw, int seed_fh,
+                        const float* tile_box, const float* group_box, int grid_w, int grid_h, int* idx_out, void* stream);
+int mvt_knn_scan_levels_ring(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
+                             int base, int R, int lo, int hi, int K, int seed_k, void* stream);
+int mvt_knn_search_levels_ring(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
+                               int base, int R, int lo, int hi, int K, int seed_k, void* stream);
+int mvt_corr_gather_dot_ring(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
+                             const int* const* idx, int C, const float* targets, const float* coords, int N, int S, int frame0,
+                             int frame_step, int base, int R, int lo, int hi, int K, float* out, int ldo, int o_off, void* stream);
+int mvt_corr_gather_dot_opts_ring(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
+                                  const int* const* idx, int C, const float* targets, const float* coords, int N, int S, int frame0,
+                                  int frame_step, int base, int R, int lo, int hi, int K, int groups, int add_offset, int add_xyz,
+                                  float* out, int ldo, int o_off, void* stream);
+/* mvt_knn1_gather of frame `frame` (resident: lo <= frame <= hi) of a ring store. */
+int mvt_knn1_gather_ring(const void* fvec, int fvec_bf16, long long P, int C, const unsigned long long* keys, int n, int nseg,
+                         int frame, int base, int R, int lo, int hi, float* feat_out, int* idx_out, void* stream);
+
 /* Secondary operator: bilinear-window correlation (CorrBlock.corr_sample,
  * spatracker/blocks.py:492-533 + bilinear_sampler :604-619).  fmap_l channels-last
  * [BS][h][w][C] for ONE level; targets [BS][N][C]; coords [BS][N][2] level-0 pixels;
@@ -475,6 +502,12 @@ int mvt_window_prepare_mapped(const float* qxyz, const int* qt, const float* fea
  * order [n] int64. */
 int mvt_window_store(const float* coords, const float* vis, const long long* order, int n, int S, int w, int T, int N, float* traj,
                      float* vis_logit, float* vis_prob, void* stream);
+/* mvt_window_store into a chunk of the clip (streaming): traj [f1-f0][N][3], vis_* [f1-f0][N] hold frames [f0, f1) of a clip of T
+ * frames (T: as far as it is known, f1 <= T), and the window's slots s with f0 <= w + s < f1 go to row w + s - f0 -- what
+ * mvt_window_store writes to those frames of the whole-clip tensors; no slot inside: nothing is written.  Rows no window writes keep
+ * what the caller put there (zeros, as in the whole-clip result). */
+int mvt_window_store_chunk(const float* coords, const float* vis, const long long* order, int n, int S, int w, int T, int f0, int f1,
+                           int N, float* traj, float* vis_logit, float* vis_prob, void* stream);
 /* The window state and result store of the time-reversed pass (backward tracking).  wr is the window start in REVERSED time:
  * slot s is frame max(T-1-wr - s, 0) of the clip; the n tracks are sorted by DESCENDING query frame and qt [n] holds the query
  * frames themselves.  mvt_window_prepare_reversed is mvt_window_prepare on the time-flipped clip (track mask frame <= qt, carried

@@ -105,9 +105,17 @@ __device__ __forceinline__ unsigned long long rank_sort(const unsigned long long
 // Store frame of window slot s: frame0 + s * frame_step clamped to the clip.  frame_step > 0 is the reference's window (slots past the
 // clip repeat the last frame, mvtracker.py:598-604); frame_step < 0 is the time-reversed pass of backward tracking, whose slots
 // run downwards from frame0 and repeat frame 0 past the clip's start.
-__device__ __forceinline__ int store_frame(int frame0, int s, int frame_step, int T) {
+// The store is addressed through a FrameRing: frames [lo, hi] are resident, frame f in slot (f - base) mod R.  The launchers pass
+// off = base + k R with 0 <= lo - off < R and require hi - lo < R, so f - off lies in [0, 2R) and one conditional subtraction is
+// the modulo.  A linear store of T frames is the ring (lo 0, hi T-1, off 0, R T): the slot is the clamped frame itself.
+struct FrameRing {
+  int lo, hi, off, R;
+};
+
+__device__ __forceinline__ int store_frame(int frame0, int s, int frame_step, FrameRing fr) {
   const int f = frame0 + s * frame_step;
-  return f < 0 ? 0 : (f < T - 1 ? f : T - 1);
+  const int slot = (f < fr.lo ? fr.lo : (f < fr.hi ? f : fr.hi)) - fr.off;
+  return slot < fr.R ? slot : slot - fr.R;
 }
 
 // Candidate tiles.  The scan visits the cloud 64 points (one wave load) at a time:
@@ -197,7 +205,7 @@ __global__ __launch_bounds__(256) void tile_group_aabb_kernel(const float* __res
 
 template <int Q>
 __device__ __forceinline__ void knn_scan_body(unsigned long long* lds, const float* __restrict__ xyz, long long P,
-                                              const float* __restrict__ coords, int N, int S, int frame0, int frame_step, int T, int K,
+                                              const float* __restrict__ coords, int N, int S, int frame0, int frame_step, FrameRing fr, int K,
                                               int nseg, unsigned long long* __restrict__ keys, int qgroups,
                                               const int* __restrict__ seed_idx, int seed_k, int seed_cw, int seed_ch, int seed_fw,
                                               int seed_fh, const float* __restrict__ box, int grid_w, int grid_h,
@@ -220,7 +228,7 @@ __device__ __forceinline__ void knn_scan_body(unsigned long long* lds, const flo
   const int seg = (int)(task - tq * (unsigned)nseg);
   const int s = (int)(tq / (unsigned)qgroups);
   const int qg = (int)(tq - (unsigned)s * (unsigned)qgroups);
-  const int frame = store_frame(frame0, s, frame_step, T);
+  const int frame = store_frame(frame0, s, frame_step, fr);
   const float* cand = xyz + (long long)frame * P * 4;
   const int ntiles = (int)((P + 63) >> 6);
   const int tper = (ntiles + nseg - 1) / nseg;
@@ -418,13 +426,13 @@ __device__ __forceinline__ void knn_scan_body(unsigned long long* lds, const flo
 
 template <int Q>
 __global__ __launch_bounds__(256) void knn_scan_kernel(const float* __restrict__ xyz, long long P, const float* __restrict__ coords,
-                                                       int N, int S, int frame0, int frame_step, int T, int K, int nseg,
+                                                       int N, int S, int frame0, int frame_step, FrameRing fr, int K, int nseg,
                                                        unsigned long long* __restrict__ keys, int qgroups,
                                                        const int* __restrict__ seed_idx, int seed_k, int seed_cw, int seed_ch,
                                                        int seed_fw, int seed_fh, const float* __restrict__ box, int grid_w, int grid_h,
                                                        int* __restrict__ idx_direct, const float* __restrict__ gbox) {
   __shared__ unsigned long long lds[4 * Q * CAP];
-  knn_scan_body<Q>(lds, xyz, P, coords, N, S, frame0, frame_step, T, K, nseg, keys, qgroups, seed_idx, seed_k, seed_cw, seed_ch, seed_fw,
+  knn_scan_body<Q>(lds, xyz, P, coords, N, S, frame0, frame_step, fr, K, nseg, keys, qgroups, seed_idx, seed_k, seed_cw, seed_ch, seed_fw,
                    seed_fh, box, grid_w, grid_h, idx_direct, gbox);
 }
 
@@ -436,10 +444,10 @@ struct KnnLevels {
 
 template <int Q>
 __global__ __launch_bounds__(256) void knn_scan_levels_kernel(KnnLevels a, const float* __restrict__ coords, int N, int S, int frame0,
-                                                              int frame_step, int T, int K, int qgroups, int seed_k) {
+                                                              int frame_step, FrameRing fr, int K, int qgroups, int seed_k) {
   __shared__ unsigned long long lds[4 * Q * CAP];
   const mvt_knn_level L = a.lv[blockIdx.y];
-  knn_scan_body<Q>(lds, L.xyz, L.P, coords, N, S, frame0, frame_step, T, K, L.nseg, L.keys, qgroups, L.seed_idx, seed_k, 0, 0, 0, 0,
+  knn_scan_body<Q>(lds, L.xyz, L.P, coords, N, S, frame0, frame_step, fr, K, L.nseg, L.keys, qgroups, L.seed_idx, seed_k, 0, 0, 0, 0,
                    L.tile_box, L.grid_w, L.grid_h);
 }
 
@@ -447,10 +455,10 @@ __global__ __launch_bounds__(256) void knn_scan_levels_kernel(KnnLevels a, const
 // the seeds of its own (track, slot) entries before it writes them, so idx_out may alias seed_idx.
 template <int Q>
 __global__ __launch_bounds__(256) void knn_search_levels_kernel(KnnLevels a, const float* __restrict__ coords, int N, int S, int frame0,
-                                                                int frame_step, int T, int K, int qgroups, int seed_k) {
+                                                                int frame_step, FrameRing fr, int K, int qgroups, int seed_k) {
   __shared__ unsigned long long lds[4 * Q * CAP];
   const mvt_knn_level L = a.lv[blockIdx.y];
-  knn_scan_body<Q>(lds, L.xyz, L.P, coords, N, S, frame0, frame_step, T, K, 1, nullptr, qgroups, L.seed_idx, seed_k, 0, 0, 0, 0, L.tile_box,
+  knn_scan_body<Q>(lds, L.xyz, L.P, coords, N, S, frame0, frame_step, fr, K, 1, nullptr, qgroups, L.seed_idx, seed_k, 0, 0, 0, 0, L.tile_box,
                    L.grid_w, L.grid_h, L.idx_out, L.group_box, true);
 }
 
@@ -504,7 +512,7 @@ struct CorrLevels {
 template <int LPR, int BF>
 __global__ __launch_bounds__(256) void corr_gather_dot_kernel(CorrLevels lv, const float* __restrict__ targets,
                                                               const float* __restrict__ coords, int N, int S, int frame0,
-                                                              int frame_step, int T, int K, float* __restrict__ out, int ldo, int o_off) {
+                                                              int frame_step, FrameRing fr, int K, float* __restrict__ out, int ldo, int o_off) {
   constexpr int EPL = BF ? 8 : 4;  // elements per lane
   constexpr int C = EPL * LPR;
   constexpr int RPL = 64 / LPR;  // rows per wave load
@@ -513,7 +521,7 @@ __global__ __launch_bounds__(256) void corr_gather_dot_kernel(CorrLevels lv, con
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);  // n * S + s
   if (row >= (long long)N * S) return;
   const int s = (int)(row % S);
-  const int frame = store_frame(frame0, s, frame_step, T);
+  const int frame = store_frame(frame0, s, frame_step, fr);
   const long long P = lv.P[level];
   const float* __restrict__ xyz = lv.xyz[level];
   const float* __restrict__ fvec = lv.fvec[level];
@@ -586,7 +594,7 @@ __global__ __launch_bounds__(256) void corr_gather_dot_kernel(CorrLevels lv, con
 template <int LPR, int BF>
 __global__ __launch_bounds__(256) void corr_gather_dot_opts_kernel(CorrLevels lv, const float* __restrict__ targets,
                                                                    const float* __restrict__ coords, int N, int S, int frame0,
-                                                                   int frame_step, int T, int K, float* __restrict__ out, int ldo, int o_off,
+                                                                   int frame_step, FrameRing fr, int K, float* __restrict__ out, int ldo, int o_off,
                                                                    int G, int add_offset, int add_xyz) {
   constexpr int EPL = BF ? 8 : 4;
   constexpr int C = EPL * LPR;
@@ -596,7 +604,7 @@ __global__ __launch_bounds__(256) void corr_gather_dot_opts_kernel(CorrLevels lv
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);  // n * S + s
   if (row >= (long long)N * S) return;
   const int s = (int)(row % S);
-  const int frame = store_frame(frame0, s, frame_step, T);
+  const int frame = store_frame(frame0, s, frame_step, fr);
   const long long P = lv.P[level];
   const float* __restrict__ xyz = lv.xyz[level];
   const float* __restrict__ fvec = lv.fvec[level];
@@ -834,6 +842,20 @@ __global__ __launch_bounds__(256) void window_corr_levels_kernel(WinLevels lv, c
 
 }  // namespace
 
+// The FrameRing of a linear store of T frames, and of a ring store (frame f in slot (f - base) mod R, frames [lo, hi] resident):
+// false = arguments rejected.  frame0 must be a resident frame; every other slot is clamped into [lo, hi] by the kernels.
+static bool linear_frames(int T, int frame0, FrameRing* fr) {
+  if (T <= 0 || frame0 < 0 || frame0 >= T) return false;
+  *fr = FrameRing{0, T - 1, 0, T};
+  return true;
+}
+
+static bool ring_frames(int base, int R, int lo, int hi, int frame0, FrameRing* fr) {
+  if (R <= 0 || base < 0 || lo < base || hi < lo || hi - lo >= R || frame0 < lo || frame0 > hi) return false;
+  *fr = FrameRing{lo, hi, base + (lo - base) / R * R, R};
+  return true;
+}
+
 extern "C" int mvt_tile_aabb(const float* xyz, long long P, int T, int grid_w, int grid_h, float* box, void* stream) {
   MVT_REQUIRE(xyz && box && P > 0 && T > 0 && P < (1LL << 31));
   MVT_REQUIRE((grid_w == 0 && grid_h == 0) || (grid_w > 0 && grid_h > 0 && grid_w % 8 == 0 && grid_h % 8 == 0 && P % ((long long)grid_w * grid_h) == 0));
@@ -851,32 +873,34 @@ extern "C" int mvt_tile_group_aabb(const float* box, long long P, int T, float* 
   return mvt_launch_status();
 }
 
-static int knn_scan_launch(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int T, int K, int nseg,
+static int knn_scan_launch(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, FrameRing fr, int K, int nseg,
                            unsigned long long* keys, const int* seed_idx, int seed_k, int seed_cw, int seed_ch, int seed_fw, int seed_fh,
                            const float* tile_box, int grid_w, int grid_h, int* idx_direct, const float* group_box, void* stream);
 
 extern "C" int mvt_knn_scan(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int T,
                             int K, int nseg, unsigned long long* keys, const int* seed_idx, int seed_k, int seed_cw, int seed_ch,
                             int seed_fw, int seed_fh, const float* tile_box, int grid_w, int grid_h, void* stream) {
-  MVT_REQUIRE(keys);
-  return knn_scan_launch(xyz, P, coords, N, S, frame0, frame_step, T, K, nseg, keys, seed_idx, seed_k, seed_cw, seed_ch, seed_fw, seed_fh,
+  FrameRing fr;
+  MVT_REQUIRE(keys && linear_frames(T, frame0, &fr));
+  return knn_scan_launch(xyz, P, coords, N, S, frame0, frame_step, fr, K, nseg, keys, seed_idx, seed_k, seed_cw, seed_ch, seed_fw, seed_fh,
                          tile_box, grid_w, grid_h, nullptr, nullptr, stream);
 }
 
 extern "C" int mvt_knn_search(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int T, int K,
                               const int* seed_idx, int seed_k, int seed_cw, int seed_ch, int seed_fw, int seed_fh, const float* tile_box,
                               const float* group_box, int grid_w, int grid_h, int* idx_out, void* stream) {
-  MVT_REQUIRE(idx_out && tile_box);
-  return knn_scan_launch(xyz, P, coords, N, S, frame0, frame_step, T, K, 1, nullptr, seed_idx, seed_k, seed_cw, seed_ch, seed_fw, seed_fh,
+  FrameRing fr;
+  MVT_REQUIRE(idx_out && tile_box && linear_frames(T, frame0, &fr));
+  return knn_scan_launch(xyz, P, coords, N, S, frame0, frame_step, fr, K, 1, nullptr, seed_idx, seed_k, seed_cw, seed_ch, seed_fw, seed_fh,
                          tile_box, grid_w, grid_h, idx_out, group_box, stream);
 }
 
-static int knn_scan_launch(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int T, int K, int nseg,
+static int knn_scan_launch(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, FrameRing fr, int K, int nseg,
                            unsigned long long* keys, const int* seed_idx, int seed_k, int seed_cw, int seed_ch, int seed_fw, int seed_fh,
                            const float* tile_box, int grid_w, int grid_h, int* idx_direct, const float* group_box, void* stream) {
   MVT_REQUIRE(!seed_idx || (seed_k >= K && seed_k <= 64 && seed_cw >= 0));
   MVT_REQUIRE(!seed_idx || seed_cw == 0 || (seed_ch > 0 && seed_fw >= 2 * seed_cw && seed_fh >= 2 * seed_ch));
-  MVT_REQUIRE(xyz && coords && (keys || idx_direct) && N > 0 && S > 0 && T > 0 && frame0 >= 0 && frame0 < T);
+  MVT_REQUIRE(xyz && coords && (keys || idx_direct) && N > 0 && S > 0);
   MVT_REQUIRE(K >= 1 && K <= 16 && nseg >= 1 && nseg * K <= 64 && P < (1LL << 31) && P >= K);
   MVT_REQUIRE((grid_w == 0 && grid_h == 0) || (grid_w > 0 && grid_h > 0 && grid_w % 8 == 0 && grid_h % 8 == 0 && P % ((long long)grid_w * grid_h) == 0));
   const long long ntiles = (P + 63) / 64, tper = (ntiles + nseg - 1) / nseg;
@@ -890,7 +914,7 @@ static int knn_scan_launch(const float* xyz, long long P, const float* coords, i
   MVT_REQUIRE(ntask < (1LL << 31));
 #define LAUNCH(QQ)                                                                                                                   \
   hipLaunchKernelGGL((knn_scan_kernel<QQ>), dim3((unsigned)mvt_cdiv(ntask, 4)), dim3(256), 0, mvt_stream(stream), xyz, P, coords, N, S, \
-                     frame0, frame_step, T, K, nseg, keys, qgroups, seed_idx, seed_k, seed_cw, seed_ch, seed_fw, seed_fh, tile_box,    \
+                     frame0, frame_step, fr, K, nseg, keys, qgroups, seed_idx, seed_k, seed_cw, seed_ch, seed_fw, seed_fh, tile_box,    \
                      grid_w, grid_h, idx_direct, group_box)
   switch (Q) {
     case 1: LAUNCH(1); break;
@@ -912,9 +936,9 @@ static int knn_check_level(const mvt_knn_level& L, int K) {
   return MVT_OK;
 }
 
-extern "C" int mvt_knn_scan_levels(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
-                                   int T, int K, int seed_k, void* stream) {
-  MVT_REQUIRE(levels >= 1 && levels <= 8 && lv && coords && N > 0 && S > 0 && T > 0 && frame0 >= 0 && frame0 < T);
+static int knn_scan_levels_impl(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
+                                   FrameRing fr, int K, int seed_k, void* stream) {
+  MVT_REQUIRE(levels >= 1 && levels <= 8 && lv && coords && N > 0 && S > 0);
   MVT_REQUIRE(K >= 1 && K <= 16 && (seed_k == 0 || (seed_k >= K && seed_k <= 64)));
   KnnLevels a{};
   int max_nseg = 1;
@@ -932,7 +956,7 @@ extern "C" int mvt_knn_scan_levels(int levels, const mvt_knn_level* lv, const fl
   MVT_REQUIRE((long long)qgroups * S * max_nseg < (1LL << 31));
   const dim3 grid((unsigned)mvt_cdiv((long long)qgroups * S * max_nseg, 4), (unsigned)levels);
 #define LAUNCH(QQ)                                                                                                              \
-  hipLaunchKernelGGL((knn_scan_levels_kernel<QQ>), grid, dim3(256), 0, mvt_stream(stream), a, coords, N, S, frame0, frame_step, T, K, \
+  hipLaunchKernelGGL((knn_scan_levels_kernel<QQ>), grid, dim3(256), 0, mvt_stream(stream), a, coords, N, S, frame0, frame_step, fr, K, \
                      qgroups, seed_k)
   switch (Q) {
     case 1: LAUNCH(1); break;
@@ -959,9 +983,9 @@ extern "C" int mvt_knn_merge_levels(int levels, const mvt_knn_level* lv, int N, 
   return mvt_launch_status();
 }
 
-extern "C" int mvt_knn_search_levels(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
-                                     int T, int K, int seed_k, void* stream) {
-  MVT_REQUIRE(levels >= 1 && levels <= 8 && lv && coords && N > 0 && S > 0 && T > 0 && frame0 >= 0 && frame0 < T);
+static int knn_search_levels_impl(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
+                                     FrameRing fr, int K, int seed_k, void* stream) {
+  MVT_REQUIRE(levels >= 1 && levels <= 8 && lv && coords && N > 0 && S > 0);
   MVT_REQUIRE(K >= 1 && K <= 16 && (seed_k == 0 || (seed_k >= K && seed_k <= 64)));
   KnnLevels a{};
   for (int l = 0; l < levels; ++l) {
@@ -977,7 +1001,7 @@ extern "C" int mvt_knn_search_levels(int levels, const mvt_knn_level* lv, const 
   MVT_REQUIRE((long long)qgroups * S < (1LL << 31));
   const dim3 grid((unsigned)mvt_cdiv((long long)qgroups * S, 4), (unsigned)levels);
 #define LAUNCH(QQ)                                                                                                                \
-  hipLaunchKernelGGL((knn_search_levels_kernel<QQ>), grid, dim3(256), 0, mvt_stream(stream), a, coords, N, S, frame0, frame_step, T, K, \
+  hipLaunchKernelGGL((knn_search_levels_kernel<QQ>), grid, dim3(256), 0, mvt_stream(stream), a, coords, N, S, frame0, frame_step, fr, K, \
                      qgroups, seed_k)
   switch (Q) {
     case 1: LAUNCH(1); break;
@@ -998,12 +1022,12 @@ extern "C" int mvt_knn_merge(const unsigned long long* keys, int N, int S, int K
   return mvt_launch_status();
 }
 
-extern "C" int mvt_corr_gather_dot(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
+static int corr_gather_dot_impl(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
                                    const int* const* idx, int C, const float* targets, const float* coords, int N, int S,
-                                   int frame0, int frame_step, int T, int K, float* out, int ldo, int o_off, void* stream) {
+                                   int frame0, int frame_step, FrameRing fr, int K, float* out, int ldo, int o_off, void* stream) {
   MVT_REQUIRE(levels >= 1 && levels <= 8 && xyz && fvec && P && idx && targets && coords && out);
   MVT_REQUIRE((fvec_bf16 == 0 || fvec_bf16 == 1));
-  MVT_REQUIRE(N > 0 && S > 0 && T > 0 && frame0 >= 0 && frame0 < T && K >= 1 && K <= 16);
+  MVT_REQUIRE(N > 0 && S > 0 && K >= 1 && K <= 16);
   MVT_REQUIRE(o_off >= 0 && ldo >= o_off + levels * 4 * K);
   CorrLevels lv{};
   for (int l = 0; l < levels; ++l) {
@@ -1016,7 +1040,7 @@ extern "C" int mvt_corr_gather_dot(int levels, const float* const* xyz, const vo
   const dim3 grid((unsigned)mvt_cdiv((long long)N * S, 4), (unsigned)levels);
 #define LAUNCH(LPR, BF)                                                                                                              \
   hipLaunchKernelGGL((corr_gather_dot_kernel<LPR, BF>), grid, dim3(256), 0, mvt_stream(stream), lv, (const float*)targets, coords, N, S, \
-                     frame0, frame_step, T, K, out, ldo, o_off)
+                     frame0, frame_step, fr, K, out, ldo, o_off)
   if (fvec_bf16) {
     switch (C) {
       case 32: LAUNCH(4, 1); break;
@@ -1108,13 +1132,13 @@ extern "C" int mvt_window_corr_levels(int levels, const void* const* fmaps, int 
   return mvt_launch_status();
 }
 
-extern "C" int mvt_corr_gather_dot_opts(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
+static int corr_gather_dot_opts_impl(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
                                         const int* const* idx, int C, const float* targets, const float* coords, int N, int S, int frame0,
-                                        int frame_step, int T, int K, int groups, int add_offset, int add_xyz, float* out, int ldo, int o_off,
+                                        int frame_step, FrameRing fr, int K, int groups, int add_offset, int add_xyz, float* out, int ldo, int o_off,
                                         void* stream) {
   MVT_REQUIRE(levels >= 1 && levels <= 8 && xyz && fvec && P && idx && targets && coords && out);
   MVT_REQUIRE((fvec_bf16 == 0 || fvec_bf16 == 1) && (add_offset == 0 || add_offset == 1) && (add_xyz == 0 || add_xyz == 1));
-  MVT_REQUIRE(N > 0 && S > 0 && T > 0 && frame0 >= 0 && frame0 < T && K >= 1 && K <= 16);
+  MVT_REQUIRE(N > 0 && S > 0 && K >= 1 && K <= 16);
   const int lpr = fvec_bf16 ? C / 8 : C / 4;  // lanes per feature row
   MVT_REQUIRE(groups >= 1 && (groups & (groups - 1)) == 0 && lpr >= 1 && groups <= lpr && lpr % groups == 0);
   const int OW = groups + 3 * add_offset + 3 * add_xyz;
@@ -1130,7 +1154,7 @@ extern "C" int mvt_corr_gather_dot_opts(int levels, const float* const* xyz, con
   const dim3 grid((unsigned)mvt_cdiv((long long)N * S, 4), (unsigned)levels);
 #define LAUNCH(LPR, BF)                                                                                                                   \
   hipLaunchKernelGGL((corr_gather_dot_opts_kernel<LPR, BF>), grid, dim3(256), 0, mvt_stream(stream), lv, (const float*)targets, coords, N, S, \
-                     frame0, frame_step, T, K, out, ldo, o_off, groups, add_offset, add_xyz)
+                     frame0, frame_step, fr, K, out, ldo, o_off, groups, add_offset, add_xyz)
   if (fvec_bf16) {
     switch (C) {
       case 32: LAUNCH(4, 1); break;
@@ -1151,3 +1175,102 @@ extern "C" int mvt_corr_gather_dot_opts(int levels, const float* const* xyz, con
 #undef LAUNCH
   return mvt_launch_status();
 }
+
+// ------------------------------------------------------------------------------------------------
+// The entries that map window slots to store frames, in their linear form (a store of T frames) and their ring form (frames
+// [lo, hi] resident, frame f in slot (f - base) mod R): one kernel each, the FrameRing is the only difference.
+#define MVT_LINEAR(T) \
+  FrameRing fr;       \
+  MVT_REQUIRE(linear_frames(T, frame0, &fr))
+#define MVT_RING()  \
+  FrameRing fr;     \
+  MVT_REQUIRE(ring_frames(base, R, lo, hi, frame0, &fr))
+
+extern "C" int mvt_knn_scan_ring(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int base,
+                                 int R, int lo, int hi, int K, int nseg, unsigned long long* keys, const int* seed_idx, int seed_k,
+                                 int seed_cw, int seed_ch, int seed_fw, int seed_fh, const float* tile_box, int grid_w, int grid_h,
+                                 void* stream) {
+  MVT_REQUIRE(keys);
+  MVT_RING();
+  return knn_scan_launch(xyz, P, coords, N, S, frame0, frame_step, fr, K, nseg, keys, seed_idx, seed_k, seed_cw, seed_ch, seed_fw, seed_fh,
+                         tile_box, grid_w, grid_h, nullptr, nullptr, stream);
+}
+
+extern "C" int mvt_knn_search_ring(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int base,
+                                   int R, int lo, int hi, int K, const int* seed_idx, int seed_k, int seed_cw, int seed_ch, int seed_fw,
+                                   int seed_fh, const float* tile_box, const float* group_box, int grid_w, int grid_h, int* idx_out,
+                                   void* stream) {
+  MVT_REQUIRE(idx_out && tile_box);
+  MVT_RING();
+  return knn_scan_launch(xyz, P, coords, N, S, frame0, frame_step, fr, K, 1, nullptr, seed_idx, seed_k, seed_cw, seed_ch, seed_fw, seed_fh,
+                         tile_box, grid_w, grid_h, idx_out, group_box, stream);
+}
+
+extern "C" int mvt_knn_scan_levels(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
+                                   int T, int K, int seed_k, void* stream) {
+  MVT_LINEAR(T);
+  return knn_scan_levels_impl(levels, lv, coords, N, S, frame0, frame_step, fr, K, seed_k, stream);
+}
+
+extern "C" int mvt_knn_scan_levels_ring(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0,
+                                        int frame_step, int base, int R, int lo, int hi, int K, int seed_k, void* stream) {
+  MVT_RING();
+  return knn_scan_levels_impl(levels, lv, coords, N, S, frame0, frame_step, fr, K, seed_k, stream);
+}
+
+extern "C" int mvt_knn_search_levels(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
+                                     int T, int K, int seed_k, void* stream) {
+  MVT_LINEAR(T);
+  return knn_search_levels_impl(levels, lv, coords, N, S, frame0, frame_step, fr, K, seed_k, stream);
+}
+
+extern "C" int mvt_knn_search_levels_ring(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0,
+                                          int frame_step, int base, int R, int lo, int hi, int K, int seed_k, void* stream) {
+  MVT_RING();
+  return knn_search_levels_impl(levels, lv, coords, N, S, frame0, frame_step, fr, K, seed_k, stream);
+}
+
+extern "C" int mvt_corr_gather_dot(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
+                                   const int* const* idx, int C, const float* targets, const float* coords, int N, int S,
+                                   int frame0, int frame_step, int T, int K, float* out, int ldo, int o_off, void* stream) {
+  MVT_LINEAR(T);
+  return corr_gather_dot_impl(levels, xyz, fvec, fvec_bf16, P, idx, C, targets, coords, N, S, frame0, frame_step, fr, K, out, ldo, o_off,
+                              stream);
+}
+
+extern "C" int mvt_corr_gather_dot_ring(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
+                                        const int* const* idx, int C, const float* targets, const float* coords, int N, int S,
+                                        int frame0, int frame_step, int base, int R, int lo, int hi, int K, float* out, int ldo,
+                                        int o_off, void* stream) {
+  MVT_RING();
+  return corr_gather_dot_impl(levels, xyz, fvec, fvec_bf16, P, idx, C, targets, coords, N, S, frame0, frame_step, fr, K, out, ldo, o_off,
+                              stream);
+}
+
+extern "C" int mvt_corr_gather_dot_opts(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
+                                        const int* const* idx, int C, const float* targets, const float* coords, int N, int S, int frame0,
+                                        int frame_step, int T, int K, int groups, int add_offset, int add_xyz, float* out, int ldo, int o_off,
+                                        void* stream) {
+  MVT_LINEAR(T);
+  return corr_gather_dot_opts_impl(levels, xyz, fvec, fvec_bf16, P, idx, C, targets, coords, N, S, frame0, frame_step, fr, K, groups,
+                                   add_offset, add_xyz, out, ldo, o_off, stream);
+}
+
+extern "C" int mvt_corr_gather_dot_opts_ring(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16,
+                                             const long long* P, const int* const* idx, int C, const float* targets, const float* coords,
+                                             int N, int S, int frame0, int frame_step, int base, int R, int lo, int hi, int K, int groups,
+                                             int add_offset, int add_xyz, float* out, int ldo, int o_off, void* stream) {
+  MVT_RING();
+  return corr_gather_dot_opts_impl(levels, xyz, fvec, fvec_bf16, P, idx, C, targets, coords, N, S, frame0, frame_step, fr, K, groups,
+                                   add_offset, add_xyz, out, ldo, o_off, stream);
+}
+
+// (the 1-NN gather reads one frame: its ring form only turns the frame into its slot)
+extern "C" int mvt_knn1_gather_ring(const void* fvec, int fvec_bf16, long long P, int C, const unsigned long long* keys, int n, int nseg,
+                                    int frame, int base, int R, int lo, int hi, float* feat_out, int* idx_out, void* stream) {
+  const int frame0 = frame;
+  MVT_RING();
+  return mvt_knn1_gather(fvec, fvec_bf16, P, C, keys, n, nseg, (frame - fr.off) % R, feat_out, idx_out, stream);
+}
+#undef MVT_LINEAR
+#undef MVT_RING

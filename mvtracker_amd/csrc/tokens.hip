@@ -122,6 +122,25 @@ __global__ void window_store_kernel(const float* __restrict__ coords, const floa
   }
 }
 
+// window_store_kernel for streaming: the output is a chunk of the clip, frames [f0, f1), and only the window's slots inside it are
+// written -- chunk [f - f0][N][.] = what window_store_kernel writes to frame f of the whole-clip tensors.
+__global__ void window_store_chunk_kernel(const float* __restrict__ coords, const float* __restrict__ vis,
+                                          const long long* __restrict__ order, int n, int S, int w, int s0, int ns, int f0, int N,
+                                          float* __restrict__ traj, float* __restrict__ vis_logit, float* __restrict__ vis_prob) {
+  const long long total = (long long)n * ns;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int s = s0 + (int)(i % ns);
+    const int tr = (int)(i / ns);
+    const long long src = (long long)tr * S + s;
+    const long long dst = (long long)(w + s - f0) * N + order[tr];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) traj[dst * 3 + a] = coords[src * 3 + a];
+    const float lg = vis[src];
+    vis_logit[dst] = lg;
+    vis_prob[dst] = 1.0f / (1.0f + expf(-lg));
+  }
+}
+
 // The two kernels above for the time-reversed pass of backward tracking: the window starts at wr in REVERSED time (frame T-1-wr of
 // the clip) and slot s reads frame max(T-1-wr - s, 0), the tracks are sorted by descending query frame and qt holds the query frames
 // themselves.  This is window_prepare_kernel on the flipped clip written in the clip's own frame numbers: the mask is
@@ -332,6 +351,19 @@ extern "C" int mvt_window_store(const float* coords, const float* vis, const lon
   MVT_REQUIRE(coords && vis && order && traj && vis_logit && vis_prob && n > 0 && n <= N && S > 0 && w >= 0 && w < T);
   hipLaunchKernelGGL(window_store_kernel, dim3(grid_for((long long)n * S)), dim3(256), 0, mvt_stream(stream), coords, vis, order, n, S, w, T,
                      N, traj, vis_logit, vis_prob);
+  return mvt_launch_status();
+}
+
+extern "C" int mvt_window_store_chunk(const float* coords, const float* vis, const long long* order, int n, int S, int w, int T, int f0,
+                                      int f1, int N, float* traj, float* vis_logit, float* vis_prob, void* stream) {
+  MVT_REQUIRE(coords && vis && order && traj && vis_logit && vis_prob && n > 0 && n <= N && S > 0 && w >= 0 && w < T);
+  MVT_REQUIRE(f0 >= 0 && f1 > f0 && f1 <= T);
+  // the window's slots inside the chunk: s0 .. s1 - 1 (none: nothing to write); f1 <= T keeps them within the clip
+  const int s0 = f0 > w ? f0 - w : 0;
+  const int s1 = f1 - w < S ? f1 - w : S;
+  if (s1 <= s0) return MVT_OK;
+  hipLaunchKernelGGL(window_store_chunk_kernel, dim3(grid_for((long long)n * (s1 - s0))), dim3(256), 0, mvt_stream(stream), coords, vis,
+                     order, n, S, w, s0, s1 - s0, f0, N, traj, vis_logit, vis_prob);
   return mvt_launch_status();
 }
 

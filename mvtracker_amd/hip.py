@@ -67,6 +67,14 @@ SIGNATURES = {
     "mvt_corr_gather_dot": [I, P, P, I, P, P, I, P, P, I, I, I, I, I, I, P, I, I, P],
     "mvt_corr_gather_dot_opts": [I, P, P, I, P, P, I, P, P, I, I, I, I, I, I, I, I, I, P, I, I, P],
     "mvt_knn1_gather": [P, I, LL, I, P, I, I, I, P, P, P],
+    "mvt_knn_scan_ring": [P, LL, P, I, I, I, I, I, I, I, I, I, I, P, P, I, I, I, I, I, P, I, I, P],
+    "mvt_knn_search_ring": [P, LL, P, I, I, I, I, I, I, I, I, I, P, I, I, I, I, I, P, P, I, I, P, P],
+    "mvt_knn_scan_levels_ring": [I, P, P, I, I, I, I, I, I, I, I, I, I, P],
+    "mvt_knn_search_levels_ring": [I, P, P, I, I, I, I, I, I, I, I, I, I, P],
+    "mvt_corr_gather_dot_ring": [I, P, P, I, P, P, I, P, P, I, I, I, I, I, I, I, I, I, P, I, I, P],
+    "mvt_corr_gather_dot_opts_ring": [I, P, P, I, P, P, I, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, I, I, P],
+    "mvt_knn1_gather_ring": [P, I, LL, I, P, I, I, I, I, I, I, I, P, P, P],
+    "mvt_window_store_chunk": [P, P, P, I, I, I, I, I, I, I, P, P, P, P],
     "mvt_window_corr": [P, P, P, P, I, I, I, I, I, I, I, I, I, P],
     "mvt_window_corr_levels": [I, P, I, P, P, P, P, P, I, I, I, I, I, I, P],
     "mvt_pos_embed": [P, I, I, I, I, P, P, P],
@@ -447,6 +455,57 @@ def knn1_gather(fvec, Pn, Cc, keys, n, nseg, frame, feat_out, idx_out=None):
           _ptr(idx_out), _stream())
 
 
+# ---- ring forms (streaming): ``ring`` = (base, R, lo, hi) stands where the linear wrapper takes T -- the store tensors hold R frame
+# slots, frame f in slot (f - base) mod R, frames [lo, hi] resident, a window slot reads clamp(frame0 + s * frame_step, lo, hi)
+def knn_scan_ring(xyz, Pn, coords, N, S, frame0, frame_step, ring, K, nseg, keys, seed_idx=None, seed_k=0, seed_dims=(0, 0, 0, 0), box=None,
+                  grid=(0, 0)):
+    _call("mvt_knn_scan_ring", _ptr(xyz), Pn, _ptr(coords), N, S, frame0, frame_step, *ring, K, nseg, _ptr(keys), _ptr(seed_idx), seed_k,
+          *seed_dims, _ptr(box), grid[0], grid[1], _stream())
+
+
+def knn_search_ring(xyz, Pn, coords, N, S, frame0, frame_step, ring, K, idx_out, box, grid=(0, 0), gbox=None, seed_idx=None, seed_k=0,
+                    seed_dims=(0, 0, 0, 0)):
+    _call("mvt_knn_search_ring", _ptr(xyz), Pn, _ptr(coords), N, S, frame0, frame_step, *ring, K, _ptr(seed_idx), seed_k, *seed_dims,
+          _ptr(box), _ptr(gbox), grid[0], grid[1], _ptr(idx_out), _stream())
+
+
+def knn_scan_levels_ring(levels, coords, N, S, frame0, frame_step, ring, K, seed_k=0):
+    arr = _knn_levels(levels)
+    _call("mvt_knn_scan_levels_ring", len(levels), C.cast(arr, C.c_void_p), _ptr(coords), N, S, frame0, frame_step, *ring, K, seed_k, _stream())
+
+
+def knn_search_levels_ring(levels, coords, N, S, frame0, frame_step, ring, K, seed_k):
+    arr = _knn_levels([dict(lv, keys=None, nseg=1) for lv in levels])
+    _call("mvt_knn_search_levels_ring", len(levels), C.cast(arr, C.c_void_p), _ptr(coords), N, S, frame0, frame_step, *ring, K, seed_k,
+          _stream())
+
+
+def corr_gather_dot_ring(xyz_l, fvec_l, P_l, idx_l, Cc, targets, coords, N, S, frame0, frame_step, ring, K, out, ldo, o_off):
+    n = len(xyz_l)
+    pa = (C.c_void_p * n)
+    bf = fvec_l[0].dtype == torch.bfloat16
+    assert all((t.dtype == torch.bfloat16) == bf for t in fvec_l)
+    _call("mvt_corr_gather_dot_ring", n, pa(*[_ptr(t) for t in xyz_l]), pa(*[_ptr(t) for t in fvec_l]), 1 if bf else 0,
+          (C.c_longlong * n)(*P_l), pa(*[_ptr(t) for t in idx_l]), Cc, _ptr(targets), _ptr(coords), N, S, frame0, frame_step, *ring, K,
+          _ptr(out), ldo, o_off, _stream())
+
+
+def corr_gather_dot_opts_ring(xyz_l, fvec_l, P_l, idx_l, Cc, targets, coords, N, S, frame0, frame_step, ring, K, groups, add_offset, add_xyz,
+                              out, ldo, o_off):
+    n = len(xyz_l)
+    pa = (C.c_void_p * n)
+    bf = fvec_l[0].dtype == torch.bfloat16
+    assert all((t.dtype == torch.bfloat16) == bf for t in fvec_l)
+    _call("mvt_corr_gather_dot_opts_ring", n, pa(*[_ptr(t) for t in xyz_l]), pa(*[_ptr(t) for t in fvec_l]), 1 if bf else 0,
+          (C.c_longlong * n)(*P_l), pa(*[_ptr(t) for t in idx_l]), Cc, _ptr(targets), _ptr(coords), N, S, frame0, frame_step, *ring, K,
+          groups, 1 if add_offset else 0, 1 if add_xyz else 0, _ptr(out), ldo, o_off, _stream())
+
+
+def knn1_gather_ring(fvec, Pn, Cc, keys, n, nseg, frame, ring, feat_out, idx_out=None):
+    _call("mvt_knn1_gather_ring", _ptr(fvec), 1 if fvec.dtype == torch.bfloat16 else 0, Pn, Cc, _ptr(keys), n, nseg, frame, *ring,
+          _ptr(feat_out), _ptr(idx_out), _stream())
+
+
 def window_corr(fmap, targets, coords, out, BS, N, Cc, h, w, level, radius, ldo, o_off):
     _call("mvt_window_corr", _ptr(fmap), _ptr(targets), _ptr(coords), _ptr(out), BS, N, Cc, h, w, level, radius, ldo, o_off,
           _stream())
@@ -552,6 +611,14 @@ def window_prepare(qxyz, qt, feat_init, prev_coords, prev_vis, n, p0, S, Cc, w, 
 def window_store(coords, vis, order, n, S, w, T, N, traj, vis_logit, vis_prob):
     assert order.dtype == torch.int64
     _call("mvt_window_store", _ptr(coords), _ptr(vis), _ptr(order), n, S, w, T, N, _ptr(traj), _ptr(vis_logit), _ptr(vis_prob), _stream())
+
+
+def window_store_chunk(coords, vis, order, n, S, w, T, f0, f1, N, traj, vis_logit, vis_prob):
+    """``window_store`` into a chunk of the clip: traj (f1-f0, N, 3) / vis_* (f1-f0, N) hold frames [f0, f1) of a clip of T frames (as
+    far as known, f1 <= T); the window's slots outside the chunk are dropped."""
+    assert order.dtype == torch.int64 and traj.shape[0] == f1 - f0 and traj.shape[1] == N
+    _call("mvt_window_store_chunk", _ptr(coords), _ptr(vis), _ptr(order), n, S, w, T, f0, f1, N, _ptr(traj), _ptr(vis_logit), _ptr(vis_prob),
+          _stream())
 
 
 def window_prepare_reversed(qxyz, qt, feat_init, prev_coords, prev_vis, n, p0, S, Cc, wr, T, coords, mask_vis, ffeats):

@@ -35,6 +35,10 @@ class ShardedTracker:
         self.staged = os.environ.get("MVT_GATHER_INPLACE", "0") == "0"
         self.last_store = None  # the frame store of the last call (tests compare it with a single-rank encode)
 
+    def open_stream(self, *args, **kwargs):
+        raise NotImplementedError("there is no streaming form of ShardedTracker (a ring frame store sharded over ranks is not built): "
+                                  "open the session on one rank's model, MVTracker.open_stream")
+
     def _world(self):
         if dist.is_available() and dist.is_initialized():
             return dist.get_world_size(self.group), dist.get_rank(self.group)

@@ -312,3 +312,79 @@ class EvaluationPredictor(torch.nn.Module):
         else:
             self.last_nan = False
         return {"traj_e": traj_e, "vis_e": vis_e > self.visibility_threshold, "vis_e_as_prob": vis_e}
+
+    def open_stream(self, query_points_3d, ring_blocks=3):
+        """Streaming form of ``forward`` in joint mode (``MVTracker.open_stream``): returns a session whose
+        ``push(rgbs, depths, intrs, extrs)`` / ``finish()`` give {"frames": (a, b), "traj_e", "vis_e", "vis_e_as_prob"} for the
+        frames that became final, the same bits as ``forward`` on the whole clip."""
+        if self.single_point:
+            raise NotImplementedError("there is no streaming form of single_point mode (one forward per query, each with local "
+                                      "support grids around the query): use forward")
+        if self.backward_tracking:
+            raise NotImplementedError("there is no streaming form of backward_tracking (inherently offline)")
+        if self.sift_size > 0 or self.num_uniformly_sampled_pts > 0:
+            raise NotImplementedError("streaming supports the support grid only: uniformly sampled support points are drawn over the "
+                                      "whole clip, whose length a session does not know")
+        if self.grid_size > 0 and self.n_grids_per_view != 1:
+            raise NotImplementedError(f"streaming takes the support grid from the first pushed frame (n_grids_per_view == 1, the "
+                                      f"reference's t = 0 grid); n_grids_per_view = {self.n_grids_per_view} places grids at frames that "
+                                      f"depend on the clip length")
+        return _PredictorStream(self, query_points_3d, ring_blocks)
+
+
+class _PredictorStream:
+    """``EvaluationPredictor.open_stream``: per-block resize, intrinsics rescale and threshold exactly as in ``forward``; the
+    support grid is added as queries (behind the caller's) when the first frame arrives."""
+
+    def __init__(self, predictor, query_points_3d, ring_blocks):
+        self.p = predictor
+        if query_points_3d.dim() != 3 or query_points_3d.shape[0] != 1 or query_points_3d.shape[2] != 4:
+            raise ValueError(f"query points must be (1, N, 4), got {tuple(query_points_3d.shape)}")
+        self.num_points = query_points_3d.shape[1]
+        self.session = predictor.model.open_stream(query_points_3d.to(torch.float32), iters=predictor.n_iters, ring_blocks=ring_blocks)
+        self.first = True
+
+    def _result(self, res):
+        vis = res["vis_e"][:, :, :self.num_points]
+        return {"frames": res["frames"], "traj_e": res["traj_e"][:, :, :self.num_points, :], "vis_e": vis > self.p.visibility_threshold,
+                "vis_e_as_prob": vis}
+
+    @torch.no_grad()
+    def push(self, rgbs, depths, intrs, extrs):
+        p = self.p
+        with hip.device_guard(rgbs):
+            hip.require_device(rgbs)
+            dev = rgbs.device
+            _, V, b, _, height_raw, width_raw = rgbs.shape
+            if not (rgbs.dtype == torch.uint8 and p.interp_shape is None):
+                rgbs = rgbs.to(torch.float32)
+            rgbs = rgbs.contiguous()
+            depths = depths.to(torch.float32).contiguous()
+            intrs, extrs = intrs.to(torch.float32), extrs.to(torch.float32)
+            if p.interp_shape is not None:  # evaluation_predictor_3dpt.py:72-87, block by block
+                height, width = p.interp_shape
+                r = torch.empty(1, V, b, 3, height, width, device=dev)
+                hip.resize_nearest(rgbs, r, V * b * 3, height_raw, width_raw, height, width)
+                d = torch.empty(1, V, b, 1, height, width, device=dev)
+                hip.resize_nearest(depths, d, V * b, height_raw, width_raw, height, width)
+                rgbs, depths = r, d
+                rs = torch.tensor([[width / width_raw, 0, 0], [0, height / height_raw, 0], [0, 0, 1]], device=dev, dtype=intrs.dtype)
+                intrs = torch.einsum("ij,BVTjk->BVTik", rs, intrs)
+            if self.first and p.grid_size > 0:  # the reference's t = 0 support grid (:101-120), from the first pushed frame
+                height, width = rgbs.shape[-2:]
+                kinv, einv = p._invert(intrs[0, :, :1], extrs[0, :, :1])
+                pix = points_on_a_grid(p.grid_size, (height, width), device=dev)
+                rows = [p._support_rows(depths[0, v, 0, 0], pix, kinv[v, 0], einv[v, 0], 0) for v in range(V)]
+                self.session.add_queries(torch.cat(rows, 0)[None])
+            self.first = False
+            return self._result(self.session.push(rgbs, depths, intrs, extrs))
+
+    @torch.no_grad()
+    def finish(self):
+        res = self.session.finish()
+        if int(self.session.nan_flag.item()) != 0:  # (the deferred NaN guard, as at the end of ``forward``)
+            log.error("Got NaN values in coords, perhaps the training exploded")
+            self.p.last_nan = True
+        else:
+            self.p.last_nan = False
+        return self._result(res)

@@ -718,9 +718,11 @@ class MVTracker(nn.Module):
             hip.avgpool2(fv[lvl - 1][a:b], fv[lvl][a:b], (b - a) * V, h, w, self.latent_dim)
 
     @hip.guarded
-    def store_geometry(self, depths, intrs, extrs):
+    def store_geometry(self, depths, intrs, extrs, into=None):
         """The query-independent half of the frame store: world-space points of every pyramid level, tile boxes.  A handful of small
-        kernels; ``forward`` enqueues them BEFORE its one host sync (the query frames), so that the GPU has work while the host wakes up."""
+        kernels; ``forward`` enqueues them BEFORE its one host sync (the query frames), so that the GPU has work while the host wakes up.
+        ``into``: (store, first slot) -- the T frames go into slots [first, first + T) of that store's tensors (a block of a ring
+        store: the kernels are the same, on block views), nothing is allocated but the camera inverses."""
         V, T, _, H, W = depths.shape
         dev = depths.device
         hs, ws = H // self.stride, W // self.stride
@@ -733,11 +735,12 @@ class MVTracker(nn.Module):
         kinv = torch.empty(V * T, 9, device=dev)
         einv = torch.empty(V * T, 12, device=dev)
         hip.invert_cameras(intrs.reshape(V * T, 9), extrs.reshape(V * T, 12), kinv, einv, V * T)
-        ds = torch.empty(T, V, hs, ws, device=dev)
+        slots = None if into is None else slice(into[1], into[1] + T)
+        ds = torch.empty(T, V, hs, ws, device=dev) if into is None else into[0]["depth_s"][slots]
         hip.depth_subsample(depths.reshape(V, T, H, W), ds, V, T, H, W, self.stride)
         xyz = []
         for lvl in range(self.corr_n_levels):
-            o = torch.empty(T, V, hs >> lvl, ws >> lvl, 4, device=dev)
+            o = torch.empty(T, V, hs >> lvl, ws >> lvl, 4, device=dev) if into is None else into[0]["xyz"][lvl][slots]
             hip.unproject(ds, kinv, einv, o, V, T, hs, ws, self.stride, lvl)
             xyz.append(o)
         P = [V * (hs >> lvl) * (ws >> lvl) for lvl in range(self.corr_n_levels)]
@@ -748,15 +751,17 @@ class MVTracker(nn.Module):
             h, w = hs >> lvl, ws >> lvl
             g = (w, h) if (w % 8 == 0 and h % 8 == 0) else (0, 0)
             nt = (P[lvl] + 63) // 64
-            b = torch.empty(T, nt, 8, device=dev)
+            b = torch.empty(T, nt, 8, device=dev) if into is None else into[0]["box"][lvl][slots]
             hip.tile_aabb(xyz[lvl], P[lvl], T, b, g)
             gb = None
             if nt > 64:
-                gb = torch.empty(T, (nt + 63) // 64, 8, device=dev)
+                gb = torch.empty(T, (nt + 63) // 64, 8, device=dev) if into is None else into[0]["gbox"][lvl][slots]
                 hip.tile_group_aabb(b, P[lvl], T, gb)
             box.append(b)
             tgrid.append(g)
             gbox.append(gb)
+        if into is not None:
+            return into[0]
         geo = {"xyz": xyz, "P": P, "T": T, "depth_s": ds, "box": box, "tile_grid": tgrid, "gbox": gbox}
         if dev.type == "cuda":
             geo["geo_event"] = torch.cuda.Event()
@@ -1087,7 +1092,12 @@ class MVTracker(nn.Module):
         dev = coords.device
         pk = self._pack(dev)
         D = self.updateformer_input_dim
-        T = store["T"]
+        # a ring store (streaming) is read through the ring forms of the same entries: ``T`` is then its (base, R, lo, hi)
+        ring = store.get("ring")
+        T = store["T"] if ring is None else ring
+        knn_search_levels, corr_gather_dot, corr_gather_dot_opts = (
+            (hip.knn_search_levels, hip.corr_gather_dot, hip.corr_gather_dot_opts) if ring is None else
+            (hip.knn_search_levels_ring, hip.corr_gather_dot_ring, hip.corr_gather_dot_opts_ring))
         Fc = L * K * self.corr_width
         default_corr = self.corr_n_groups == 1 and self.corr_add_neighbor_offset and not self.corr_add_neighbor_xyz
         pos = torch.empty(n, D, device=dev)
@@ -1111,7 +1121,7 @@ class MVTracker(nn.Module):
         for it in range(iters):
             if it > 0:
                 # every level is seeded by its own previous neighbours: the four scans are independent -> one launch
-                hip.knn_search_levels(levels, coords, n, S, frame0, frame_step, T, K, seed_k=K)
+                knn_search_levels(levels, coords, n, S, frame0, frame_step, T, K, seed_k=K)
             else:
                 n0 = 0
                 if carry is not None and carry[1] > 0 and self.seed_across_windows:
@@ -1127,7 +1137,7 @@ class MVTracker(nn.Module):
                         slot = self._slot_cache[(S, dev)] = torch.tensor([min(s_ + S // 2, S - 1) for s_ in range(S)], device=dev)
                     seed_t = prev_idx[:, :n0].index_select(2, slot).contiguous()
                     lv0 = [dict(lv, seed_idx=seed_t[l_], idx_out=idx[l_][:n0]) for l_, lv in enumerate(levels)]
-                    hip.knn_search_levels(lv0, coords, n0, S, frame0, frame_step, T, K, seed_k=K)
+                    knn_search_levels(lv0, coords, n0, S, frame0, frame_step, T, K, seed_k=K)
                 # rows [n1, n) were searched ahead of time (``pre_idx``: the tracks that enter at this window, i.e. everything behind the
                 # carried ones); rows [n0, n1) still need their first, unseeded search -- empty unless the carried tracks were not seeded
                 # from the previous window (``seed_across_windows`` off)
@@ -1136,14 +1146,14 @@ class MVTracker(nn.Module):
                     # new tracks: all four levels in ONE unseeded launch (every search starts from the farthest-corner bound of the
                     # nearest full tile) -- 262 us against four dependent coarse-to-fine launches of ~100 us each
                     lv1 = [dict(lv, seed_idx=None, idx_out=idx[l_][n0:n1]) for l_, lv in enumerate(levels)]
-                    hip.knn_search_levels(lv1, coords[n0:n1], n1 - n0, S, frame0, frame_step, T, K, seed_k=0)
+                    knn_search_levels(lv1, coords[n0:n1], n1 - n0, S, frame0, frame_step, T, K, seed_k=0)
             if default_corr:
-                hip.corr_gather_dot(store["xyz"], store["fvec"], store["P"], [idx[lvl] for lvl in range(L)], C, ffeats, coords, n, S, frame0,
-                                    frame_step, T, K, fcorr, Fc, 0)
+                corr_gather_dot(store["xyz"], store["fvec"], store["P"], [idx[lvl] for lvl in range(L)], C, ffeats, coords, n, S, frame0,
+                                frame_step, T, K, fcorr, Fc, 0)
             else:  # the reference's non-default correlation layouts (grouped dots, no offsets, neighbour coordinates)
-                hip.corr_gather_dot_opts(store["xyz"], store["fvec"], store["P"], [idx[lvl] for lvl in range(L)], C, ffeats, coords, n, S,
-                                         frame0, frame_step, T, K, self.corr_n_groups, self.corr_add_neighbor_offset, self.corr_add_neighbor_xyz,
-                                         fcorr, Fc, 0)
+                corr_gather_dot_opts(store["xyz"], store["fvec"], store["P"], [idx[lvl] for lvl in range(L)], C, ffeats, coords, n, S,
+                                     frame0, frame_step, T, K, self.corr_n_groups, self.corr_add_neighbor_offset, self.corr_add_neighbor_xyz,
+                                     fcorr, Fc, 0)
             if it == 0 and after_first_corr is not None:  # (forward: the later frame blocks' encoder starts on the second stream now)
                 after_first_corr()
             if (trace is None and "updater_struct" in pk and self.fuse_head and self.fuse_input and self.fuse_tokens
@@ -1215,8 +1225,12 @@ class MVTracker(nn.Module):
         for a, b in zip(cuts[:-1], cuts[1:]):
             t = int(frames[a])
             keys = torch.empty((b - a) * ns, device=qxyz.device, dtype=torch.int64)
-            hip.knn_scan(store["xyz"][0], P0, qxyz[a:b], b - a, 1, t, 0, store["T"], 1, ns, keys, box=store["box"][0],
-                         grid=store["tile_grid"][0])
+            if store.get("ring") is None:
+                hip.knn_scan(store["xyz"][0], P0, qxyz[a:b], b - a, 1, t, 0, store["T"], 1, ns, keys, box=store["box"][0],
+                             grid=store["tile_grid"][0])
+            else:
+                hip.knn_scan_ring(store["xyz"][0], P0, qxyz[a:b], b - a, 1, t, 0, store["ring"], 1, ns, keys, box=store["box"][0],
+                                  grid=store["tile_grid"][0])
             if keys_for is not None:
                 keys.record_stream(keys_for)
             yield a, b, t, keys
@@ -1226,7 +1240,10 @@ class MVTracker(nn.Module):
         P0 = store["P"][0]
         ns = self._nseg(P0, 1)
         for a, b, t, keys in groups:
-            hip.knn1_gather(store["fvec"][0], P0, self.latent_dim, keys, b - a, ns, t, feat[a:b])
+            if store.get("ring") is None:
+                hip.knn1_gather(store["fvec"][0], P0, self.latent_dim, keys, b - a, ns, t, feat[a:b])
+            else:
+                hip.knn1_gather_ring(store["fvec"][0], P0, self.latent_dim, keys, b - a, ns, t, store["ring"], feat[a:b])
 
     def _feat_init(self, store, frames, qxyz, a0, a1, feat):
         self._feat_init_gather(store, self._feat_init_scan(store, frames, qxyz, a0, a1), feat)
@@ -1304,22 +1321,28 @@ class MVTracker(nn.Module):
         return store, pending, pending_back, start_side_encoder
 
     def _run_windows(self, store, windows, frame0s, frame_step, prepare, rows, store_out, unsort, out, iters, trace,
-                     enter_frames=None, pre=None, pending=(), after_first_corr=None):
+                     enter_frames=None, pre=None, pending=(), after_first_corr=None, carry=None, T=None):
         """One pass of the reference's window loop (mvtracker.py:537-695) over ``windows`` = [(start, active prefix), ...], slot s
         of window i reading store frame clamp(frame0s[i] + s * frame_step, 0, T-1).  ``prepare`` / ``store_out``: the library's
         window-state and result-store entry of the pass, ``rows`` = (query xyz, query frames, initial feature rows) in the pass's
         sorted order on the device, ``unsort`` = what ``store_out`` takes to put window rows back into the caller's.  ``out``: the
         call's result tensors.  Forward pass only: ``enter_frames`` (host query frames: the feature rows of the tracks that enter
         a window are initialised there), ``pre`` (``_presearch``), ``pending`` ((first frame, event) of the feature blocks in
-        flight on the second stream, in frame order), ``after_first_corr`` (``_refine``, first window).  Returns the windows run."""
+        flight on the second stream, in frame order), ``after_first_corr`` (``_refine``, first window).  Returns the windows run.
+        Streaming (``mvtracker_amd.streaming``) runs the loop a few windows at a time: ``carry`` is a dict that holds what one window
+        hands to the next (p0, coords, vis, prev_idx, w) between calls, ``T`` the clip length as far as it is known (``out`` then only
+        needs the NaN flag), and with ``store_out`` None the session stores the carried window's slots itself."""
         S, C = self.S, self.latent_dim
         qxyz, qt_d, feat = rows
         dev = qxyz.device
-        T, N = out["traj"].shape[:2]
+        if T is None:
+            T = out["traj"].shape[0]
         pre = {} if pre is None else pre
         done = []
         p0 = 0
         coords = vis = prev_idx = None
+        if carry:
+            p0, coords, vis, prev_idx = carry["p0"], carry["coords"], carry["vis"], carry["prev_idx"]
         for (w, p1), f0 in zip(windows, frame0s):  # mvtracker.py:537; p1 = number of queries with t < w+S (:538-540)
             assert p1 > 0
             while pending and pending[0][0] < w + S:  # the frames this window reads must have left the encoder
@@ -1350,9 +1373,12 @@ class MVTracker(nn.Module):
             after_first_corr = None
             coords = preds[-1]
             # :692-693, un-sorted (:710-711); the reversed pass writes only frames before each row's query frame
-            store_out(coords, vis, *unsort, p1, S, w, T, N, out["traj"], out["vis_logit"], out["vis_prob"])
+            if store_out is not None:
+                store_out(coords, vis, *unsort, p1, S, w, T, out["traj"].shape[1], out["traj"], out["vis_logit"], out["vis_prob"])
             done.append((w, p1))
             p0 = p1
+            if carry is not None:
+                carry.update(p0=p0, coords=coords, vis=vis, prev_idx=prev_idx, w=w)
         return done
 
     @torch.no_grad()
@@ -1581,6 +1607,18 @@ class MVTracker(nn.Module):
                 "vis_e": vis_prob[None, :, b0:b1],
             })
         return results
+
+    def open_stream(self, query_points, iters=4, ring_blocks=3, backward_tracking=False):
+        """Streaming session (``mvtracker_amd.streaming.StreamSession``): push frame blocks as they arrive, get
+        the tracks of the frames that became final, from a ring frame store whose size does not depend on the clip length.  The
+        concatenated emissions are the bits of ``forward`` on the whole clip.  ``query_points`` (1,N,4), N >= 1."""
+        from .streaming import StreamSession
+        if backward_tracking:
+            raise NotImplementedError("there is no streaming form of backward_tracking: the time-reversed pass starts at the clip's last "
+                                      "frame and is inherently offline (call forward(..., backward_tracking=True) on the whole clip)")
+        if isinstance(query_points, (list, tuple)):
+            raise NotImplementedError("there is no streaming form of forward_grouped: open one session per query set")
+        return StreamSession(self, query_points, iters=iters, ring_blocks=ring_blocks)
 
     def check_finite(self):
         """Deferred NaN guard (reference mvtracker.py:401-404): raises if the last forward produced NaN tracks."""
