@@ -7,6 +7,7 @@ its remote pieces (torch.hub / HuggingFace downloads, Rerun logging, depth estim
 
 Mirrors reference demo.py: sample layout :650, 922-929; temporal / spatial subsampling :905-944 (``--temporal_stride``,
 ``--spatial_downsample``); ``--random_query_points`` :967-993 (512 queries drawn from the depth of frame 0 inside a cylinder);
+``--sample-queries`` = the evaluator's sampling for unlabelled clips (evaluation/evaluator_3dpt.py:286-388, on the device);
 the predictor call :1004-1010 (bf16 = the demo's autocast arithmetic); the result file :1086-1121.  The wall time of the predictor
 call is reported with the evaluator's convention (frames / second, evaluation/evaluator_3dpt.py:496-523)."""
 import argparse
@@ -23,23 +24,11 @@ sys.path.insert(0, ROOT)
 
 def random_queries(depths, intrs, extrs, num_queries=512, t0=0, xy_radius=12.0, z_min=-1.0, z_max=10.0, seed=0):
     """demo.py:967-993: unproject every pixel of frame t0 (all views), keep the points inside the cylinder, draw num_queries."""
-    from mvtracker_amd import hip
-    _, V, T, _, H, W = depths.shape
-    dev = depths.device
-    kinv = torch.empty(V * T, 9, device=dev)
-    einv = torch.empty(V * T, 12, device=dev)
-    hip.invert_cameras(intrs[0].reshape(V * T, 9).contiguous(), extrs[0].reshape(V * T, 12).contiguous(), kinv, einv, V * T)
-    ds = depths[0, :, :, 0].permute(1, 0, 2, 3).contiguous()  # (T,V,H,W): the frame store's depth layout at stride 1
-    xyz = torch.empty(T, V, H, W, 4, device=dev)
-    hip.unproject(ds, kinv, einv, xyz, V, T, H, W, 1, 0)
-    pts = xyz[t0].reshape(-1, 4)[:, :3]
-    r2 = pts[:, 0] ** 2 + pts[:, 1] ** 2
-    pool = pts[(r2 <= xy_radius ** 2) & (pts[:, 2] >= z_min) & (pts[:, 2] <= z_max) & (ds[t0].reshape(-1) > 0)]
-    assert pool.shape[0] > 0, "cylinder mask removed all points; increase the radius or the z range"
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    idx = torch.randperm(pool.shape[0], generator=g)[:num_queries].to(dev)
-    q = pool[idx]
-    return torch.cat([torch.full((q.shape[0], 1), float(t0), device=dev), q], 1)[None]
+    from mvtracker_amd.queries import sample_queries
+    try:  # demo.py's rule: valid depth (no confidence map), x^2 + y^2 <= r^2
+        return sample_queries(depths, intrs, extrs, [(t0, z_min, z_max, xy_radius, num_queries, "")], seed=seed, radius_inclusive=True)
+    except ValueError:
+        raise AssertionError("cylinder mask removed all points; increase the radius or the z range") from None
 
 
 def main():
@@ -52,6 +41,12 @@ def main():
     ap.add_argument("--temporal_stride", type=int, default=1)
     ap.add_argument("--spatial_downsample", type=int, default=1)
     ap.add_argument("--random_query_points", action="store_true")
+    ap.add_argument("--sample-queries", choices=["random", "kmeans"], default=None,
+                    help="sample the queries from the depth of frame 0 like the reference's evaluator does for unlabelled clips "
+                         "(mvtracker_amd.sample_queries): a random draw or the k-means centres of the points inside --region")
+    ap.add_argument("--num-queries", type=int, default=1000, metavar="N", help="queries drawn by --sample-queries")
+    ap.add_argument("--region", type=float, nargs=3, default=(2.1, -0.1, 4.2), metavar=("R", "ZMIN", "ZMAX"),
+                    help="cylinder of --sample-queries around the z axis: radius and z range")
     ap.add_argument("--single_point", action="store_true")
     ap.add_argument("--grid-size", type=int, default=5)
     ap.add_argument("--n-iters", type=int, default=4)
@@ -91,7 +86,12 @@ def main():
             s["query_points_3d"][..., 0] = torch.floor(s["query_points_3d"][..., 0] / args.temporal_stride)
     else:
         s = sample_io.load_sample(args.sample_path, device=dev, temporal_stride=args.temporal_stride, spatial_downsample=args.spatial_downsample)
-    if args.random_query_points or s["query_points_3d"].shape[1] == 0:
+    if args.sample_queries is not None:
+        from mvtracker_amd import sample_queries
+        r, zmin, zmax = args.region
+        s["query_points_3d"] = sample_queries(s["depths"], s["intrs"], s["extrs"],
+                                              [(0, zmin, zmax, r, args.num_queries, "kmeans" if args.sample_queries == "kmeans" else "")])
+    elif args.random_query_points or s["query_points_3d"].shape[1] == 0:
         s["query_points_3d"] = random_queries(s["depths"].float(), s["intrs"], s["extrs"])
     V, T = s["rgbs"].shape[1:3]
     print(f"clip: {V} views x {T} frames x {tuple(s['rgbs'].shape[-2:])}, {s['query_points_3d'].shape[1]} queries, precision {args.precision}")

@@ -651,6 +651,66 @@ int mvt_update_head_bf16(const float* tok, int ldt, const unsigned short* w0, co
                          const unsigned short* wu, const float* bu, float* coords, float* ffeats, float* delta /* NULL or [rows][ldd] */,
                          int ldd, long long rows, int hidden, int out_dim, int* nan_flag, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Query sampling from depth for unlabelled clips (reference: evaluation/evaluator_3dpt.py:286-388,
+ * kmeans_sample :42-59).  Every sum taken across lanes or workgroups is an integer (fixed point):
+ * the results do not depend on the order of addition.  No kernel waits on another workgroup.
+ * --------------------------------------------------------------------------------------------- */
+#define MVT_POOL_RADIUS_INCLUSIVE 1 /* x^2 + y^2 <= radius^2 (demo.py:980) instead of the evaluator's < */
+/* Candidate pool of frame t: every pixel of depths (V,T,1,H,W) at frame t (read in place), unprojected with mvt_unproject's
+ * arithmetic at stride 1 (kinv / einv [V*T] from mvt_invert_cameras), kept when it is valid -- conf > conf_threshold with a
+ * confidence map (same layout), depth > 0 without one (conf = NULL) -- and inside the cylinder (x-x0)^2 + (y-y0)^2 < radius_sq
+ * (squares and sum rounded separately, as torch does), z_min <= z <= z_max; radius_sq / z_min / z_max may be infinite.
+ * pool [V*H*W][3] receives the kept points in raster order (view, row, column = init_pointcloud_from_rgbd's order), *count their
+ * number M; rows from M on are not written.  block_counts: workspace of ceil(V*H*W / 256) int32.  V*H*W < 2^31.
+ * Three launches: per-workgroup counts, a one-workgroup scan, a scatter at wave-ballot prefix positions. */
+int mvt_query_pool(const float* depths, const float* conf, const float* kinv, const float* einv, int V, int T, int t, int H, int W,
+                   float conf_threshold, float x0, float y0, float radius_sq, float z_min, float z_max, int flags, float* pool,
+                   int* count, int* block_counts, void* stream);
+
+/* k-means over pts [M][3], 1 <= k <= MVT_KMEANS_MAX_K, k <= M < 2^31 (anything else: MVT_ERR_ARG before any launch).
+ * state: MVT_KM_WORDS 64-bit words on the device, doubles and integers as named below. */
+#define MVT_KMEANS_MAX_K 4096
+#define MVT_KMEANS_MAX_CAND 10       /* 2 + floor(ln 4096) candidates per seeding step */
+#define MVT_KMEANS_SEED_BLOCKS 4096  /* workgroups of a seeding pass (their prefix lives in LDS) */
+#define MVT_KMEANS_STAT_BLOCKS 1024
+#define MVT_KM_LO 0           /* 3 doubles: bounding-box minimum */
+#define MVT_KM_HI 3           /* 3 doubles: bounding-box maximum */
+#define MVT_KM_SCALE 6        /* double, a power of two: fixed-point units per coordinate unit */
+#define MVT_KM_SCALE2 7       /* double, a power of two: fixed-point units per squared-distance unit */
+#define MVT_KM_TOL 8          /* double: tol * mean per-coordinate variance (sklearn's stopping threshold) */
+#define MVT_KM_ITER 9         /* int64: Lloyd iterations done */
+#define MVT_KM_CONVERGED 10   /* int64 flag */
+#define MVT_KM_EMPTY 11       /* int64: empty clusters of the last assignment */
+#define MVT_KM_INERTIA 12     /* double: inertia of the last assignment */
+#define MVT_KM_INERTIA_ACC 13 /* uint64: running fixed-point inertia */
+#define MVT_KM_SHIFT 14       /* double: sum of squared centre shifts of the last update */
+#define MVT_KM_POT 15         /* uint64: fixed-point potential after the last seeding step */
+#define MVT_KM_CAND 16        /* MVT_KMEANS_MAX_CAND int64: candidate point indices of the running seeding step */
+#define MVT_KM_WORDS 32
+/* Bounding box, fixed-point scales (a value gets min(2^40, 2^62 / M) levels: M of them sum below 2^63), the stopping threshold,
+ * and the counters of a fresh run.  partial: workspace of MVT_KMEANS_STAT_BLOCKS * 6 doubles. */
+int mvt_kmeans_stats(const float* pts, long long M, float tol, double* partial, long long* state, void* stream);
+/* Greedy k-means++ (sklearn _kmeans_plusplus): the first centre uniform, then per centre 2 + floor(ln k) candidates drawn with
+ * probability proportional to the squared distance to the nearest centre so far, the one that lowers the potential most kept.
+ * Draws are a hash of (seed, step, candidate).  Two launches per centre, no host read-back.  centres [k][3] out;
+ * min_d2: workspace [M] floats; partials: workspace of MVT_KMEANS_MAX_CAND * MVT_KMEANS_SEED_BLOCKS uint64.  Needs mvt_kmeans_stats. */
+int mvt_kmeans_seed(const float* pts, long long M, int k, long long seed, float* min_d2, void* partials, float* centres,
+                    long long* state, void* stream);
+/* Nearest centre of every point (direct dx^2 + dy^2 + dz^2 in fp32 against centres in LDS, ties to the lowest index) -> labels [M],
+ * and acc [k][4] uint64 += (fixed-point coordinate sums, count); the inertia in fp64 per point, summed in fixed point.  acc must
+ * be zero on entry (mvt_kmeans_update leaves it so).  Returns at once when the state says converged or max_iter iterations are
+ * done, unless final_pass. */
+int mvt_kmeans_assign(const float* pts, long long M, const float* centres, int k, int* labels, void* acc, long long* state,
+                      int max_iter, int final_pass, void* stream);
+/* centre = lo + sum / (count * scale) in fp64, stored as fp32 (an empty cluster keeps its centre), acc cleared, iteration
+ * counted, converged when the sum of squared shifts <= the threshold.  final_pass: only report inertia and empty clusters of the
+ * assignment in acc (centres, acc and the counters stay). */
+int mvt_kmeans_update(float* centres, int k, void* acc, long long* state, int max_iter, int final_pass, void* stream);
+/* n_iters <= 64 times (assign, update) in one call; iterations after convergence or max_iter are empty launches. */
+int mvt_kmeans_iterate(const float* pts, long long M, float* centres, int k, int* labels, void* acc, long long* state, int n_iters,
+                       int max_iter, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

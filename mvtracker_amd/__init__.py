@@ -1,11 +1,12 @@
 """MI355X-native multi-view point-tracking forward path (drop-in for mvtracker.models' predictor).
 
-    from mvtracker_amd import MVTracker, EvaluationPredictor, load_mvtracker
+    from mvtracker_amd import MVTracker, EvaluationPredictor, load_mvtracker, sample_queries
 
 ``synth`` (numpy only) can be imported without the HIP library; everything else loads
 libmvtracker_hip.so on import and raises if it is missing -- there is no CPU fallback.
 """
-__all__ = ["MVTracker", "EvaluationPredictor", "load_mvtracker", "hip", "synth", "sample_io", "adapter", "geometry", "parallel"]
+__all__ = ["MVTracker", "EvaluationPredictor", "load_mvtracker", "hip", "synth", "sample_io", "adapter", "geometry", "parallel", "queries",
+           "sample_queries", "kmeans_centres", "DEFAULT_SPEC"]
 
 
 def __getattr__(name):
@@ -18,7 +19,10 @@ def __getattr__(name):
     if name == "load_mvtracker":
         from .factory import load_mvtracker
         return load_mvtracker
-    if name in ("hip", "synth", "sample_io", "adapter", "geometry", "parallel"):
+    if name in ("sample_queries", "kmeans_centres", "DEFAULT_SPEC"):
+        from . import queries
+        return getattr(queries, name)
+    if name in ("hip", "synth", "sample_io", "adapter", "geometry", "parallel", "queries"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

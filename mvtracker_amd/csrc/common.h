@@ -42,6 +42,22 @@ __device__ __forceinline__ float mvt_act(float x, int act) {
   }
 }
 
+// World-space point of cell (x, y) of a pixel grid of step st (pixel centre (i + 0.5) * st - 0.5, model_utils.py:462-466) at depth d:
+// K^-1 (kinv, 9 floats) to the camera ray, times d, then rows 0..2 of [R|t]^-1 (einv, 12 floats).  The one statement of the
+// unprojection arithmetic: mvt_unproject (pyramid.hip) and mvt_query_pool (query_sample.hip) both call it.
+__device__ __forceinline__ f32x4 mvt_unproject_point(const float* __restrict__ K, const float* __restrict__ E, int x, int y, float st, float d) {
+  float px = ((float)x + 0.5f) * st - 0.5f, py = ((float)y + 0.5f) * st - 0.5f;
+  float cx = (K[0] * px + K[1] * py + K[2]) * d;
+  float cy = (K[3] * px + K[4] * py + K[5]) * d;
+  float cz = (K[6] * px + K[7] * py + K[8]) * d;
+  f32x4 o;
+  o[0] = E[0] * cx + E[1] * cy + E[2] * cz + E[3];
+  o[1] = E[4] * cx + E[5] * cy + E[6] * cz + E[7];
+  o[2] = E[8] * cx + E[9] * cy + E[10] * cz + E[11];
+  o[3] = 0.f;
+  return o;
+}
+
 // Activation tensors of the encoder are fp32 or, in bf16 mode, bf16 (MVT_IO_* flags).  Element offsets, fp32 values.
 // Plain cast (v_cvt_pk_bf16_f32, round to nearest even): a NaN stays a NaN.  Rounding by integer arithmetic on the f32 bits
 // turns some NaNs into 0 / inf (MI355X_MICROARCH.md, bf16 conversion pitfall), which would launder a NaN born in the bf16

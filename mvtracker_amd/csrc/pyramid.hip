@@ -86,17 +86,7 @@ __global__ void unproject_kernel(const float* __restrict__ depth_s, const float*
     long long tv = r / h;
     int t = (int)(tv / V), v = (int)(tv - (long long)t * V);
     float d = depth_s[(tv * hs + (long long)y * f) * ws + (long long)x * f];
-    float px = ((float)x + 0.5f) * st - 0.5f, py = ((float)y + 0.5f) * st - 0.5f;
-    const float* K = kinv + ((long long)v * T + t) * 9;
-    const float* E = einv + ((long long)v * T + t) * 12;
-    float cx = (K[0] * px + K[1] * py + K[2]) * d;
-    float cy = (K[3] * px + K[4] * py + K[5]) * d;
-    float cz = (K[6] * px + K[7] * py + K[8]) * d;
-    f32x4 o;
-    o[0] = E[0] * cx + E[1] * cy + E[2] * cz + E[3];
-    o[1] = E[4] * cx + E[5] * cy + E[6] * cz + E[7];
-    o[2] = E[8] * cx + E[9] * cy + E[10] * cz + E[11];
-    o[3] = 0.f;
+    const f32x4 o = mvt_unproject_point(kinv + ((long long)v * T + t) * 9, einv + ((long long)v * T + t) * 12, x, y, st, d);
     *reinterpret_cast<f32x4*>(xyz + i * 4) = o;
   }
 }

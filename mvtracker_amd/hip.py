@@ -106,6 +106,12 @@ SIGNATURES = {
     "mvt_updateformer_forward_tokens": [P, P, I, P, I, P, P, P, P, LL, P],
     "mvt_token_input_proj_bf16": [P, P, I, P, I, P, P, P, I, I, I, P, P, P, P, I, P, I, LL, I, P],
     "mvt_update_head_bf16": [P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, LL, I, I, P, P],
+    "mvt_query_pool": [P, P, P, P, I, I, I, I, I, F, F, F, F, F, F, I, P, P, P, P],
+    "mvt_kmeans_stats": [P, LL, F, P, P, P],
+    "mvt_kmeans_seed": [P, LL, I, LL, P, P, P, P, P],
+    "mvt_kmeans_assign": [P, LL, P, I, P, P, P, I, I, P],
+    "mvt_kmeans_update": [P, I, P, P, I, I, P],
+    "mvt_kmeans_iterate": [P, LL, P, I, P, P, P, I, I, P],
 }
 _RET = {"mvt_build_arch": C.c_char_p, "mvt_encoder_workspace_bytes": C.c_longlong, "mvt_updateformer_workspace_bytes": C.c_longlong,
         "mvt_updateformer_grouped_workspace_bytes": C.c_longlong}
@@ -797,3 +803,63 @@ def updateformer_forward_tokens_grouped(weights: UpdaterWeights, coords, fcorr, 
                      Fc, Cf, E)
     _call("mvt_updateformer_forward_tokens_grouped", C.addressof(weights), C.addressof(ti), sum(group_n), *_group_n(group_n), _ptr(delta), ldd,
           _ptr(upd_coords), _ptr(upd_ffeats), _ptr(nan_flag), _ptr(workspace), workspace.numel(), _stream())
+
+
+# ------------------------------------------------------------------ query sampling (mvtracker_amd/queries.py drives these)
+POOL_RADIUS_INCLUSIVE = 1  # MVT_POOL_RADIUS_INCLUSIVE
+KMEANS_MAX_K, KMEANS_MAX_CAND, KMEANS_SEED_BLOCKS, KMEANS_STAT_BLOCKS = 4096, 10, 4096, 1024
+KM_LO, KM_HI, KM_SCALE, KM_SCALE2, KM_TOL, KM_ITER, KM_CONVERGED, KM_EMPTY, KM_INERTIA, KM_SHIFT, KM_POT, KM_WORDS = 0, 3, 6, 7, 8, 9, 10, 11, 12, 14, 15, 32
+
+
+def query_pool(depths, conf, kinv, einv, V, T, t, H, W, conf_threshold, x0, y0, radius_sq, z_min, z_max, pool, count, block_counts,
+               radius_inclusive=False):
+    """Candidate pool of frame t of the clip depths (V,T,1,H,W) [conf: the same layout or None] -> pool (V*H*W,3), count (1,) int32."""
+    assert depths.is_contiguous() and depths.dtype == torch.float32 and depths.numel() == V * T * H * W
+    assert conf is None or (conf.is_contiguous() and conf.dtype == torch.float32 and conf.numel() == V * T * H * W)
+    assert pool.dtype == torch.float32 and pool.numel() >= V * H * W * 3 and count.dtype == torch.int32
+    assert block_counts.dtype == torch.int32 and block_counts.numel() >= (V * H * W + 255) // 256
+    _call("mvt_query_pool", _ptr(depths), _ptr(conf), _ptr(_f32c(kinv)), _ptr(_f32c(einv)), V, T, t, H, W, conf_threshold, x0, y0, radius_sq,
+          z_min, z_max, POOL_RADIUS_INCLUSIVE if radius_inclusive else 0, _ptr(pool), _ptr(count), _ptr(block_counts), _stream())
+
+
+def _km_check(pts, M, state):
+    assert pts.dtype == torch.float32 and pts.is_contiguous() and pts.numel() == M * 3
+    assert state.dtype == torch.int64 and state.numel() >= KM_WORDS
+
+
+def kmeans_stats(pts, M, tol, partial, state):
+    _km_check(pts, M, state)
+    assert partial.dtype == torch.float64 and partial.numel() >= KMEANS_STAT_BLOCKS * 6
+    _call("mvt_kmeans_stats", _ptr(pts), M, tol, _ptr(partial), _ptr(state), _stream())
+
+
+def kmeans_seed(pts, M, k, seed, min_d2, partials, centres, state):
+    _km_check(pts, M, state)
+    assert min_d2.dtype == torch.float32 and min_d2.numel() >= M and centres.dtype == torch.float32 and centres.numel() >= k * 3
+    assert partials.dtype == torch.int64 and partials.numel() >= KMEANS_MAX_CAND * KMEANS_SEED_BLOCKS
+    _call("mvt_kmeans_seed", _ptr(pts), M, k, seed, _ptr(min_d2), _ptr(partials), _ptr(centres), _ptr(state), _stream())
+
+
+def _km_check_acc(centres, k, labels, M, acc):
+    assert centres.dtype == torch.float32 and centres.is_contiguous() and centres.numel() >= k * 3
+    assert labels is None or (labels.dtype == torch.int32 and labels.numel() >= M)
+    assert acc.dtype == torch.int64 and acc.numel() >= k * 4
+
+
+def kmeans_assign(pts, M, centres, k, labels, acc, state, max_iter=300, final_pass=False):
+    """labels (M,) int32 <- nearest centre; acc (k,4) int64 += fixed-point coordinate sums and counts (zero it before the first call)."""
+    _km_check(pts, M, state)
+    _km_check_acc(centres, k, labels, M, acc)
+    _call("mvt_kmeans_assign", _ptr(pts), M, _ptr(centres), k, _ptr(labels), _ptr(acc), _ptr(state), max_iter, int(final_pass), _stream())
+
+
+def kmeans_update(centres, k, acc, state, max_iter=300, final_pass=False):
+    _km_check_acc(centres, k, None, 0, acc)
+    assert state.dtype == torch.int64 and state.numel() >= KM_WORDS
+    _call("mvt_kmeans_update", _ptr(centres), k, _ptr(acc), _ptr(state), max_iter, int(final_pass), _stream())
+
+
+def kmeans_iterate(pts, M, centres, k, labels, acc, state, n_iters, max_iter):
+    _km_check(pts, M, state)
+    _km_check_acc(centres, k, labels, M, acc)
+    _call("mvt_kmeans_iterate", _ptr(pts), M, _ptr(centres), k, _ptr(labels), _ptr(acc), _ptr(state), n_iters, max_iter, _stream())

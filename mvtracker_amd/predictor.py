@@ -313,6 +313,15 @@ class EvaluationPredictor(torch.nn.Module):
             self.last_nan = False
         return {"traj_e": traj_e, "vis_e": vis_e > self.visibility_threshold, "vis_e_as_prob": vis_e}
 
+    @staticmethod
+    def sample_queries(depths, intrs, extrs, spec=None, **kw):
+        """Query points for a clip without labels (``mvtracker_amd.queries.sample_queries``; the evaluator's sampling,
+        evaluation/evaluator_3dpt.py:286-388): a (1, N, 4) tensor for ``forward(query_points_3d=...)``, ``open_stream(...)`` or a
+        session's ``add_queries(...)``.  The inputs are the clip as ``forward`` takes it; ``interp_shape`` plays no part (a nearest
+        resize with rescaled intrinsics keeps world points, and the queries are in world space)."""
+        from . import queries
+        return queries.sample_queries(depths, intrs, extrs, queries.DEFAULT_SPEC if spec is None else spec, **kw)
+
     def open_stream(self, query_points_3d, ring_blocks=3):
         """Streaming form of ``forward`` in joint mode (``MVTracker.open_stream``): returns a session whose
         ``push(rgbs, depths, intrs, extrs)`` / ``finish()`` give {"frames": (a, b), "traj_e", "vis_e", "vis_e_as_prob"} for the
