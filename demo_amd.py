@@ -8,6 +8,8 @@ its remote pieces (torch.hub / HuggingFace downloads, Rerun logging, depth estim
 Mirrors reference demo.py: sample layout :650, 922-929; temporal / spatial subsampling :905-944 (``--temporal_stride``,
 ``--spatial_downsample``); ``--random_query_points`` :967-993 (512 queries drawn from the depth of frame 0 inside a cylinder);
 ``--sample-queries`` = the evaluator's sampling for unlabelled clips (evaluation/evaluator_3dpt.py:286-388, on the device);
+``--normalize-scene auto`` = the dataset's scene normalisation for a user's own recording (datasets/generic_scene_dataset.py:288-358,
+on the device: queries are sampled and tracks saved in the recording's own world, the model sees the normalised scene);
 the predictor call :1004-1010 (bf16 = the demo's autocast arithmetic); the result file :1086-1121.  The wall time of the predictor
 call is reported with the evaluator's convention (frames / second, evaluation/evaluator_3dpt.py:496-523)."""
 import argparse
@@ -47,6 +49,12 @@ def main():
     ap.add_argument("--num-queries", type=int, default=1000, metavar="N", help="queries drawn by --sample-queries")
     ap.add_argument("--region", type=float, nargs=3, default=(2.1, -0.1, 4.2), metavar=("R", "ZMIN", "ZMAX"),
                     help="cylinder of --sample-queries around the z axis: radius and z range")
+    ap.add_argument("--normalize-scene", choices=["none", "auto"], default="none",
+                    help="auto: centre the scene, lift its floor to z = 0 and rescale it to the size the weights were trained on "
+                         "(mvtracker_amd.auto_scene_normalization on frame 0); tracks are saved in the clip's own world")
+    ap.add_argument("--target-radius", type=float, default=6.3, help="median camera distance after --normalize-scene auto")
+    ap.add_argument("--norm-conf-thresh", type=float, default=4.8,
+                    help="confidence above which a pixel counts for --normalize-scene auto (clips with a depths_conf entry only)")
     ap.add_argument("--single_point", action="store_true")
     ap.add_argument("--grid-size", type=int, default=5)
     ap.add_argument("--n-iters", type=int, default=4)
@@ -93,15 +101,22 @@ def main():
                                               [(0, zmin, zmax, r, args.num_queries, "kmeans" if args.sample_queries == "kmeans" else "")])
     elif args.random_query_points or s["query_points_3d"].shape[1] == 0:
         s["query_points_3d"] = random_queries(s["depths"].float(), s["intrs"], s["extrs"])
+    xf = None
+    if args.normalize_scene == "auto":  # (after the queries: sampling stays in the clip's own world)
+        from mvtracker_amd import auto_scene_normalization
+        xf = auto_scene_normalization(s["depths"], s["intrs"], s["extrs"], depths_conf=s.get("depths_conf"), conf_thresh=args.norm_conf_thresh,
+                                      target_radius=args.target_radius)
+        print(f"scene normalisation: scale {xf.scale:.4f}, translation {np.round(xf.translation, 4).tolist()}")
     V, T = s["rgbs"].shape[1:3]
     print(f"clip: {V} views x {T} frames x {tuple(s['rgbs'].shape[-2:])}, {s['query_points_3d'].shape[1]} queries, precision {args.precision}")
-    call = lambda: predictor(rgbs=s["rgbs"], depths=s["depths"], intrs=s["intrs"], extrs=s["extrs"], query_points_3d=s["query_points_3d"])
+    call = lambda: predictor(rgbs=s["rgbs"], depths=s["depths"], intrs=s["intrs"], extrs=s["extrs"], query_points_3d=s["query_points_3d"],
+                             scene_transform=xf)
     if args.streaming:
         if args.block_frames < 1:
             raise SystemExit("--block-frames must be at least 1")
 
         def call():
-            st = predictor.open_stream(s["query_points_3d"])
+            st = predictor.open_stream(s["query_points_3d"], scene_transform=xf)
             outs = [st.push(*(s[k][:, :, t:t + args.block_frames] for k in ("rgbs", "depths", "intrs", "extrs")))
                     for t in range(0, T, args.block_frames)]
             outs.append(st.finish())

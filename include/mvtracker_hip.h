@@ -711,6 +711,57 @@ int mvt_kmeans_update(float* centres, int k, void* acc, long long* state, int ma
 int mvt_kmeans_iterate(const float* pts, long long M, float* centres, int k, int* labels, void* acc, long long* state, int n_iters,
                        int max_iter, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Scene normalisation (reference: datasets/generic_scene_dataset.py:288-358 compute_auto_scene_normalization,
+ * datasets/utils.py:210-301 transform_scene).  Sums across workgroups are integers, or fp64 sums in an
+ * order fixed by the problem size: two runs give the same bits.  No kernel waits on another workgroup.
+ * --------------------------------------------------------------------------------------------- */
+#define MVT_SELECT_WS_WORDS 264 /* uint32 words of a select's workspace: 256 histogram bins, prefix, rank, two words of the successor */
+/* out[0] = the k-th smallest (0-based) of n fp32 values, the bits of np.sort(values)[k].  Radix select on the monotone uint32
+ * image of the float (sign bit set: all bits flipped; clear: the sign bit set), four passes of 8 bits: a digit histogram in LDS,
+ * integer adds into 256 global bins, then one workgroup picks the digit and the remaining rank -- no host read between passes.
+ * Order rule: the image's, so -0.0 < +0.0 (numpy calls them equal and may place them either way) and NaNs sort by their bits;
+ * callers refuse NaN.  1 <= n < 2^31, 0 <= k < n, else MVT_ERR_ARG before any launch.  workspace: MVT_SELECT_WS_WORDS uint32. */
+int mvt_select_kth(const float* values, long long n, long long k, float* out, void* workspace, void* stream);
+
+#define MVT_SCENE_BLOCKS 1024 /* workgroups of the passes that leave per-workgroup fp64 partial sums */
+/* state of mvt_scene_stats: MVT_SN_WORDS 64-bit words on the device */
+#define MVT_SN_M 0           /* int64: points kept */
+#define MVT_SN_CENTROID 1    /* 3 doubles */
+#define MVT_SN_Z_QUANTILE 4  /* double: the q_floor quantile of z */
+#define MVT_SN_FLOOR 5       /* double: that quantile - centroid z (the reference's quantile of the centred z, up to rounding) */
+#define MVT_SN_Z_LO 6        /* double: order statistic Z_RANK of z */
+#define MVT_SN_Z_HI 7        /* double: order statistic Z_RANK + 1 (Z_LO again when there is none) */
+#define MVT_SN_Z_RANK 8      /* int64: floor(q_floor * (M - 1)), the product rounded to fp32 as torch.quantile does for a float32 tensor */
+#define MVT_SN_R_QUANTILE 9  /* double: the q_radius quantile of |p - centroid - (0, 0, floor)| */
+#define MVT_SN_R_LO 10
+#define MVT_SN_R_HI 11
+#define MVT_SN_R_RANK 12
+#define MVT_SN_NONFINITE 13  /* int64: valid pixels whose depth is not finite */
+#define MVT_SN_Z_WEIGHT 14   /* double: the rank's fraction, the interpolation weight between LO and HI */
+#define MVT_SN_R_WEIGHT 15
+#define MVT_SN_WORDS 16
+/* Pool statistics of frame t of depths (V,T,1,H,W) [conf: the same layout or NULL], both read in place.  A pixel is valid when
+ * conf > conf_thresh && depth > 0 (conf = NULL: depth > 0); a view with fewer than min_points valid pixels is left out whole; the
+ * rest is unprojected with mvt_unproject's arithmetic at stride 1 (kinv / einv [V*T] from mvt_invert_cameras).  state receives the
+ * kept count M, the centroid (fp64 sums in a fixed order), the q_floor quantile of z and, when q_radius >= 0, the q_radius
+ * quantile of the centred-and-lifted points' norms (each norm in fp64, rounded to fp32 once); quantiles are torch.quantile's
+ * default: linear interpolation between two exact order statistics (radix select, as mvt_select_kth).  M = 0 leaves the
+ * quantiles meaningless.  Workspaces: keys V*H*W uint32, partial MVT_SCENE_BLOCKS * 3 doubles, iws MVT_SELECT_WS_WORDS + V int32.
+ * V*H*W < 2^31.  14 launches, 25 with the radius quantile; no host read. */
+int mvt_scene_stats(const float* depths, const float* conf, const float* kinv, const float* einv, int V, int T, int t, int H, int W,
+                    float conf_thresh, int min_points, float q_floor, float q_radius, unsigned int* keys, double* partial, int* iws,
+                    long long* state, void* stream);
+
+/* The similarity transform X' = t + R (s X) of transform_scene.  xf: 13 doubles on the HOST (s, R row-major, t), s finite and
+ * positive.  Any of the three parts may be absent (count 0).  depths_out [n_depth] = depths * s; extrs_out [n_extr][3][4] =
+ * [Re | s te] [R^T | -R^T t; 0 1] (the rigid inverse in closed form); queries_out [n_query][4] = (t, t + R (s xyz)).  All
+ * arithmetic in fp64, rounded to fp32 once; out of place (in == out is allowed). */
+int mvt_scene_apply(const float* depths, float* depths_out, long long n_depth, const float* extrs, float* extrs_out, int n_extr,
+                    const float* queries, float* queries_out, long long n_query, const double* xf, void* stream);
+/* The same map on rows of three floats (track points); with the inverse's parameters (1/s, R^T, -R^T t / s) it undoes it. */
+int mvt_scene_tracks(const float* tracks, float* out, long long n_rows, const double* xf, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

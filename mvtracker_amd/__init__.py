@@ -1,12 +1,12 @@
 """MI355X-native multi-view point-tracking forward path (drop-in for mvtracker.models' predictor).
 
-    from mvtracker_amd import MVTracker, EvaluationPredictor, load_mvtracker, sample_queries
+    from mvtracker_amd import MVTracker, EvaluationPredictor, load_mvtracker, sample_queries, auto_scene_normalization
 
 ``synth`` (numpy only) can be imported without the HIP library; everything else loads
 libmvtracker_hip.so on import and raises if it is missing -- there is no CPU fallback.
 """
 __all__ = ["MVTracker", "EvaluationPredictor", "load_mvtracker", "hip", "synth", "sample_io", "adapter", "geometry", "parallel", "queries",
-           "sample_queries", "kmeans_centres", "DEFAULT_SPEC"]
+           "sample_queries", "kmeans_centres", "DEFAULT_SPEC", "scene", "SceneTransform", "auto_scene_normalization"]
 
 
 def __getattr__(name):
@@ -22,7 +22,10 @@ def __getattr__(name):
     if name in ("sample_queries", "kmeans_centres", "DEFAULT_SPEC"):
         from . import queries
         return getattr(queries, name)
-    if name in ("hip", "synth", "sample_io", "adapter", "geometry", "parallel", "queries"):
+    if name in ("SceneTransform", "auto_scene_normalization"):
+        from . import scene
+        return getattr(scene, name)
+    if name in ("hip", "synth", "sample_io", "adapter", "geometry", "parallel", "queries", "scene"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

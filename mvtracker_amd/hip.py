@@ -112,6 +112,10 @@ SIGNATURES = {
     "mvt_kmeans_assign": [P, LL, P, I, P, P, P, I, I, P],
     "mvt_kmeans_update": [P, I, P, P, I, I, P],
     "mvt_kmeans_iterate": [P, LL, P, I, P, P, P, I, I, P],
+    "mvt_select_kth": [P, LL, LL, P, P, P],
+    "mvt_scene_stats": [P, P, P, P, I, I, I, I, I, F, I, F, F, P, P, P, P, P],
+    "mvt_scene_apply": [P, P, LL, P, P, I, P, P, LL, P, P],
+    "mvt_scene_tracks": [P, P, LL, P, P],
 }
 _RET = {"mvt_build_arch": C.c_char_p, "mvt_encoder_workspace_bytes": C.c_longlong, "mvt_updateformer_workspace_bytes": C.c_longlong,
         "mvt_updateformer_grouped_workspace_bytes": C.c_longlong}
@@ -863,3 +867,55 @@ def kmeans_iterate(pts, M, centres, k, labels, acc, state, n_iters, max_iter):
     _km_check(pts, M, state)
     _km_check_acc(centres, k, labels, M, acc)
     _call("mvt_kmeans_iterate", _ptr(pts), M, _ptr(centres), k, _ptr(labels), _ptr(acc), _ptr(state), n_iters, max_iter, _stream())
+
+
+# ------------------------------------------------------------------ scene normalisation (mvtracker_amd/scene.py drives these)
+SELECT_WS_WORDS, SCENE_BLOCKS = 264, 1024  # MVT_SELECT_WS_WORDS, MVT_SCENE_BLOCKS
+(SN_M, SN_CENTROID, SN_Z_QUANTILE, SN_FLOOR, SN_Z_LO, SN_Z_HI, SN_Z_RANK, SN_R_QUANTILE, SN_R_LO, SN_R_HI, SN_R_RANK, SN_NONFINITE,
+ SN_Z_WEIGHT, SN_R_WEIGHT, SN_WORDS) = 0, 1, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16
+
+
+def select_kth(values, n, k, out, workspace):
+    """out[0] <- the k-th smallest (0-based) of the first n fp32 values, exactly (radix select; the caller refuses NaN)."""
+    assert values.dtype == torch.float32 and values.is_contiguous() and values.numel() >= n
+    assert out.dtype == torch.float32 and out.numel() >= 1
+    assert workspace.dtype == torch.int32 and workspace.numel() >= SELECT_WS_WORDS
+    _call("mvt_select_kth", _ptr(values), n, k, _ptr(out), _ptr(workspace), _stream())
+
+
+def scene_stats(depths, conf, kinv, einv, V, T, t, H, W, conf_thresh, min_points, q_floor, q_radius, keys, partial, iws, state):
+    """Pool statistics of frame t of depths (V,T,1,H,W) [conf: the same layout or None] -> state (SN_WORDS int64 words, doubles and
+    integers as SN_* name them).  q_radius None: no radius quantile."""
+    assert depths.is_contiguous() and depths.dtype == torch.float32 and depths.numel() == V * T * H * W
+    assert conf is None or (conf.is_contiguous() and conf.dtype == torch.float32 and conf.numel() == V * T * H * W)
+    assert keys.dtype == torch.int32 and keys.numel() >= V * H * W
+    assert partial.dtype == torch.float64 and partial.numel() >= SCENE_BLOCKS * 3
+    assert iws.dtype == torch.int32 and iws.numel() >= SELECT_WS_WORDS + V
+    assert state.dtype == torch.int64 and state.numel() >= SN_WORDS
+    _call("mvt_scene_stats", _ptr(depths), _ptr(conf), _ptr(_f32c(kinv)), _ptr(_f32c(einv)), V, T, t, H, W, conf_thresh, min_points, q_floor,
+          -1.0 if q_radius is None else q_radius, _ptr(keys), _ptr(partial), _ptr(iws), _ptr(state), _stream())
+
+
+def _xf(params):
+    assert len(params) == 13, len(params)
+    return (C.c_double * 13)(*[float(p) for p in params])
+
+
+def scene_apply(params, depths=None, depths_out=None, extrs=None, extrs_out=None, queries=None, queries_out=None):
+    """X' = t + R (s X) with params = (s, R row-major, t), 13 host floats: depths * s, extrinsics [n][3][4] right-multiplied by the
+    rigid inverse, query rows (N,4) with the frame column kept.  Each part: a contiguous fp32 tensor and its output of the same size."""
+    for a, b in ((depths, depths_out), (extrs, extrs_out), (queries, queries_out)):
+        assert (a is None) == (b is None)
+        assert a is None or (a.dtype == b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel())
+    assert extrs is None or extrs.numel() % 12 == 0
+    assert queries is None or queries.numel() % 4 == 0
+    n = lambda t_, d: 0 if t_ is None else t_.numel() // d
+    _call("mvt_scene_apply", _ptr(depths), _ptr(depths_out), n(depths, 1), _ptr(extrs), _ptr(extrs_out), n(extrs, 12), _ptr(queries),
+          _ptr(queries_out), n(queries, 4), _xf(params), _stream())
+
+
+def scene_tracks(params, tracks, out):
+    """The same map on rows of three floats (…,3)."""
+    assert tracks.dtype == out.dtype == torch.float32 and tracks.is_contiguous() and out.is_contiguous()
+    assert tracks.numel() == out.numel() and tracks.numel() % 3 == 0 and tracks.numel() > 0
+    _call("mvt_scene_tracks", _ptr(tracks), _ptr(out), tracks.numel() // 3, _xf(params), _stream())

@@ -105,6 +105,7 @@ class EvaluationPredictor(torch.nn.Module):
         # 1 = one forward per query.  (An attribute, not a constructor argument: the constructor mirrors the reference's.)
         self.single_point_group_size = 1
         self._stream_pool = {}
+        self.last_scene_transform = None  # the SceneTransform of the last forward / open_stream (None: the scene went in as it was)
         self.model.eval()
 
     # ---- helpers -------------------------------------------------------------------------
@@ -130,6 +131,24 @@ class EvaluationPredictor(torch.nn.Module):
         cam = (ph @ kinv.t()) * z[:, None]
         return cam @ einv[:, :3].t() + einv[:, 3]
 
+    @staticmethod
+    def _scene_transform(scene_transform, auto_inputs=None):
+        """``scene_transform`` of ``forward`` / ``open_stream`` as a SceneTransform or None.  ``"auto"``:
+        ``auto_scene_normalization`` of ``auto_inputs`` = (depths, intrs, extrs, depths_conf)."""
+        if scene_transform is None:
+            return None
+        from . import scene
+        if isinstance(scene_transform, scene.SceneTransform):
+            return scene_transform
+        if isinstance(scene_transform, str) and scene_transform == "auto":
+            if auto_inputs is None:
+                raise ValueError('a streaming session cannot take scene_transform="auto": the normalisation is computed from a whole '
+                                 "frame of all views before anything is tracked.  Call mvtracker_amd.auto_scene_normalization(depths, "
+                                 "intrs, extrs) on the first frame and pass the SceneTransform it returns")
+            depths, intrs, extrs, conf = auto_inputs
+            return scene.auto_scene_normalization(depths, intrs, extrs, depths_conf=conf)
+        raise ValueError(f'scene_transform must be None, a SceneTransform or "auto", got {scene_transform!r}')
+
     def _support_rows(self, depth, pix, kinv, einv, t):
         z = _bilinear_sample_depth(depth, pix[:, 0], pix[:, 1])
         world = self._unproject(pix, z, kinv, einv)
@@ -148,8 +167,13 @@ class EvaluationPredictor(torch.nn.Module):
             save_debug_logs=False,
             debug_logs_path="",
             query_points_view=None,
+            scene_transform=None,
+            depths_conf=None,
             **kwargs,
     ):
+        """``scene_transform``: a ``SceneTransform`` or ``"auto"`` (``auto_scene_normalization`` of the raw inputs, with
+        ``depths_conf`` when given): depths, extrinsics and queries go to the model transformed, ``traj_e`` comes back in the
+        caller's world, and the transform is kept as ``last_scene_transform``.  None: nothing is done."""
         batch_size, num_views, num_frames, _, height_raw, width_raw = rgbs.shape
         _, num_points, _ = query_points_3d.shape
         assert rgbs.shape == (batch_size, num_views, num_frames, 3, height_raw, width_raw)
@@ -172,6 +196,12 @@ class EvaluationPredictor(torch.nn.Module):
         intrs = intrs.to(torch.float32)
         extrs = extrs.to(torch.float32)
         query_points_3d = query_points_3d.to(torch.float32)
+        # scene normalisation, from the raw inputs (a nearest resize with rescaled intrinsics keeps world points); the support
+        # points below are built from the transformed depths and cameras, so they need nothing of their own
+        xf = self._scene_transform(scene_transform, (depths, intrs, extrs, depths_conf))
+        self.last_scene_transform = xf
+        if xf is not None:
+            depths, extrs, query_points_3d, _ = xf.apply(depths=depths, extrs=extrs, query_points=query_points_3d)
 
         if self.interp_shape is None:  # evaluation_predictor_3dpt.py:72-87
             height, width = height_raw, width_raw
@@ -311,6 +341,8 @@ class EvaluationPredictor(torch.nn.Module):
             self.last_nan = True
         else:
             self.last_nan = False
+        if xf is not None:
+            traj_e = xf.restore_tracks(traj_e)
         return {"traj_e": traj_e, "vis_e": vis_e > self.visibility_threshold, "vis_e_as_prob": vis_e}
 
     @staticmethod
@@ -322,10 +354,12 @@ class EvaluationPredictor(torch.nn.Module):
         from . import queries
         return queries.sample_queries(depths, intrs, extrs, queries.DEFAULT_SPEC if spec is None else spec, **kw)
 
-    def open_stream(self, query_points_3d, ring_blocks=3):
+    def open_stream(self, query_points_3d, ring_blocks=3, scene_transform=None):
         """Streaming form of ``forward`` in joint mode (``MVTracker.open_stream``): returns a session whose
         ``push(rgbs, depths, intrs, extrs)`` / ``finish()`` give {"frames": (a, b), "traj_e", "vis_e", "vis_e_as_prob"} for the
-        frames that became final, the same bits as ``forward`` on the whole clip."""
+        frames that became final, the same bits as ``forward`` on the whole clip.  ``scene_transform``: a ``SceneTransform`` applied
+        to the queries here, to every pushed block's depths and extrinsics, and undone on every returned chunk (``"auto"`` is
+        refused: it needs a frame before the session has one)."""
         if self.single_point:
             raise NotImplementedError("there is no streaming form of single_point mode (one forward per query, each with local "
                                       "support grids around the query): use forward")
@@ -338,24 +372,32 @@ class EvaluationPredictor(torch.nn.Module):
             raise NotImplementedError(f"streaming takes the support grid from the first pushed frame (n_grids_per_view == 1, the "
                                       f"reference's t = 0 grid); n_grids_per_view = {self.n_grids_per_view} places grids at frames that "
                                       f"depend on the clip length")
-        return _PredictorStream(self, query_points_3d, ring_blocks)
+        xf = self._scene_transform(scene_transform)
+        self.last_scene_transform = xf
+        return _PredictorStream(self, query_points_3d, ring_blocks, xf)
 
 
 class _PredictorStream:
     """``EvaluationPredictor.open_stream``: per-block resize, intrinsics rescale and threshold exactly as in ``forward``; the
     support grid is added as queries (behind the caller's) when the first frame arrives."""
 
-    def __init__(self, predictor, query_points_3d, ring_blocks):
+    def __init__(self, predictor, query_points_3d, ring_blocks, scene_transform=None):
         self.p = predictor
+        self.xf = scene_transform
         if query_points_3d.dim() != 3 or query_points_3d.shape[0] != 1 or query_points_3d.shape[2] != 4:
             raise ValueError(f"query points must be (1, N, 4), got {tuple(query_points_3d.shape)}")
         self.num_points = query_points_3d.shape[1]
+        if self.xf is not None:
+            query_points_3d = self.xf.apply(query_points=query_points_3d)[2]
         self.session = predictor.model.open_stream(query_points_3d.to(torch.float32), iters=predictor.n_iters, ring_blocks=ring_blocks)
         self.first = True
 
     def _result(self, res):
         vis = res["vis_e"][:, :, :self.num_points]
-        return {"frames": res["frames"], "traj_e": res["traj_e"][:, :, :self.num_points, :], "vis_e": vis > self.p.visibility_threshold,
+        traj = res["traj_e"][:, :, :self.num_points, :]
+        if self.xf is not None:
+            traj = self.xf.restore_tracks(traj)
+        return {"frames": res["frames"], "traj_e": traj, "vis_e": vis > self.p.visibility_threshold,
                 "vis_e_as_prob": vis}
 
     @torch.no_grad()
@@ -370,6 +412,8 @@ class _PredictorStream:
             rgbs = rgbs.contiguous()
             depths = depths.to(torch.float32).contiguous()
             intrs, extrs = intrs.to(torch.float32), extrs.to(torch.float32)
+            if self.xf is not None:
+                depths, extrs, _, _ = self.xf.apply(depths=depths, extrs=extrs)
             if p.interp_shape is not None:  # evaluation_predictor_3dpt.py:72-87, block by block
                 height, width = p.interp_shape
                 r = torch.empty(1, V, b, 3, height, width, device=dev)
