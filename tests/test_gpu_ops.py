@@ -1,5 +1,6 @@
 """Parity of every entry point of libmvtracker_hip.so against the oracle / plain torch fp32-fp64
-references on identical inputs.  Runs on the MI355X box only (`-m gpu`); all calls go through the C ABI."""
+references on identical inputs.  Runs on the MI355X box only (`-m gpu`); all calls go through the C ABI.
+(The GEMM / conv / fused-MLP kernels variant by variant, on integer inputs with exact answers: test_gpu_matmul_exact.py.)"""
 import math
 import os
 import sys
