@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void token_assemble_kernel(const float* __rest
     x[row * ldx + d] = (v + pos[(long long)n * D + d]) + time_embed[(long long)s * D + d];
   }
   // the pad columns [D, ldx) are read as K padding by the input-transform GEMM: exact zeros, written here (no memset of x)
-  if (threadIdx.x < ldx - D) x[row * ldx + D + threadIdx.x] = 0.f;
+  for (int d = D + threadIdx.x; d < ldx; d += blockDim.x) x[row * ldx + d] = 0.f;
 }
 
 // Per-window track state (mvtracker.py:510-511, 645-680): one launch instead of a dozen tensor ops.

@@ -445,7 +445,7 @@ def delta_split(delta, ldd, gw, gb, coords, dn, rows, Cc, nan_flag=None):
 
 
 def rowdot(x, ldx, w, b, out, rows, Cc):
-    out.reshape(-1)[:rows].copy_(_v(x, rows, Cc, ldx) @ w[:Cc] + b[0])
+    out.reshape(-1)[:rows].copy_(_v(x, rows, Cc, ldx) @ w[:Cc] + (b[0] if b is not None else 0.0))
 
 
 def layernorm(x, ldx, w, b, y, ldy, rows, Cc, eps):
