@@ -33,7 +33,7 @@ def random_queries(depths, intrs, extrs, num_queries=512, t0=0, xy_radius=12.0, 
         raise AssertionError("cylinder mask removed all points; increase the radius or the z range") from None
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--sample-path", help="sample NPZ (rgbs, depths, intrs, extrs[, query_points])")
@@ -67,7 +67,27 @@ def main():
     ap.add_argument("--block-frames", type=int, default=6, metavar="B", help="frames per pushed block with --streaming")
     ap.add_argument("--save-npz", help="result file (tracks_3d, visibilities, query_points, camera data)")
     ap.add_argument("--device", default="cuda:0")
-    args = ap.parse_args()
+    ap.add_argument("--clean-depths", choices=["statistical", "radius"], default=None,
+                    help="remove outliers from every (view, frame) depth map before tracking (mvtracker_amd.clean_depths, the reference "
+                         "demo's --clean_pointcloud on the device); the saved NPZ gains the keep mask")
+    ap.add_argument("--pc-clean-nb-neighbors", type=int, default=20, help="statistical: neighbours of the mean distance")
+    ap.add_argument("--pc-clean-std-ratio", type=float, default=2.0, help="statistical: threshold = mean + ratio * deviation")
+    ap.add_argument("--pc-clean-radius", type=float, default=0.05, help="radius: search radius, in the clip's own units")
+    ap.add_argument("--pc-clean-min-points", type=int, default=5, help="radius: a point needs more neighbours than this")
+    return ap
+
+
+def depth_cleaning_from_args(args):
+    """The DepthCleaning of --clean-depths and the --pc-clean-* flags, or None."""
+    if args.clean_depths is None:
+        return None
+    from mvtracker_amd import DepthCleaning
+    return DepthCleaning(method=args.clean_depths, nb_neighbors=args.pc_clean_nb_neighbors, std_ratio=args.pc_clean_std_ratio,
+                         radius=args.pc_clean_radius, min_points=args.pc_clean_min_points)
+
+
+def main():
+    args = build_parser().parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("demo_amd.py needs an MI355X: the tracker has no CPU path")
     from mvtracker_amd import sample_io, synth
@@ -101,22 +121,28 @@ def main():
                                               [(0, zmin, zmax, r, args.num_queries, "kmeans" if args.sample_queries == "kmeans" else "")])
     elif args.random_query_points or s["query_points_3d"].shape[1] == 0:
         s["query_points_3d"] = random_queries(s["depths"].float(), s["intrs"], s["extrs"])
+    cleaning, keep = depth_cleaning_from_args(args), None
+    norm_depths = s["depths"]
+    if cleaning is not None:  # (the predictor cleans the raw depths itself; this call is for the saved mask and the normalisation)
+        from mvtracker_amd import clean_depths
+        norm_depths, keep = clean_depths(s["depths"].float(), s["intrs"], s["extrs"], cleaning)
+        print(f"depth cleaning ({args.clean_depths}): {int((~keep & (s['depths'] > 0)).sum())} of {int((s['depths'] > 0).sum())} valid pixels removed")
     xf = None
     if args.normalize_scene == "auto":  # (after the queries: sampling stays in the clip's own world)
         from mvtracker_amd import auto_scene_normalization
-        xf = auto_scene_normalization(s["depths"], s["intrs"], s["extrs"], depths_conf=s.get("depths_conf"), conf_thresh=args.norm_conf_thresh,
+        xf = auto_scene_normalization(norm_depths, s["intrs"], s["extrs"], depths_conf=s.get("depths_conf"), conf_thresh=args.norm_conf_thresh,
                                       target_radius=args.target_radius)
         print(f"scene normalisation: scale {xf.scale:.4f}, translation {np.round(xf.translation, 4).tolist()}")
     V, T = s["rgbs"].shape[1:3]
     print(f"clip: {V} views x {T} frames x {tuple(s['rgbs'].shape[-2:])}, {s['query_points_3d'].shape[1]} queries, precision {args.precision}")
     call = lambda: predictor(rgbs=s["rgbs"], depths=s["depths"], intrs=s["intrs"], extrs=s["extrs"], query_points_3d=s["query_points_3d"],
-                             scene_transform=xf)
+                             scene_transform=xf, depth_cleaning=cleaning)
     if args.streaming:
         if args.block_frames < 1:
             raise SystemExit("--block-frames must be at least 1")
 
         def call():
-            st = predictor.open_stream(s["query_points_3d"], scene_transform=xf)
+            st = predictor.open_stream(s["query_points_3d"], scene_transform=xf, depth_cleaning=cleaning)
             outs = [st.push(*(s[k][:, :, t:t + args.block_frames] for k in ("rgbs", "depths", "intrs", "extrs")))
                     for t in range(0, T, args.block_frames)]
             outs.append(st.finish())
@@ -131,6 +157,8 @@ def main():
     print(f"{'streaming session' if args.streaming else 'predictor call'}: {1e3 * dt:.1f} ms = {T / dt:.1f} frames/s = {n * T / dt:.0f} query-points*frames/s; "
           f"{int(out['vis_e'].sum())} of {out['vis_e'].numel()} track points visible; NaN guard {'TRIPPED' if predictor.last_nan else 'clean'}")
     if args.save_npz:
+        if keep is not None:
+            s["keep"] = keep[0].cpu().numpy()
         sample_io.save_result(args.save_npz, out["traj_e"], out["vis_e"], s, temporal_stride=args.temporal_stride,
                               spatial_downsample=args.spatial_downsample)
         print("saved", args.save_npz)

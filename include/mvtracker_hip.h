@@ -762,6 +762,58 @@ int mvt_scene_apply(const float* depths, float* depths_out, long long n_depth, c
 /* The same map on rows of three floats (track points); with the inverse's parameters (1/s, R^T, -R^T t / s) it undoes it. */
 int mvt_scene_tracks(const float* tracks, float* out, long long n_rows, const double* xf, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Depth cleaning: statistical and radius outlier removal of every (view, frame) cloud (reference: the demo's
+ * --clean_pointcloud, utils/visualizer_rerun.py _clean_point_cloud_with_open3d, i.e. Open3D's remove_statistical_outlier /
+ * remove_radius_outlier, whose rules the entries restate: the neighbour searches include the query point itself, the sample
+ * deviation divides by valid - 1, the radius test is strict).  Every (view, frame) depth map is its own cloud.
+ * Three stages, five launches with the two box launches between the first two, no host read between them:
+ *   mvt_clean_points -> mvt_tile_aabb -> mvt_tile_group_aabb -> mvt_clean_search -> mvt_clean_mask
+ * Workspace per cloud of P points: xyz 16 P, a / c 4 P, keep P, boxes 32 ceil(P / 64) (1 + 1/64) bytes: under 22 bytes a
+ * point.  The Python layer (mvtracker_amd/clean.py) cuts a clip into runs of frames of at most 2^23 padded points, which bounds
+ * the workspace at 176 MiB whatever the clip's length.
+ * --------------------------------------------------------------------------------------------- */
+#define MVT_CLEAN_STATISTICAL 0
+#define MVT_CLEAN_RADIUS 1
+#define MVT_CLEAN_MAX_K 64
+/* Cloud points of frames [t0, t0 + nt) of depths (V,T,1,H,W) [conf: the same layout or NULL], both read in place:
+ * xyz [V*nt][Hp*Wp][4], cloud v * nt + (t - t0), raster order on the grid padded to whole 8x8 patches (Hp, Wp = H, W rounded
+ * up to multiples of 8), which is the patch-tile layout of mvt_tile_aabb with grid_w = Wp, grid_h = Hp.  A pixel is valid when
+ * its depth is finite and > 0, conf > conf_thresh (conf given), its point is finite and (sphere given: 4 floats on the HOST,
+ * centre and radius > 0) fma(dz,dz,fma(dy,dy,dx*dx)) < fl(radius radius), the d2 of the searches.  A valid pixel
+ * gets the bits mvt_unproject gives at stride 1, level 0 (kinv / einv [V*T] from mvt_invert_cameras) and .w = 0; every other
+ * pixel, and the padding, gets (NaN, NaN, NaN, 0): mvt_tile_aabb ignores it and the search skips it.
+ * H, W <= 32768, Hp * Wp < 2^31, V * nt <= 65535.  1 launch. */
+int mvt_clean_points(const float* depths, const float* conf, const float* kinv, const float* einv, int V, int T, int t0, int nt, int H,
+                     int W, float conf_thresh, const float* sphere, float* xyz, void* stream);
+/* The self-search: every point of each of the C clouds xyz [C][P][4] is a query against its own cloud.  A point takes part
+ * when its three coordinates are finite.  d2(i,j) = fma(dz,dz,fma(dy,dy,dx*dx)) in fp32, the arithmetic of mvt_knn_scan.
+ *   MVT_CLEAN_STATISTICAL (1 <= K <= MVT_CLEAN_MAX_K): a_out [C][P] = the mean Euclidean distance from the point to its
+ *     k' = min(K, M) nearest points of the cloud, ITSELF INCLUDED at distance 0 (M = points taking part): each distance is the
+ *     fp64 sqrt of the fp32 d2, summed in fp64 in ascending order of d2, divided by k', rounded to fp32 once.  NaN for a point
+ *     that takes no part.
+ *   MVT_CLEAN_RADIUS (radius > 0, min_points >= 0): c_out [C][P] = min(#{j : d2(i,j) < fl(radius radius)}, min_points + 1),
+ *     self included; -1 for a point that takes no part.
+ * Exact at any point order: tile_box [C][ceil(P/64)][8] from mvt_tile_aabb(xyz, P, C, grid_w, grid_h) and group_box
+ * [C][ceil(ntiles/64)][8] from mvt_tile_group_aabb(tile_box, P, C) only prune, and a box is skipped only when its distance,
+ * taken with the scan's own monotone arithmetic on the per-axis gaps, exceeds the current bound.  grid_w = grid_h = 0: linear
+ * tiles of 64 points (an unorganised list); grid_w, grid_h > 0 (multiples of 8, P = grid_w * grid_h): 8x8 patches of ONE image
+ * per cloud.  The result is the same, only the speed differs.  One wave per tile, one query per lane; LDS K * 512 bytes per
+ * workgroup of 128 threads; every loop is bounded by the tile count (a cloud of NaNs, an empty cloud and M < K end normally).
+ * C <= 65535, P < 2^31 - 64.  1 launch. */
+int mvt_clean_search(const float* xyz, int C, long long P, int grid_w, int grid_h, int mode, int K, float radius, int min_points,
+                     const float* tile_box, const float* group_box, float* a_out, int* c_out, void* stream);
+/* Cloud statistics and the keep mask.  state [C][4] doubles = {M, mu, sigma, thr}, keep [C][P] uint8.
+ *   MVT_CLEAN_STATISTICAL (a [C][P] from the search, c ignored): M = points taking part (a not NaN);
+ *     mu = (sum of the a > 0) / M; sigma = sqrt(sum over a > 0 of (a - mu)^2 / (M - 1)); thr = mu + std_ratio sigma;
+ *     keep = a > 0 && a < thr; M <= 1 keeps nothing (sigma = 0).  The divisor is M, every point taking part, not the number
+ *     of a > 0.  fp64 sums in an order fixed by P alone (thread-strided, a shuffle tree, the four waves in order): no atomics,
+ *     the same bits in every run.
+ *   MVT_CLEAN_RADIUS (c [C][P], a ignored): M = points taking part (c >= 0), mu = sigma = thr = 0; keep = c > min_points.
+ * One workgroup per cloud.  1 launch. */
+int mvt_clean_mask(const float* a, const int* c, int C, long long P, int mode, float std_ratio, int min_points, double* state,
+                   unsigned char* keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,6 +116,9 @@ SIGNATURES = {
     "mvt_scene_stats": [P, P, P, P, I, I, I, I, I, F, I, F, F, P, P, P, P, P],
     "mvt_scene_apply": [P, P, LL, P, P, I, P, P, LL, P, P],
     "mvt_scene_tracks": [P, P, LL, P, P],
+    "mvt_clean_points": [P, P, P, P, I, I, I, I, I, I, F, P, P, P],
+    "mvt_clean_search": [P, I, LL, I, I, I, I, F, I, P, P, P, P, P],
+    "mvt_clean_mask": [P, P, I, LL, I, F, I, P, P, P],
 }
 _RET = {"mvt_build_arch": C.c_char_p, "mvt_encoder_workspace_bytes": C.c_longlong, "mvt_updateformer_workspace_bytes": C.c_longlong,
         "mvt_updateformer_grouped_workspace_bytes": C.c_longlong}
@@ -919,3 +922,39 @@ def scene_tracks(params, tracks, out):
     assert tracks.dtype == out.dtype == torch.float32 and tracks.is_contiguous() and out.is_contiguous()
     assert tracks.numel() == out.numel() and tracks.numel() % 3 == 0 and tracks.numel() > 0
     _call("mvt_scene_tracks", _ptr(tracks), _ptr(out), tracks.numel() // 3, _xf(params), _stream())
+
+
+# ------------------------------------------------------------------ depth cleaning (mvtracker_amd/clean.py drives these)
+CLEAN_STATISTICAL, CLEAN_RADIUS, CLEAN_MAX_K = 0, 1, 64  # MVT_CLEAN_*
+
+
+def clean_points(depths, conf, kinv, einv, V, T, t0, nt, H, W, conf_thresh, sphere, xyz):
+    """Cloud points of frames [t0, t0 + nt) of depths (V,T,1,H,W) [conf: the same layout or None] -> xyz (V*nt, Hp*Wp, 4) on the grid
+    padded to multiples of 8, NaN where the pixel is not valid.  sphere: None or (cx, cy, cz, radius) host numbers."""
+    Hp, Wp = (H + 7) // 8 * 8, (W + 7) // 8 * 8
+    assert depths.is_contiguous() and depths.dtype == torch.float32 and depths.numel() == V * T * H * W
+    assert conf is None or (conf.is_contiguous() and conf.dtype == torch.float32 and conf.numel() == V * T * H * W)
+    assert xyz.dtype == torch.float32 and xyz.is_contiguous() and xyz.numel() >= V * nt * Hp * Wp * 4
+    sp = None if sphere is None else (C.c_float * 4)(*[float(v) for v in sphere])
+    _call("mvt_clean_points", _ptr(depths), _ptr(conf), _ptr(_f32c(kinv)), _ptr(_f32c(einv)), V, T, t0, nt, H, W,
+          0.0 if conf_thresh is None else conf_thresh, sp, _ptr(xyz), _stream())
+
+
+def clean_search(xyz, Cn, Pn, grid, mode, K, radius, min_points, box, gbox, a_out=None, c_out=None):
+    """Self-search of Cn clouds xyz (Cn, Pn, 4): a_out (Cn, Pn) fp32 mean distance to the K nearest (CLEAN_STATISTICAL) or c_out
+    (Cn, Pn) int32 neighbours within radius, stopped at min_points + 1 (CLEAN_RADIUS).  box / gbox from tile_aabb / tile_group_aabb."""
+    nt = (Pn + 63) // 64
+    assert xyz.dtype == torch.float32 and xyz.is_contiguous() and xyz.numel() >= Cn * Pn * 4
+    assert box.dtype == torch.float32 and box.numel() >= Cn * nt * 8 and gbox.dtype == torch.float32 and gbox.numel() >= Cn * ((nt + 63) // 64) * 8
+    out = a_out if mode == CLEAN_STATISTICAL else c_out
+    assert out is not None and out.dtype == (torch.float32 if mode == CLEAN_STATISTICAL else torch.int32) and out.numel() >= Cn * Pn
+    _call("mvt_clean_search", _ptr(xyz), Cn, Pn, grid[0], grid[1], mode, K, radius, min_points, _ptr(box), _ptr(gbox), _ptr(a_out), _ptr(c_out),
+          _stream())
+
+
+def clean_mask(a, c, Cn, Pn, mode, std_ratio, min_points, state, keep):
+    """state (Cn, 4) fp64 = (M, mu, sigma, thr) and keep (Cn, Pn) uint8 from the search's a (CLEAN_STATISTICAL) or c (CLEAN_RADIUS)."""
+    src = a if mode == CLEAN_STATISTICAL else c
+    assert src is not None and src.numel() >= Cn * Pn and src.dtype == (torch.float32 if mode == CLEAN_STATISTICAL else torch.int32)
+    assert state.dtype == torch.float64 and state.numel() >= Cn * 4 and keep.dtype == torch.uint8 and keep.numel() >= Cn * Pn
+    _call("mvt_clean_mask", _ptr(a), _ptr(c), Cn, Pn, mode, std_ratio, min_points, _ptr(state), _ptr(keep), _stream())

@@ -169,9 +169,13 @@ class EvaluationPredictor(torch.nn.Module):
             query_points_view=None,
             scene_transform=None,
             depths_conf=None,
+            depth_cleaning=None,
             **kwargs,
     ):
-        """``scene_transform``: a ``SceneTransform`` or ``"auto"`` (``auto_scene_normalization`` of the raw inputs, with
+        """``depth_cleaning``: a ``DepthCleaning``: every (view, frame) depth map is cleaned of outliers first
+        (``mvtracker_amd.clean_depths`` on the raw inputs, with ``depths_conf`` when given, so its radius is in the caller's units),
+        and everything below sees the cleaned depths.  None: not one launch is issued.
+        ``scene_transform``: a ``SceneTransform`` or ``"auto"`` (``auto_scene_normalization`` of the raw inputs, with
         ``depths_conf`` when given): depths, extrinsics and queries go to the model transformed, ``traj_e`` comes back in the
         caller's world, and the transform is kept as ``last_scene_transform``.  None: nothing is done."""
         batch_size, num_views, num_frames, _, height_raw, width_raw = rgbs.shape
@@ -196,6 +200,9 @@ class EvaluationPredictor(torch.nn.Module):
         intrs = intrs.to(torch.float32)
         extrs = extrs.to(torch.float32)
         query_points_3d = query_points_3d.to(torch.float32)
+        if depth_cleaning is not None:  # before the normalisation and the resize
+            from . import clean
+            depths = clean.clean_depths(depths, intrs, extrs, depth_cleaning, depths_conf=depths_conf)[0]
         # scene normalisation, from the raw inputs (a nearest resize with rescaled intrinsics keeps world points); the support
         # points below are built from the transformed depths and cameras, so they need nothing of their own
         xf = self._scene_transform(scene_transform, (depths, intrs, extrs, depths_conf))
@@ -354,12 +361,14 @@ class EvaluationPredictor(torch.nn.Module):
         from . import queries
         return queries.sample_queries(depths, intrs, extrs, queries.DEFAULT_SPEC if spec is None else spec, **kw)
 
-    def open_stream(self, query_points_3d, ring_blocks=3, scene_transform=None):
+    def open_stream(self, query_points_3d, ring_blocks=3, scene_transform=None, depth_cleaning=None):
         """Streaming form of ``forward`` in joint mode (``MVTracker.open_stream``): returns a session whose
         ``push(rgbs, depths, intrs, extrs)`` / ``finish()`` give {"frames": (a, b), "traj_e", "vis_e", "vis_e_as_prob"} for the
         frames that became final, the same bits as ``forward`` on the whole clip.  ``scene_transform``: a ``SceneTransform`` applied
         to the queries here, to every pushed block's depths and extrinsics, and undone on every returned chunk (``"auto"`` is
-        refused: it needs a frame before the session has one)."""
+        refused: it needs a frame before the session has one).  ``depth_cleaning``: a ``DepthCleaning`` applied to every pushed block
+        before anything else (``push(..., depths_conf=...)`` takes the block's confidence map); clouds are per (view, frame), so
+        the streamed clip is cleaned exactly as the offline one."""
         if self.single_point:
             raise NotImplementedError("there is no streaming form of single_point mode (one forward per query, each with local "
                                       "support grids around the query): use forward")
@@ -372,18 +381,22 @@ class EvaluationPredictor(torch.nn.Module):
             raise NotImplementedError(f"streaming takes the support grid from the first pushed frame (n_grids_per_view == 1, the "
                                       f"reference's t = 0 grid); n_grids_per_view = {self.n_grids_per_view} places grids at frames that "
                                       f"depend on the clip length")
+        if depth_cleaning is not None:
+            from . import clean
+            clean._check(depth_cleaning)
         xf = self._scene_transform(scene_transform)
         self.last_scene_transform = xf
-        return _PredictorStream(self, query_points_3d, ring_blocks, xf)
+        return _PredictorStream(self, query_points_3d, ring_blocks, xf, depth_cleaning)
 
 
 class _PredictorStream:
     """``EvaluationPredictor.open_stream``: per-block resize, intrinsics rescale and threshold exactly as in ``forward``; the
     support grid is added as queries (behind the caller's) when the first frame arrives."""
 
-    def __init__(self, predictor, query_points_3d, ring_blocks, scene_transform=None):
+    def __init__(self, predictor, query_points_3d, ring_blocks, scene_transform=None, depth_cleaning=None):
         self.p = predictor
         self.xf = scene_transform
+        self.cleaning = depth_cleaning
         if query_points_3d.dim() != 3 or query_points_3d.shape[0] != 1 or query_points_3d.shape[2] != 4:
             raise ValueError(f"query points must be (1, N, 4), got {tuple(query_points_3d.shape)}")
         self.num_points = query_points_3d.shape[1]
@@ -401,7 +414,7 @@ class _PredictorStream:
                 "vis_e_as_prob": vis}
 
     @torch.no_grad()
-    def push(self, rgbs, depths, intrs, extrs):
+    def push(self, rgbs, depths, intrs, extrs, depths_conf=None):
         p = self.p
         with hip.device_guard(rgbs):
             hip.require_device(rgbs)
@@ -412,6 +425,9 @@ class _PredictorStream:
             rgbs = rgbs.contiguous()
             depths = depths.to(torch.float32).contiguous()
             intrs, extrs = intrs.to(torch.float32), extrs.to(torch.float32)
+            if self.cleaning is not None:
+                from . import clean
+                depths = clean.clean_depths(depths, intrs, extrs, self.cleaning, depths_conf=depths_conf)[0]
             if self.xf is not None:
                 depths, extrs, _, _ = self.xf.apply(depths=depths, extrs=extrs)
             if p.interp_shape is not None:  # evaluation_predictor_3dpt.py:72-87, block by block

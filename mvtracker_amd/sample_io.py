@@ -72,4 +72,6 @@ def save_result(path: str, traj_e: torch.Tensor, vis_e: torch.Tensor, sample: Di
     for k in _OPTIONAL:
         if k in sample:
             data[k] = sample[k]
+    if "keep" in sample:  # the depth cleaning's mask (V,T,1,H,W), when the demo cleaned the depths
+        data["keep"] = np.asarray(sample["keep"])
     np.savez_compressed(path, **data)
