@@ -17,7 +17,9 @@ C. Every output / workspace tensor is NaN-poisoned before a launch, padding colu
    kernel's four forms at both sides of their thresholds; argument refusals launch nothing.
 
 MVT_ATTN_FRAME_CTX is not reached here: its keys are not an input but LayerNorm + projection of the context block's rows inside the
-kernel, so no key can be planted; it stays covered by the bit-identity of test_updater_fused_attention_matches_separate_launches.
+kernel, so no key tensor can be planted.  Planted weights can: tests/test_gpu_updater_wiring_exact.py drives it through the
+composite updater call with planted projections, at full and ragged 64-token tiles; the bit-identity with the two-launch form is in
+test_updater_fused_attention_matches_separate_launches (n = 1024).
 """
 import functools
 import math

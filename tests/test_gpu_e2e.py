@@ -814,9 +814,11 @@ def test_updater_fused_attention_matches_separate_launches(model, n):
     the outputs agree to bf16 rounding (a flipped rounding of one bf16 activation moves an output by ~1e-3 of its scale), not bit
     for bit; the bits that only move WHERE partials are combined (16) stay bit-identical.  The bar against the reference is
     test_updateformer_bf16_vs_reference / test_refine_window_bf16_vs_reference_autocast.
-    Bit 5 (the virtual-self block's pass 2 inside the point<-virtual block, MVT_ATTN_FRAME_CTX; active from 4096 point rows:
-    n = 1024 and n = 400, the latter with a partial last tile and fewer tiles per frame) repeats pass 2's arithmetic in pass 2's
-    order: bit-identical to the same flags without it."""
+    Bit 5 (the virtual-self block's pass 2 inside the point<-virtual block, MVT_ATTN_FRAME_CTX) repeats pass 2's arithmetic in pass 2's
+    order: bit-identical to the same flags without it.  It is active from 4096 point rows outside the small-M form of the
+    point<-virtual block, at S = 12 from 673 tracks: of the sizes here only n = 1024 reaches it (full 64-token tiles); at n = 400 the
+    small form runs and 39 == 55 compares one path with itself.  The ragged tiles of the context form (n = 673, 740) are run by
+    tests/test_gpu_updater_wiring_exact.py."""
     x = torch.randn(1, n, 12, 581, generator=torch.Generator().manual_seed(n)).to(DEV)
     outs = {}
     with _with_precision(model, "bf16"):
