@@ -74,6 +74,18 @@ def build_parser():
     ap.add_argument("--pc-clean-std-ratio", type=float, default=2.0, help="statistical: threshold = mean + ratio * deviation")
     ap.add_argument("--pc-clean-radius", type=float, default=0.05, help="radius: search radius, in the clip's own units")
     ap.add_argument("--pc-clean-min-points", type=int, default=5, help="radius: a point needs more neighbours than this")
+    ap.add_argument("--align-cameras", action="store_true",
+                    help="refine the views' extrinsics against each other by point-to-plane ICP of their clouds before tracking "
+                         "(mvtracker_amd.align_cameras, the reference's run_icp_point_to_plane on the device); the saved NPZ holds the "
+                         "corrected extrinsics and the per-view corrections")
+    ap.add_argument("--align-max-distance", type=float, default=0.05, help="correspondence cap, in the clip's own units")
+    ap.add_argument("--align-iterations", type=int, default=30, help="ICP iterations per view and sweep")
+    ap.add_argument("--align-sweeps", type=int, default=2, help="passes over the views")
+    ap.add_argument("--align-frames", type=int, nargs="+", default=[0], metavar="F", help="frames whose clouds are aligned")
+    ap.add_argument("--align-anchor", type=int, default=0, help="the view that stays fixed")
+    ap.add_argument("--align-sample-stride", type=int, default=1, help="every s-th pixel row and column of a view is a query")
+    ap.add_argument("--align-normal-max-edge", type=float, default=None,
+                    help="a normal needs its four grid neighbours within this distance (default: --align-max-distance)")
     return ap
 
 
@@ -84,6 +96,16 @@ def depth_cleaning_from_args(args):
     from mvtracker_amd import DepthCleaning
     return DepthCleaning(method=args.clean_depths, nb_neighbors=args.pc_clean_nb_neighbors, std_ratio=args.pc_clean_std_ratio,
                          radius=args.pc_clean_radius, min_points=args.pc_clean_min_points)
+
+
+def camera_alignment_from_args(args):
+    """The CameraAlignment of --align-cameras and the --align-* flags, or None."""
+    if not args.align_cameras:
+        return None
+    from mvtracker_amd import CameraAlignment
+    return CameraAlignment(max_distance=args.align_max_distance, max_iterations=args.align_iterations, sweeps=args.align_sweeps,
+                           frames=tuple(args.align_frames), anchor=args.align_anchor, sample_stride=args.align_sample_stride,
+                           normal_max_edge=args.align_normal_max_edge)
 
 
 def main():
@@ -114,6 +136,24 @@ def main():
             s["query_points_3d"][..., 0] = torch.floor(s["query_points_3d"][..., 0] / args.temporal_stride)
     else:
         s = sample_io.load_sample(args.sample_path, device=dev, temporal_stride=args.temporal_stride, spatial_downsample=args.spatial_downsample)
+    # cleaning and camera alignment first, in the predictor's order (clean, then align on the cleaned depths): the queries below are
+    # sampled, the saved mask is cleaned and the scene is normalised with the corrected cameras, which are also what is saved
+    cleaning, alignment, keep = depth_cleaning_from_args(args), camera_alignment_from_args(args), None
+    norm_depths = s["depths"]
+    if cleaning is not None and alignment is not None:
+        from mvtracker_amd import clean_depths
+        norm_depths = clean_depths(s["depths"].float(), s["intrs"], s["extrs"], cleaning)[0]
+    if alignment is not None:  # once, here: the warm-up and the timed call both get the corrected cameras
+        from mvtracker_amd import align_cameras
+        correction = align_cameras(norm_depths.float(), s["intrs"], s["extrs"], alignment, depths_conf=s.get("depths_conf"))
+        s["extrs"] = correction.apply(s["extrs"])
+        s["camera_corrections"] = correction.transforms.cpu().numpy()
+        print(f"camera alignment: fitness {np.round(correction.fitness.cpu().numpy(), 3).tolist()}, rmse "
+              f"{np.round(correction.rmse.cpu().numpy(), 4).tolist()}, iterations {correction.iterations.cpu().tolist()}")
+    if cleaning is not None:  # (the predictor cleans the raw depths itself; this call is for the saved mask and the normalisation)
+        from mvtracker_amd import clean_depths
+        norm_depths, keep = clean_depths(s["depths"].float(), s["intrs"], s["extrs"], cleaning)
+        print(f"depth cleaning ({args.clean_depths}): {int((~keep & (s['depths'] > 0)).sum())} of {int((s['depths'] > 0).sum())} valid pixels removed")
     if args.sample_queries is not None:
         from mvtracker_amd import sample_queries
         r, zmin, zmax = args.region
@@ -121,12 +161,6 @@ def main():
                                               [(0, zmin, zmax, r, args.num_queries, "kmeans" if args.sample_queries == "kmeans" else "")])
     elif args.random_query_points or s["query_points_3d"].shape[1] == 0:
         s["query_points_3d"] = random_queries(s["depths"].float(), s["intrs"], s["extrs"])
-    cleaning, keep = depth_cleaning_from_args(args), None
-    norm_depths = s["depths"]
-    if cleaning is not None:  # (the predictor cleans the raw depths itself; this call is for the saved mask and the normalisation)
-        from mvtracker_amd import clean_depths
-        norm_depths, keep = clean_depths(s["depths"].float(), s["intrs"], s["extrs"], cleaning)
-        print(f"depth cleaning ({args.clean_depths}): {int((~keep & (s['depths'] > 0)).sum())} of {int((s['depths'] > 0).sum())} valid pixels removed")
     xf = None
     if args.normalize_scene == "auto":  # (after the queries: sampling stays in the clip's own world)
         from mvtracker_amd import auto_scene_normalization

@@ -814,6 +814,77 @@ int mvt_clean_search(const float* xyz, int C, long long P, int grid_w, int grid_
 int mvt_clean_mask(const float* a, const int* c, int C, long long P, int mode, float std_ratio, int min_points, double* state,
                    unsigned char* keep, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Camera alignment: point-to-plane ICP of one view's clouds onto the clouds of the other views (reference:
+ * conversions/droid/utils/optimization.py run_icp_point_to_plane, i.e. Open3D registration_icp with
+ * TransformationEstimationPointToPlane, whose rules the entries restate: the correspondence is the nearest target point strictly
+ * inside max_correspondence_distance, r = (p - q) . n, J = [p x n | n], J^T J x = -J^T r, T(x) = TransformVector6dToMatrix4d(x),
+ * fitness = correspondences / source points, inlier_rmse = sqrt(sum d2 / correspondences), stop when both change by less than
+ * 1e-6).  Clouds are [frames][P][4] float rows (x, y, z, 0) with NaN rows for points that take no part: organised (grid_w x grid_h,
+ * multiples of 8, P = grid_w grid_h, raster order: what mvt_clean_points writes with nt = frames) or point lists (grid 0, 0).
+ * A frame's source cloud only meets the same frame's target clouds; the normal equations are summed over the frames.
+ * One ICP run of max_iterations is max_iterations + 1 times (mvt_align_correspond, mvt_align_solve), the last solve with
+ * final_call = 1, then mvt_align_transform -> mvt_align_normals -> mvt_tile_aabb -> mvt_tile_group_aabb of the moved clouds.
+ * No atomics and no host read: both entries return at once when istate[MVT_ALIGN_I_DONE] is set.
+ * --------------------------------------------------------------------------------------------- */
+#define MVT_ALIGN_MAX_TARGETS 8
+#define MVT_ALIGN_ROW 30  /* doubles per partial row: 21 upper entries of J^T J (row-major), 6 of J^T r, count, sum r^2, sum d2 */
+#define MVT_ALIGN_HIST 10 /* doubles per evaluation: count, fitness, rmse, sum r^2, x[6] (0 when no update followed) */
+#define MVT_ALIGN_I_DONE 0 /* words of istate (4 int32, zeroed by the caller before a run) */
+#define MVT_ALIGN_I_ITERATIONS 1
+#define MVT_ALIGN_I_STATUS 2
+#define MVT_ALIGN_I_EVALS 3
+#define MVT_ALIGN_FEW 1      /* status bit: fewer than 6 correspondences, D left as it was */
+#define MVT_ALIGN_SINGULAR 2 /* status bit: a pivot <= 1e-12 x the largest diagonal entry, D left as it was */
+typedef struct mvt_align_cloud {
+  const float* xyz;       /* [frames][P][4] the target's points as they stand now */
+  const float* nrm;       /* [frames][P][4] their normals; a point with a NaN normal.x takes no part */
+  const float* tile_box;  /* [frames][ceil(P/64)][8] from mvt_tile_aabb(xyz, P, frames, grid_w, grid_h) */
+  const float* group_box; /* [frames][ceil(ntiles/64)][8] from mvt_tile_group_aabb */
+  long long P;
+  int grid_w, grid_h;
+} mvt_align_cloud;
+/* Normals of C organised clouds xyz [C][grid_h grid_w][4]: with a = p[x+1] - p[x-1], b = p[y+1] - p[y-1] (fp32),
+ * c = a x b with every product and difference rounded on its own, n = c / sqrt(fma(cz,cz,fma(cy,cy,cx cx))) (correctly rounded
+ * sqrt and divisions).  Valid when the pixel is not on the border, the centre and the four neighbours are finite, each neighbour
+ * has d2(neighbour, centre) <= fl(max_edge max_edge) (the d2 of the searches) and the length is > 0 and finite; every other pixel
+ * gets (NaN, NaN, NaN, 0).  The orientation is left as it falls: point-to-plane only uses (n . d)^2.  1 launch. */
+int mvt_align_normals(const float* xyz, int C, int grid_w, int grid_h, float max_edge, float* nrm, void* stream);
+/* xyz[i] = D xyz0[i] for n rows of 4 floats; D: 12 doubles ON THE DEVICE (rows of [R|t]).  Coordinate r is
+ * fma(D[4r+2], z, fma(D[4r+1], y, D[4r] x)) + D[4r+3] in fp64, rounded to fp32 once; a NaN row stays NaN, and so does every row whose
+ * result is not finite in all three coordinates (an infinite input, an overflow): the marker of a point that takes no part; .w = 0. */
+int mvt_align_transform(const float* xyz0, const double* D, long long n, float* xyz, void* stream);
+/* Query tiles of a source cloud (host arithmetic, no launch): the number of 64-query tiles per frame, or -1 for arguments the
+ * search refuses.  Point list (grid 0, 0; sample_stride 1): query slot q = point q.  Organised: the pixels with y % s == 0 and
+ * x % s == 0 form hs x ws samples (hs = ceil(grid_h / s), ws = ceil(grid_w / s)), cut into 8x8 patches of samples,
+ * *tiles_per_row = ceil(ws / 8) patches per row; slot (tile, lane) is sample (8 (tile / tpr) + lane / 8, 8 (tile % tpr) + lane % 8),
+ * pixel (s sy, s sx), and takes no part when it lies outside the samples. */
+int mvt_align_queries(long long P, int grid_w, int grid_h, int sample_stride, int* tiles_per_row);
+/* The search and the tile sums.  Queries: the slots above of src_xyz0 [frames][src_P][4], each taken as D p0 with
+ * mvt_align_transform's rounding.  Candidates: the points with a valid normal of targets[0..n_targets) (host array), same frame.
+ * d2 = fma(dz,dz,fma(dy,dy,dx dx)) in fp32, the arithmetic of mvt_knn_scan.  Result per query: the candidate with the smallest
+ * (d2, cloud, index) among those with d2 < cap2 (strict; cap2 = fl(fl(cap) fl(cap)) comes in rounded).  Tile and group boxes only
+ * prune: a box is skipped when its distance, with the same monotone arithmetic, EXCEEDS the query's current bound (its best d2,
+ * cap2 at the start) -- strictly, so that a point at exactly the bound in a tile visited later still wins a tie by its index.
+ * q_idx / q_d2 [frames][tiles 64] (both or neither): the global target index (point j of target k is sum of P of the targets
+ * before k, + j; -1 for none) and d2 (NaN for none).  partial [frames][tiles][MVT_ALIGN_ROW]: the sums over the tile's matched
+ * queries, each by the shuffle tree lane ^ 32, ^ 16, .. ^ 1 in fp64, with r and J in fp64 from the fp32 p (query), q (target
+ * point) and n.  One wave per tile, one query per lane, 128 threads, no LDS.  Returns at once when istate[0] != 0.
+ * The targets' points together < 2^31 - 64.  1 launch. */
+int mvt_align_correspond(const float* src_xyz0, long long src_P, int src_grid_w, int src_grid_h, int sample_stride, int frames,
+                         const double* D, float cap2, const mvt_align_cloud* targets, int n_targets, const int* istate,
+                         double* partial, int* q_idx, float* q_d2, void* stream);
+/* One evaluation of the ICP loop, in one workgroup.  Column c of partial [n_rows][MVT_ALIGN_ROW] is summed by 8 threads (thread g
+ * takes rows g, g + 8, .. ascending; the 8 sums are added for g = 0..7: an order fixed by n_rows) -> sums [30] (optional).
+ * count = sums[27], fitness = count / *n_queries (device double: the source points taking part), rmse = sqrt(sums[29] / count),
+ * written to hist[evals] (MVT_ALIGN_HIST doubles, while evals < max_hist) and to result [4] = {fitness, rmse, iterations, status}.
+ * If this is not the first evaluation and |fitness - previous| < 1e-6 and |rmse - previous| < 1e-6 (the previous ones read from
+ * result): done.  Otherwise, unless final_call: count < 6 -> MVT_ALIGN_FEW and done; else LDL^T of J^T J (a pivot
+ * <= 1e-12 max diagonal -> MVT_ALIGN_SINGULAR and done), x = solution of J^T J x = -J^T r, T(x) = [Rz(x2) Ry(x1) Rx(x0) | x3 x4 x5],
+ * D <- T(x) D, iterations += 1, x to the hist row.  Returns at once when istate[0] != 0.  1 launch. */
+int mvt_align_solve(const double* partial, long long n_rows, const double* n_queries, int final_call, int max_hist, double* D,
+                    int* istate, double* hist, double* sums, double* result, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

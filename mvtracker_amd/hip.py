@@ -119,6 +119,11 @@ SIGNATURES = {
     "mvt_clean_points": [P, P, P, P, I, I, I, I, I, I, F, P, P, P],
     "mvt_clean_search": [P, I, LL, I, I, I, I, F, I, P, P, P, P, P],
     "mvt_clean_mask": [P, P, I, LL, I, F, I, P, P, P],
+    "mvt_align_normals": [P, I, I, I, F, P, P],
+    "mvt_align_transform": [P, P, LL, P, P],
+    "mvt_align_queries": [LL, I, I, I, P],
+    "mvt_align_correspond": [P, LL, I, I, I, I, P, F, P, I, P, P, P, P, P],
+    "mvt_align_solve": [P, LL, P, I, I, P, P, P, P, P, P],
 }
 _RET = {"mvt_build_arch": C.c_char_p, "mvt_encoder_workspace_bytes": C.c_longlong, "mvt_updateformer_workspace_bytes": C.c_longlong,
         "mvt_updateformer_grouped_workspace_bytes": C.c_longlong}
@@ -958,3 +963,70 @@ def clean_mask(a, c, Cn, Pn, mode, std_ratio, min_points, state, keep):
     assert src is not None and src.numel() >= Cn * Pn and src.dtype == (torch.float32 if mode == CLEAN_STATISTICAL else torch.int32)
     assert state.dtype == torch.float64 and state.numel() >= Cn * 4 and keep.dtype == torch.uint8 and keep.numel() >= Cn * Pn
     _call("mvt_clean_mask", _ptr(a), _ptr(c), Cn, Pn, mode, std_ratio, min_points, _ptr(state), _ptr(keep), _stream())
+
+
+# ------------------------------------------------------------------ camera alignment (mvtracker_amd/align.py drives these)
+ALIGN_MAX_TARGETS, ALIGN_ROW, ALIGN_HIST = 8, 30, 10  # MVT_ALIGN_*
+ALIGN_I_DONE, ALIGN_I_ITERATIONS, ALIGN_I_STATUS, ALIGN_I_EVALS = 0, 1, 2, 3
+ALIGN_FEW, ALIGN_SINGULAR = 1, 2
+
+
+class AlignCloud(C.Structure):
+    """mvt_align_cloud of include/mvtracker_hip.h."""
+    _fields_ = [("xyz", C.c_void_p), ("nrm", C.c_void_p), ("tile_box", C.c_void_p), ("group_box", C.c_void_p), ("P", C.c_longlong),
+                ("grid_w", C.c_int), ("grid_h", C.c_int)]
+
+
+def align_normals(xyz, Cn, grid, max_edge, nrm):
+    """nrm (Cn, h*w, 4) <- normals of the Cn organised clouds xyz (Cn, h*w, 4), grid = (w, h); NaN rows where there is none."""
+    n = Cn * grid[0] * grid[1] * 4
+    assert xyz.dtype == nrm.dtype == torch.float32 and xyz.is_contiguous() and nrm.is_contiguous() and xyz.numel() >= n and nrm.numel() >= n
+    _call("mvt_align_normals", _ptr(xyz), Cn, grid[0], grid[1], max_edge, _ptr(nrm), _stream())
+
+
+def align_transform(xyz0, D, n, xyz):
+    """xyz[:n] = D xyz0[:n] (rows of 4 floats); D: 12 doubles on the device."""
+    assert xyz0.dtype == xyz.dtype == torch.float32 and xyz0.is_contiguous() and xyz.is_contiguous()
+    assert xyz0.numel() >= n * 4 and xyz.numel() >= n * 4 and D.dtype == torch.float64 and D.is_contiguous() and D.numel() >= 12
+    _call("mvt_align_transform", _ptr(xyz0), _ptr(D), n, _ptr(xyz), _stream())
+
+
+def align_queries(Pn, grid=(0, 0), sample_stride=1):
+    """(query tiles per frame, tiles per row) of a source cloud; raises for a cloud the search refuses."""
+    tpr = C.c_int(0)
+    n = _lib.mvt_align_queries(Pn, grid[0], grid[1], sample_stride, C.cast(C.pointer(tpr), C.c_void_p))
+    if n <= 0:
+        raise HipError(f"mvt_align_queries refused P {Pn} grid {grid} sample_stride {sample_stride}")
+    return n, tpr.value
+
+
+def align_correspond(src0, Pn, grid, sample_stride, frames, D, cap2, targets, istate, partial, q_idx=None, q_d2=None):
+    """targets: list of dicts(xyz, nrm, box, gbox, P, grid) of (frames, P, 4) clouds; partial (frames, tiles, ALIGN_ROW) fp64;
+    q_idx / q_d2 (frames, tiles * 64) int32 / fp32 or None."""
+    ntq = align_queries(Pn, grid, sample_stride)[0]
+    assert src0.dtype == torch.float32 and src0.is_contiguous() and src0.numel() >= frames * Pn * 4
+    assert D.dtype == torch.float64 and D.is_contiguous() and D.numel() >= 12 and istate.dtype == torch.int32 and istate.numel() >= 4
+    assert partial.dtype == torch.float64 and partial.is_contiguous() and partial.numel() >= frames * ntq * ALIGN_ROW
+    assert (q_idx is None) == (q_d2 is None)
+    assert q_idx is None or (q_idx.dtype == torch.int32 and q_d2.dtype == torch.float32 and min(q_idx.numel(), q_d2.numel()) >= frames * ntq * 64)
+    arr = (AlignCloud * max(1, len(targets)))()
+    for i, t in enumerate(targets):
+        nt = (t["P"] + 63) // 64
+        for k in ("xyz", "nrm"):
+            assert t[k].dtype == torch.float32 and t[k].is_contiguous() and t[k].numel() >= frames * t["P"] * 4
+        assert t["box"].dtype == torch.float32 and t["box"].is_contiguous() and t["box"].numel() >= frames * nt * 8
+        assert t["gbox"].dtype == torch.float32 and t["gbox"].is_contiguous() and t["gbox"].numel() >= frames * ((nt + 63) // 64) * 8
+        arr[i] = AlignCloud(_ptr(t["xyz"]), _ptr(t["nrm"]), _ptr(t["box"]), _ptr(t["gbox"]), t["P"], t["grid"][0], t["grid"][1])
+    _call("mvt_align_correspond", _ptr(src0), Pn, grid[0], grid[1], sample_stride, frames, _ptr(D), cap2, C.cast(arr, C.c_void_p), len(targets),
+          _ptr(istate), _ptr(partial), _ptr(q_idx), _ptr(q_d2), _stream())
+
+
+def align_solve(partial, n_rows, n_queries, final_call, D, istate, hist, result, sums=None):
+    """One evaluation of the ICP loop: hist (max_hist, ALIGN_HIST) fp64, result (4,) fp64, sums (ALIGN_ROW,) fp64 or None."""
+    assert partial.dtype == torch.float64 and partial.is_contiguous() and partial.numel() >= n_rows * ALIGN_ROW
+    assert n_queries.dtype == torch.float64 and n_queries.numel() >= 1 and D.dtype == torch.float64 and D.is_contiguous() and D.numel() >= 12
+    assert istate.dtype == torch.int32 and istate.numel() >= 4 and hist.dtype == torch.float64 and hist.is_contiguous()
+    assert result.dtype == torch.float64 and result.is_contiguous() and result.numel() >= 4
+    assert sums is None or (sums.dtype == torch.float64 and sums.numel() >= ALIGN_ROW)
+    _call("mvt_align_solve", _ptr(partial), n_rows, _ptr(n_queries), int(final_call), hist.numel() // ALIGN_HIST, _ptr(D), _ptr(istate), _ptr(hist),
+          _ptr(sums), _ptr(result), _stream())

@@ -106,6 +106,7 @@ class EvaluationPredictor(torch.nn.Module):
         self.single_point_group_size = 1
         self._stream_pool = {}
         self.last_scene_transform = None  # the SceneTransform of the last forward / open_stream (None: the scene went in as it was)
+        self.last_camera_correction = None  # the CameraCorrection of the last forward (None: the cameras went in as they were)
         self.model.eval()
 
     # ---- helpers -------------------------------------------------------------------------
@@ -170,9 +171,13 @@ class EvaluationPredictor(torch.nn.Module):
             scene_transform=None,
             depths_conf=None,
             depth_cleaning=None,
+            camera_alignment=None,
             **kwargs,
     ):
-        """``depth_cleaning``: a ``DepthCleaning``: every (view, frame) depth map is cleaned of outliers first
+        """``camera_alignment``: a ``CameraAlignment`` (the views are refined against each other by ``mvtracker_amd.align_cameras`` on
+        the raw inputs after depth cleaning, so ``max_distance`` is in the caller's units) or a ready ``CameraCorrection``; everything
+        below sees ``correction.apply(extrs)``, and the correction is kept as ``last_camera_correction``.  None: not one launch.
+        ``depth_cleaning``: a ``DepthCleaning``: every (view, frame) depth map is cleaned of outliers first
         (``mvtracker_amd.clean_depths`` on the raw inputs, with ``depths_conf`` when given, so its radius is in the caller's units),
         and everything below sees the cleaned depths.  None: not one launch is issued.
         ``scene_transform``: a ``SceneTransform`` or ``"auto"`` (``auto_scene_normalization`` of the raw inputs, with
@@ -203,6 +208,17 @@ class EvaluationPredictor(torch.nn.Module):
         if depth_cleaning is not None:  # before the normalisation and the resize
             from . import clean
             depths = clean.clean_depths(depths, intrs, extrs, depth_cleaning, depths_conf=depths_conf)[0]
+        self.last_camera_correction = None
+        if camera_alignment is not None:  # after the cleaning, before the normalisation and the resize
+            from . import align
+            if isinstance(camera_alignment, align.CameraCorrection):
+                correction = camera_alignment
+            elif isinstance(camera_alignment, align.CameraAlignment):
+                correction = align.align_cameras(depths, intrs, extrs, camera_alignment, depths_conf=depths_conf)
+            else:
+                raise ValueError(f"camera_alignment must be None, a CameraAlignment or a CameraCorrection, got {camera_alignment!r}")
+            self.last_camera_correction = correction
+            extrs = correction.apply(extrs)
         # scene normalisation, from the raw inputs (a nearest resize with rescaled intrinsics keeps world points); the support
         # points below are built from the transformed depths and cameras, so they need nothing of their own
         xf = self._scene_transform(scene_transform, (depths, intrs, extrs, depths_conf))

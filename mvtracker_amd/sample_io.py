@@ -74,4 +74,6 @@ def save_result(path: str, traj_e: torch.Tensor, vis_e: torch.Tensor, sample: Di
             data[k] = sample[k]
     if "keep" in sample:  # the depth cleaning's mask (V,T,1,H,W), when the demo cleaned the depths
         data["keep"] = np.asarray(sample["keep"])
+    if "camera_corrections" in sample:  # the camera alignment's per-view transforms (V,4,4), when the demo aligned the cameras
+        data["camera_corrections"] = np.asarray(sample["camera_corrections"])
     np.savez_compressed(path, **data)
