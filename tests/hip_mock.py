@@ -290,9 +290,28 @@ def tile_aabb(xyz, Pn, T, box, grid=(0, 0)):
     box.zero_()  # culling only prunes: the mock scan ignores the boxes
 
 
+KEY_MAX = -1  # the library's padding key 0xFFFFFFFFFFFFFFFF, read as int64
+_SIGN = torch.iinfo(torch.int64).min
+
+
+def _unsigned(keys):
+    """int64 tensor whose signed order is the unsigned order of ``keys`` (the library compares its keys as uint64)."""
+    return keys ^ _SIGN
+
+
+def _frame(frame0, s, frame_step, T):
+    """Store frame of window slot s: frame0 + s * frame_step clamped to the clip at BOTH ends (store_frame of knn_corr.hip)."""
+    return min(max(frame0 + s * frame_step, 0), T - 1)
+
+
+def _rows(idx, Pn):
+    """Neighbour indices as the kernels read them: unsigned, anything >= Pn is row Pn - 1."""
+    return (idx.long() & 0xFFFFFFFF).clamp(max=Pn - 1)
+
+
 def knn_scan(xyz, Pn, coords, N, S, frame0, frame_step, T, K, nseg, keys, seed_idx=None, seed_k=0, seed_dims=(0, 0, 0, 0), box=None,
              grid=(0, 0)):
-    # the seed / boxes only prune; the result is the exact kNN either way.  Check the seed contract: valid distinct indices.
+    # the seed / boxes only prune; the merged result is the exact kNN either way.  Check the seed contract: valid distinct indices.
     if seed_idx is not None:
         si = seed_idx.reshape(N, S, seed_k).long()
         cw, ch, fw, fh = seed_dims
@@ -305,15 +324,20 @@ def knn_scan(xyz, Pn, coords, N, S, frame0, frame_step, T, K, nseg, keys, seed_i
     c = torch.as_strided(coords, (N, S, 3), (S * 3, 3, 1))
     kv = torch.as_strided(keys, (N, S, nseg, K), (S * nseg * K, nseg * K, K, 1))
     per = ((Pn + 63) // 64 + nseg - 1) // nseg * 64
-    kv.fill_(torch.iinfo(torch.int64).max)  # pads a short segment (sorts last, like the library's KEY_MAX)
+    kv.fill_(KEY_MAX)  # pads a short segment (sorts last in the library's unsigned order)
     for s in range(S):
-        f = min(frame0 + s * frame_step, T - 1)
+        f = _frame(frame0, s, frame_step, T)
         d2 = _d2(X[f, :, :3], c[:, s])
         key = (d2.view(torch.int32).to(torch.int64) << 32) | torch.arange(Pn)[None]
+        key = torch.where(torch.isnan(d2), torch.full_like(key, KEY_MAX), key)  # a NaN distance passes no compare: never a candidate
+        if seed_idx is not None:  # the seed's largest distance is the first threshold: nothing beyond it is ever listed
+            sd = torch.gather(d2, 1, si[:, s])
+            thr = torch.where(torch.isnan(sd), torch.full_like(sd, float("inf")), sd).amax(1, keepdim=True)
+            key = torch.where(d2 > thr, torch.full_like(key, KEY_MAX), key)
         for g in range(nseg):
-            seg = key[:, g * per:min(Pn, (g + 1) * per)]
+            seg = _unsigned(key[:, g * per:min(Pn, (g + 1) * per)])
             kk = min(K, seg.shape[1])
-            kv[:, s, g, :kk] = torch.topk(seg, kk, dim=1, largest=False, sorted=True).values
+            kv[:, s, g, :kk] = _unsigned(torch.topk(seg, kk, dim=1, largest=False, sorted=True).values)
 
 
 def knn_scan_levels(levels, coords, N, S, frame0, frame_step, T, K, seed_k=0):
@@ -355,7 +379,7 @@ def knn_merge_levels(levels, N, S, K):
 
 def knn_merge(keys, N, S, K, nseg, Pn, idx_out):
     kv = torch.as_strided(keys, (N, S, nseg * K), (S * nseg * K, nseg * K, 1))
-    idx = (torch.sort(kv, dim=2).values[:, :, :K] & 0xFFFFFFFF).clamp(max=Pn - 1)
+    idx = (_unsigned(torch.sort(_unsigned(kv), dim=2, stable=True).values[:, :, :K]) & 0xFFFFFFFF).clamp(max=Pn - 1)
     idx_out.reshape(N, S, K).copy_(idx.int())
 
 
@@ -365,11 +389,11 @@ def corr_gather_dot(xyz_l, fvec_l, P_l, idx_l, Cc, targets, coords, N, S, frame0
     for lvl, (xyz, fvec, Pn, idx_t) in enumerate(zip(xyz_l, fvec_l, P_l, idx_l)):
         X = torch.as_strided(xyz, (T, Pn, 4), (Pn * 4, 4, 1))
         Fv = torch.as_strided(fvec, (T, Pn, Cc), (Pn * Cc, Cc, 1))
-        idx = idx_t.reshape(N, S, K).long()
+        idx = _rows(idx_t.reshape(N, S, K), Pn)
         o = torch.as_strided(out, (N, S, K, 4), (S * ldo, ldo, 4, 1), out.storage_offset() + o_off + lvl * 4 * K)
         for s in range(S):
-            f = min(frame0 + s * frame_step, T - 1)
-            nf = Fv[f][idx[:, s]]
+            f = _frame(frame0, s, frame_step, T)
+            nf = Fv[f][idx[:, s]].float()  # (bf16 rows: fp32 accumulation, as the kernel)
             o[:, s, :, 0] = torch.einsum("nc,nkc->nk", tg[:, s], nf) / math.sqrt(Cc)
             o[:, s, :, 1:] = X[f][idx[:, s]][..., :3] - c[:, s, None]
 
@@ -382,10 +406,10 @@ def corr_gather_dot_opts(xyz_l, fvec_l, P_l, idx_l, Cc, targets, coords, N, S, f
     for lvl, (xyz, fvec, Pn, idx_t) in enumerate(zip(xyz_l, fvec_l, P_l, idx_l)):
         X = torch.as_strided(xyz, (T, Pn, 4), (Pn * 4, 4, 1))
         Fv = torch.as_strided(fvec, (T, Pn, Cc), (Pn * Cc, Cc, 1))
-        idx = idx_t.reshape(N, S, K).long()
+        idx = _rows(idx_t.reshape(N, S, K), Pn)
         o = torch.as_strided(out, (N, S, K, OW), (S * ldo, ldo, OW, 1), out.storage_offset() + o_off + lvl * OW * K)
         for s in range(S):
-            f = min(frame0 + s * frame_step, T - 1)
+            f = _frame(frame0, s, frame_step, T)
             nf = Fv[f][idx[:, s]].float()
             o[:, s, :, :groups] = torch.einsum("ngc,nkgc->nkg", tg[:, s].reshape(N, groups, -1), nf.reshape(N, K, groups, -1)) / math.sqrt(Cc / groups)
             nx = X[f][idx[:, s]][..., :3]
@@ -398,7 +422,7 @@ def corr_gather_dot_opts(xyz_l, fvec_l, P_l, idx_l, Cc, targets, coords, N, S, f
 
 
 def knn1_gather(fvec, Pn, Cc, keys, n, nseg, frame, feat_out, idx_out=None):
-    idx = keys.reshape(n, nseg).min(1).values & 0xFFFFFFFF
+    idx = _rows(_unsigned(_unsigned(keys.reshape(n, nseg)).min(1).values), Pn)
     Fv = torch.as_strided(fvec, (frame + 1, Pn, Cc), (Pn * Cc, Cc, 1))
     feat_out.reshape(n, Cc).copy_(Fv[frame][idx])
     if idx_out is not None:
@@ -473,7 +497,23 @@ def broadcast_rows(v, x, ld, n, S, Cc):
 
 
 def window_corr(fmap, targets, coords, out, BS, N, Cc, h, w, level, radius, ldo, o_off):
-    raise NotImplementedError("window_corr is only exercised on the GPU")
+    """The target dotted with every texel of the (2r+2)^2 patch around floor(coords / 2^level) (zero outside the map), then the four
+    neighbouring dots blended with the window's one pair of fractions; output a * (2r+1) + b samples (x + a - r, y + b - r)."""
+    win, side = 2 * radius + 1, 2 * radius + 2
+    fm = torch.as_strided(fmap, (BS, h, w, Cc), (h * w * Cc, w * Cc, Cc, 1)).float()
+    tg = torch.as_strided(targets, (BS * N, Cc), (Cc, 1))
+    c = torch.as_strided(coords, (BS * N, 2), (2, 1)) * (1.0 / (1 << level))
+    c0 = torch.floor(c)
+    frac = c - c0
+    o = torch.as_strided(out, (BS * N, win * win), (ldo, 1), out.storage_offset() + o_off)
+    for row in range(BS * N):
+        dm = F.pad(fm[row // N] @ tg[row], (side, side, side, side))  # zero border wide enough for any clamped patch corner
+        x0 = int(c0[row, 0].clamp(-radius - 2, w + radius)) - radius + side  # (clamped: a patch wholly outside stays wholly outside)
+        y0 = int(c0[row, 1].clamp(-radius - 2, h + radius)) - radius + side
+        p = dm[y0:y0 + side, x0:x0 + side]
+        ax, ay = frac[row, 0], frac[row, 1]
+        v = (1 - ay) * ((1 - ax) * p[:-1, :-1] + ax * p[:-1, 1:]) + ay * ((1 - ax) * p[1:, :-1] + ax * p[1:, 1:])
+        o[row] = v.t().reshape(-1) / math.sqrt(Cc)
 
 
 def window_prepare(qxyz, qt, feat_init, prev_coords, prev_vis, n, p0, S, Cc, w, T, coords, mask_vis, ffeats):
