@@ -86,6 +86,11 @@ def build_parser():
     ap.add_argument("--align-sample-stride", type=int, default=1, help="every s-th pixel row and column of a view is a query")
     ap.add_argument("--align-normal-max-edge", type=float, default=None,
                     help="a normal needs its four grid neighbours within this distance (default: --align-max-distance)")
+    ap.add_argument("--align-normals", choices=("grid", "pca"), default="grid",
+                    help="target normals: the cross product of grid neighbours, or a PCA over the nearest points "
+                         "(mvtracker_amd.estimate_normals, the reference's estimate_normals)")
+    ap.add_argument("--align-normal-radius", type=float, default=None, help="PCA normals: neighbour radius (default: --align-max-distance)")
+    ap.add_argument("--align-normal-max-nn", type=int, default=30, help="PCA normals: neighbours per point, at most")
     return ap
 
 
@@ -102,10 +107,13 @@ def camera_alignment_from_args(args):
     """The CameraAlignment of --align-cameras and the --align-* flags, or None."""
     if not args.align_cameras:
         return None
-    from mvtracker_amd import CameraAlignment
-    return CameraAlignment(max_distance=args.align_max_distance, max_iterations=args.align_iterations, sweeps=args.align_sweeps,
-                           frames=tuple(args.align_frames), anchor=args.align_anchor, sample_stride=args.align_sample_stride,
-                           normal_max_edge=args.align_normal_max_edge)
+    from mvtracker_amd import CameraAlignment, PcaCameraAlignment
+    kw = dict(max_distance=args.align_max_distance, max_iterations=args.align_iterations, sweeps=args.align_sweeps,
+              frames=tuple(args.align_frames), anchor=args.align_anchor, sample_stride=args.align_sample_stride,
+              normal_max_edge=args.align_normal_max_edge)
+    if args.align_normals == "pca":
+        return PcaCameraAlignment(normal_radius=args.align_normal_radius, normal_max_nn=args.align_normal_max_nn, **kw)
+    return CameraAlignment(**kw)
 
 
 def main():

@@ -885,6 +885,67 @@ int mvt_align_correspond(const float* src_xyz0, long long src_P, int src_grid_w,
 int mvt_align_solve(const double* partial, long long n_rows, const double* n_queries, int final_call, int max_hist, double* D,
                     int* istate, double* hist, double* sums, double* result, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Cloud preparation: PCA normals and voxel downsampling (reference: conversions/droid/utils/optimization.py estimate_normals /
+ * downsample_pointcloud, i.e. Open3D's estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) and voxel_down_sample, whose rules
+ * the entries restate).  The two parts share no kernel.
+ * --------------------------------------------------------------------------------------------- */
+#define MVT_NORMALS_MAX_NN 64
+/* Normals of every point of each of the C clouds xyz [C][P][4] from a PCA over its neighbours in the same cloud.  A point takes
+ * part when its three coordinates are finite.  d2(i,j) = fma(dz,dz,fma(dy,dy,dx*dx)) in fp32, the arithmetic of mvt_knn_scan.
+ * Neighbours of point i: of the points taking part with d2 < fl(fl(radius) fl(radius)) (strict; i itself is one, at d2 = 0), the
+ * max_nn smallest by the key (d2, index) -- Open3D's knnSearch(max_nn) cut at r^2, so r^2 bounds the search from the first
+ * candidate on.  radius = +inf gives plain kNN.  3 <= max_nn <= MVT_NORMALS_MAX_NN.
+ * With n neighbours: e_j = (double)p_j - (double)p_i (exact), S1 = sum e_j and S2 = sum e_j e_j^T in fp64 in ascending key order,
+ * C = S2 / n - (S1 / n)(S1 / n)^T, and the normal is a unit eigenvector of the smallest eigenvalue of C (cyclic Jacobi in fp64, a
+ * fixed number of sweeps), rounded to fp32 once; .w = 0.
+ * DEVIATION from Open3D: with n < 3, or lambda_mid <= 1e-12 lambda_max (collinear or coincident neighbours), and for a point that
+ * takes no part, the row is (NaN, NaN, NaN, 0), which mvt_align_correspond skips; Open3D leaves (0, 0, 1) there, which ICP would
+ * take for a real plane.
+ * viewpoint: NULL, or [C][3] floats on the device: the normal is flipped so that n . (vp - p_i) >= 0 in fp64 (Open3D's
+ * orient_normals_towards_camera_location).  Without it the sign is left as it falls: point-to-plane only uses (n . d)^2.
+ * Optional outputs (NULL: not written): nbr_idx [C][P][max_nn] the neighbours in ascending key order, padded with -1;
+ * nbr_cnt [C][P] = n, -1 for a point that takes no part; cov [C][P][6] = C as (xx, xy, xz, yy, yz, zz), NaN for such a point.
+ * grid_w, grid_h, tile_box, group_box: as mvt_clean_search takes them (they only prune: a box is skipped only when its lower
+ * bound EXCEEDS the query's bound, so an equal-d2 point with a lower index in a later tile still wins).  One wave per tile, one
+ * query per lane, workgroups of 64 threads with max_nn * 512 bytes of LDS; no barrier, no atomics; every loop is bounded by the
+ * tile count, max_nn or the sweep count.  C <= 65535, P < 2^31 - 64.  1 launch. */
+int mvt_normals_estimate(const float* xyz, int C, long long P, int grid_w, int grid_h, int max_nn, float radius, const float* tile_box,
+                         const float* group_box, const float* viewpoint, float* nrm, int* nbr_idx, int* nbr_cnt, double* cov,
+                         void* stream);
+
+/* Voxel downsampling of ONE cloud xyz [P][4], 0 < P < 2^31 (Open3D voxel_down_sample), three entries with no host read between:
+ *   mvt_voxel_bounds -> mvt_voxel_insert -> mvt_voxel_emit
+ * state: MVT_VOXEL_STATE_WORDS 64-bit words on the device, doubles and integers as named below. */
+#define MVT_VOXEL_RANGE 1        /* status bit: a cell index >= 2^21 on some axis; nothing is emitted */
+#define MVT_VOXEL_FULL 2         /* status bit: the table had no slot left for a cell; nothing is emitted */
+#define MVT_VOXEL_ORIGIN 0       /* 3 doubles */
+#define MVT_VOXEL_SIZE 3         /* double: the voxel size */
+#define MVT_VOXEL_STATUS 4       /* int64: MVT_VOXEL_* bits */
+#define MVT_VOXEL_POINTS 5       /* int64: points taking part */
+#define MVT_VOXEL_STATE_WORDS 8
+#define MVT_VOXEL_BOUND_BLOCKS 1024
+#define MVT_VOXEL_SLOT_WORDS 6   /* 64-bit words per slot of the table: key, three sums, count / first, row / spare */
+/* lo = the per-axis minimum of the points taking part (finite coordinates), origin = lo - voxel / 2 in fp64; the status is
+ * cleared.  voxel finite and > 0.  partial: workspace of MVT_VOXEL_BOUND_BLOCKS * 4 doubles.  2 launches. */
+int mvt_voxel_bounds(const float* xyz, long long P, double voxel, double* partial, long long* state, void* stream);
+/* The hash grid.  u = ((double)p - origin) / voxel (a division, as in Open3D), cell = floor(u); the key is the three 21-bit cells
+ * packed into 64 bits.  table: capacity * MVT_VOXEL_SLOT_WORDS 64-bit words, capacity a power of two >= 2 P (cleared here).  A
+ * point claims its cell's slot with a 64-bit atomicCAS and linear probing bounded by the capacity: a failed swap returns the slot's
+ * key, which is its own or another cell's, and then it moves on -- nothing spins on another thread; no slot left sets
+ * MVT_VOXEL_FULL, a cell index >= 2^21 MVT_VOXEL_RANGE.  Per slot, integer atomics only: the count, first = the smallest input
+ * index, and three uint64 sums of rint((u - cell) 2^32) (P < 2^31 keeps them below 2^63), so no result depends on the order of
+ * arrival; which slot a cell gets does, but no output depends on that.  2 launches. */
+int mvt_voxel_insert(const float* xyz, long long P, long long* state, long long* table, long long capacity, void* stream);
+/* One row per occupied cell, in ascending order of `first` (a voxel appears where its first point appeared):
+ * points [Mv][4] = origin + (cell + sum / (count 2^32)) voxel per axis in fp64, rounded to fp32 once, .w = 0; counts [Mv];
+ * first [Mv]; *n_out = Mv; labels (optional) [P] = the output row of every input point, -1 for a point that takes no part.
+ * The outputs need room for as many rows as points take part (at most P).  With a status bit set *n_out = 0, no row is written and
+ * every label is -1.  block_counts: workspace of ceil(P / 256) int32.  Count, scan, scatter as mvt_query_pool, then the labels:
+ * 3 or 4 launches. */
+int mvt_voxel_emit(const float* xyz, long long P, const long long* state, long long* table, long long capacity, int* block_counts,
+                   float* points, int* counts, int* first, int* labels, int* n_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,13 +1,14 @@
 """MI355X-native multi-view point-tracking forward path (drop-in for mvtracker.models' predictor).
 
-    from mvtracker_amd import MVTracker, EvaluationPredictor, load_mvtracker, sample_queries, auto_scene_normalization, DepthCleaning, clean_depths, CameraAlignment, align_cameras
+    from mvtracker_amd import MVTracker, EvaluationPredictor, load_mvtracker, sample_queries, auto_scene_normalization, DepthCleaning, clean_depths, CameraAlignment, align_cameras, estimate_normals, voxel_downsample
 
 ``synth`` (numpy only) can be imported without the HIP library; everything else loads
 libmvtracker_hip.so on import and raises if it is missing -- there is no CPU fallback.
 """
 __all__ = ["MVTracker", "EvaluationPredictor", "load_mvtracker", "hip", "synth", "sample_io", "adapter", "geometry", "parallel", "queries",
            "sample_queries", "kmeans_centres", "DEFAULT_SPEC", "scene", "SceneTransform", "auto_scene_normalization", "clean", "DepthCleaning", "clean_depths",
-           "clean_point_cloud", "align", "CameraAlignment", "CameraCorrection", "align_cameras", "align_point_clouds"]
+           "clean_point_cloud", "align", "CameraAlignment", "PcaCameraAlignment", "CameraCorrection", "align_cameras", "align_point_clouds", "cloud",
+           "estimate_normals", "voxel_downsample"]
 
 
 def __getattr__(name):
@@ -29,10 +30,13 @@ def __getattr__(name):
     if name in ("DepthCleaning", "clean_depths", "clean_point_cloud"):
         from . import clean
         return getattr(clean, name)
-    if name in ("CameraAlignment", "CameraCorrection", "align_cameras", "align_point_clouds"):
+    if name in ("CameraAlignment", "PcaCameraAlignment", "CameraCorrection", "align_cameras", "align_point_clouds"):
         from . import align
         return getattr(align, name)
-    if name in ("hip", "synth", "sample_io", "adapter", "geometry", "parallel", "queries", "scene", "clean", "align"):
+    if name in ("estimate_normals", "voxel_downsample"):
+        from . import cloud
+        return getattr(cloud, name)
+    if name in ("hip", "synth", "sample_io", "adapter", "geometry", "parallel", "queries", "scene", "clean", "align", "cloud"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

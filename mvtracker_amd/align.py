@@ -12,6 +12,8 @@ The reference does this with Open3D (conversions/droid/utils/optimization.py ``r
     extrs_fixed = c.apply(extrs)                                    # extrs @ inv(D_v)
     out = predictor(rgbs=..., depths=..., ..., camera_alignment=a)  # after depth cleaning, before normalisation and resize
     T, fitness, rmse = align_point_clouds(source, target, target_normals, 0.05, 30)   # registration_icp on point lists
+    T, fitness, rmse = align_point_clouds(source, target, None, 0.05, 30)             # the target's normals by PCA (cloud.py)
+    a = PcaCameraAlignment(max_distance=0.05, normal_radius=0.1)                      # PCA normals instead of the grid cross product
 """
 from __future__ import annotations
 
@@ -60,6 +62,22 @@ class CameraAlignment:
         return (f"CameraAlignment(max_distance={self.max_distance}, max_iterations={self.max_iterations}, sweeps={self.sweeps}, "
                 f"frames={self.frames}, anchor={self.anchor}, sample_stride={self.sample_stride}, normal_max_edge={self.normal_max_edge}, "
                 f"conf_thresh={self.conf_thresh})")
+
+
+class PcaCameraAlignment(CameraAlignment):
+    """A ``CameraAlignment`` whose target normals come from ``mvt_normals_estimate`` (a PCA over each point's ``normal_max_nn`` nearest
+    points within ``normal_radius``; None: ``max_distance``), the reference's estimate_normals, instead of the cross product of
+    grid neighbours: coarse or oblique views keep their normals.  ``normal_max_edge`` is unused."""
+
+    def __init__(self, max_distance=0.05, max_iterations=30, sweeps=2, frames=(0,), anchor=0, sample_stride=1, normal_max_edge=None,
+                 conf_thresh=None, normal_radius=None, normal_max_nn=30):
+        super().__init__(max_distance, max_iterations, sweeps, frames, anchor, sample_stride, normal_max_edge, conf_thresh)
+        from . import cloud
+        r = self.max_distance if normal_radius is None else normal_radius
+        self.normal_radius, self.normal_max_nn = cloud.check_normal_search(r, normal_max_nn)
+
+    def __repr__(self):
+        return f"Pca{super().__repr__()[:-1]}, normal_radius={self.normal_radius}, normal_max_nn={self.normal_max_nn})"
 
 
 def _check(alignment):
@@ -224,10 +242,21 @@ class ClipAlignment:
         self.nrm = torch.empty(V, F, P, 4, device=dev)
         self.box = torch.empty(V, F, nt, 8, device=dev)
         self.gbox = torch.empty(V, F, (nt + 63) // 64, 8, device=dev)
-        hip.align_normals(self.xyz, V * F, self.grid, a.normal_max_edge, self.nrm)
-        build_search(self.xyz, V * F, P, self.grid, self.box, self.gbox)
+        self.rebuild(self.xyz, V * F, self.nrm, self.box, self.gbox)
         self.D = _eye_rows(V, dev)
         self.results = torch.zeros(V, 4, dtype=torch.float64, device=dev)
+
+    def rebuild(self, xyz, n_clouds, nrm, box, gbox):
+        """Normals and boxes of clouds that have just been written: the grid cross product, then the boxes; for a
+        ``PcaCameraAlignment`` the boxes first, since the PCA's neighbour search walks them."""
+        a = self.alignment
+        if isinstance(a, PcaCameraAlignment):
+            from . import cloud
+            build_search(xyz, n_clouds, self.P, self.grid, box, gbox)
+            cloud.normals_of_clouds(xyz, n_clouds, self.P, self.grid, a.normal_radius, a.normal_max_nn, nrm=nrm, box=box, gbox=gbox)
+        else:
+            hip.align_normals(xyz, n_clouds, self.grid, a.normal_max_edge, nrm)
+            build_search(xyz, n_clouds, self.P, self.grid, box, gbox)
 
     def targets(self, v):
         return [dict(xyz=self.xyz[u], nrm=self.nrm[u], box=self.box[u], gbox=self.gbox[u], P=self.P, grid=self.grid) for u in range(self.V) if u != v]
@@ -239,8 +268,7 @@ class ClipAlignment:
 
     def commit(self, v):
         hip.align_transform(self.xyz0[v], self.D[v], self.F * self.P, self.xyz[v])  # the view as it stands now, for the views that follow
-        hip.align_normals(self.xyz[v], self.F, self.grid, self.alignment.normal_max_edge, self.nrm[v])
-        build_search(self.xyz[v], self.F, self.P, self.grid, self.box[v], self.gbox[v])
+        self.rebuild(self.xyz[v], self.F, self.nrm[v], self.box[v], self.gbox[v])
 
     def run(self):
         for _ in range(self.alignment.sweeps):
@@ -287,21 +315,27 @@ def _list_cloud(points, what):
     return out
 
 
-def list_problem(source, target, target_normals, max_distance, max_iterations, init=None, keep_queries=False):
+def list_problem(source, target, target_normals, max_distance, max_iterations, init=None, keep_queries=False, normal_radius=0.05,
+                 normal_max_nn=30):
     """The ``IcpRun`` of ``align_point_clouds`` (point lists: linear tiles)."""
+    from . import cloud
     if not (math.isfinite(float(max_distance)) and float(max_distance) > 0.0):
         raise ValueError(f"max_distance must be finite and positive, got {max_distance!r}")
     if int(max_iterations) != max_iterations or not 1 <= int(max_iterations) <= 1000:
         raise ValueError(f"max_iterations must be an integer in 1..1000, got {max_iterations!r}")
     src = _list_cloud(source, "source")
     tgt = _list_cloud(target, "target")
-    if tuple(target_normals.shape) != tuple(target.shape):
+    if target_normals is None:
+        cloud.check_normal_search(normal_radius, normal_max_nn)
+    elif tuple(target_normals.shape) != tuple(target.shape):
         raise ValueError(f"target_normals must have the shape of target, got {tuple(target_normals.shape)}")
     if init is not None and tuple(init.shape) != (4, 4):
         raise ValueError(f"init must be (4, 4), got {tuple(init.shape)}")
     hip.require_device(source)
     dev = source.device
     M, N = source.shape[0], target.shape[0]
+    if target_normals is None:
+        target_normals = cloud.estimate_normals(target, normal_radius, normal_max_nn)
     nrm = _list_cloud(target_normals, "target_normals")
     nt = (N + 63) // 64
     box = torch.empty(1, nt, 8, device=dev)
@@ -313,12 +347,13 @@ def list_problem(source, target, target_normals, max_distance, max_iterations, i
 
 
 @hip.guarded
-def align_point_clouds(source, target, target_normals, max_distance, max_iterations, init=None):
+def align_point_clouds(source, target, target_normals, max_distance, max_iterations, init=None, *, normal_radius=0.05, normal_max_nn=30):
     """Open3D's ``registration_icp(source, target, max_distance, init, TransformationEstimationPointToPlane(),
     ICPConvergenceCriteria(max_iteration=max_iterations))`` on point lists: source (M,3), target (N,3) with normals (N,3), all on the
     device; rows that are not finite (and target rows without a finite normal) take no part.  Returns ``(transform, fitness, rmse)``:
-    the 4x4 fp64 transform on the device that moves the source onto the target, and Open3D's two figures for it."""
-    run = list_problem(source, target, target_normals, max_distance, max_iterations, init)
+    the 4x4 fp64 transform on the device that moves the source onto the target, and Open3D's two figures for it.
+    ``target_normals=None``: they are ``estimate_normals(target, normal_radius, normal_max_nn)``, the reference's preparation."""
+    run = list_problem(source, target, target_normals, max_distance, max_iterations, init, normal_radius=normal_radius, normal_max_nn=normal_max_nn)
     run.run()
     fitness, rmse = run.result[:2].tolist()
     return _to44(run.D), fitness, rmse

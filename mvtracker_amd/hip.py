@@ -124,6 +124,10 @@ SIGNATURES = {
     "mvt_align_queries": [LL, I, I, I, P],
     "mvt_align_correspond": [P, LL, I, I, I, I, P, F, P, I, P, P, P, P, P],
     "mvt_align_solve": [P, LL, P, I, I, P, P, P, P, P, P],
+    "mvt_normals_estimate": [P, I, LL, I, I, I, F, P, P, P, P, P, P, P, P],
+    "mvt_voxel_bounds": [P, LL, C.c_double, P, P, P],
+    "mvt_voxel_insert": [P, LL, P, P, LL, P],
+    "mvt_voxel_emit": [P, LL, P, P, LL, P, P, P, P, P, P, P],
 }
 _RET = {"mvt_build_arch": C.c_char_p, "mvt_encoder_workspace_bytes": C.c_longlong, "mvt_updateformer_workspace_bytes": C.c_longlong,
         "mvt_updateformer_grouped_workspace_bytes": C.c_longlong}
@@ -1030,3 +1034,59 @@ def align_solve(partial, n_rows, n_queries, final_call, D, istate, hist, result,
     assert sums is None or (sums.dtype == torch.float64 and sums.numel() >= ALIGN_ROW)
     _call("mvt_align_solve", _ptr(partial), n_rows, _ptr(n_queries), int(final_call), hist.numel() // ALIGN_HIST, _ptr(D), _ptr(istate), _ptr(hist),
           _ptr(sums), _ptr(result), _stream())
+
+
+# ------------------------------------------------------------------ cloud preparation (mvtracker_amd/cloud.py drives these)
+NORMALS_MAX_NN = 64  # MVT_NORMALS_MAX_NN
+VOXEL_RANGE, VOXEL_FULL = 1, 2  # MVT_VOXEL_* status bits
+VOXEL_ORIGIN, VOXEL_SIZE, VOXEL_STATUS, VOXEL_POINTS, VOXEL_STATE_WORDS, VOXEL_BOUND_BLOCKS, VOXEL_SLOT_WORDS = 0, 3, 4, 5, 8, 1024, 6
+
+
+def normals_estimate(xyz, Cn, Pn, grid, max_nn, radius, box, gbox, nrm, viewpoint=None, nbr_idx=None, nbr_cnt=None, cov=None):
+    """nrm (Cn, Pn, 4) <- PCA normals of the Cn clouds xyz (Cn, Pn, 4) over the max_nn nearest points within radius (NaN rows where
+    there is none).  box / gbox from tile_aabb / tile_group_aabb; viewpoint (Cn, 3) fp32 or None; optional nbr_idx (Cn, Pn, max_nn)
+    int32, nbr_cnt (Cn, Pn) int32, cov (Cn, Pn, 6) fp64."""
+    nt = (Pn + 63) // 64
+    assert xyz.dtype == nrm.dtype == torch.float32 and xyz.is_contiguous() and nrm.is_contiguous()
+    assert xyz.numel() >= Cn * Pn * 4 and nrm.numel() >= Cn * Pn * 4
+    assert box.dtype == torch.float32 and box.numel() >= Cn * nt * 8 and gbox.dtype == torch.float32 and gbox.numel() >= Cn * ((nt + 63) // 64) * 8
+    assert viewpoint is None or (viewpoint.dtype == torch.float32 and viewpoint.is_contiguous() and viewpoint.numel() >= Cn * 3)
+    assert nbr_idx is None or (nbr_idx.dtype == torch.int32 and nbr_idx.is_contiguous() and nbr_idx.numel() >= Cn * Pn * max_nn)
+    assert nbr_cnt is None or (nbr_cnt.dtype == torch.int32 and nbr_cnt.numel() >= Cn * Pn)
+    assert cov is None or (cov.dtype == torch.float64 and cov.is_contiguous() and cov.numel() >= Cn * Pn * 6)
+    _call("mvt_normals_estimate", _ptr(xyz), Cn, Pn, grid[0], grid[1], max_nn, radius, _ptr(box), _ptr(gbox), _ptr(viewpoint), _ptr(nrm),
+          _ptr(nbr_idx), _ptr(nbr_cnt), _ptr(cov), _stream())
+
+
+def voxel_capacity(Pn):
+    """Slots of the hash table of a cloud of Pn points: the power of two >= 2 Pn."""
+    return 1 << max(1, (2 * Pn - 1).bit_length())
+
+
+def _voxel_check(xyz, Pn, state, table=None, capacity=0):
+    assert xyz.dtype == torch.float32 and xyz.is_contiguous() and xyz.numel() >= Pn * 4
+    assert state.dtype == torch.int64 and state.numel() >= VOXEL_STATE_WORDS
+    assert table is None or (table.dtype == torch.int64 and table.is_contiguous() and table.numel() >= capacity * VOXEL_SLOT_WORDS)
+
+
+def voxel_bounds(xyz, Pn, voxel, partial, state):
+    """state <- origin = (minimum of the points taking part) - voxel / 2, the voxel size, a clear status, the points taking part."""
+    _voxel_check(xyz, Pn, state)
+    assert partial.dtype == torch.float64 and partial.numel() >= VOXEL_BOUND_BLOCKS * 4
+    _call("mvt_voxel_bounds", _ptr(xyz), Pn, float(voxel), _ptr(partial), _ptr(state), _stream())
+
+
+def voxel_insert(xyz, Pn, state, table, capacity):
+    """table (capacity * VOXEL_SLOT_WORDS int64 words) <- per cell the count, the first index and the fixed-point offset sums."""
+    _voxel_check(xyz, Pn, state, table, capacity)
+    _call("mvt_voxel_insert", _ptr(xyz), Pn, _ptr(state), _ptr(table), capacity, _stream())
+
+
+def voxel_emit(xyz, Pn, state, table, capacity, block_counts, points, counts, first, n_out, labels=None):
+    """points (>= Mv, 4) fp32, counts / first (>= Mv) int32, n_out (1,) int32 = Mv, labels (Pn,) int32 or None."""
+    _voxel_check(xyz, Pn, state, table, capacity)
+    assert block_counts.dtype == torch.int32 and block_counts.numel() >= (Pn + 255) // 256
+    assert points.dtype == torch.float32 and points.is_contiguous() and counts.dtype == first.dtype == n_out.dtype == torch.int32
+    assert labels is None or (labels.dtype == torch.int32 and labels.numel() >= Pn)
+    _call("mvt_voxel_emit", _ptr(xyz), Pn, _ptr(state), _ptr(table), capacity, _ptr(block_counts), _ptr(points), _ptr(counts), _ptr(first),
+          _ptr(labels), _ptr(n_out), _stream())
