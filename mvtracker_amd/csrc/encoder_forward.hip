@@ -12,6 +12,7 @@ inline long long align256(long long b) { return (b + 255) & ~255LL; }
 
 struct Plan {
   long long stem, z0, y, s[4], d, cat, c2, part, st, total;  // byte offsets
+  long long st_ch;                                           // channels a statistics table / a partials slot is sized for
 };
 
 // workspace: bf16 activations + statistics scratch.  stem / z0 / y: one 64-channel map at H/2 each (the largest activation);
@@ -38,9 +39,11 @@ inline Plan plan(long long n, int H, int W, int C) {
   P.cat = take(n * hs * ws * 416 * 2);
   P.c2 = take(n * hs * ws * 2 * C * 2);
   // statistics: per conv n * slots * Cout * 2 floats, slots <= tiles of the H/2 map
+  // (the widest conv is conv2 with 2C channels -- more than the stages' 2 x 128 of a folded launch once latent_dim > 128)
   const long long slots_max = ((h2 + 7) / 8) * ((w2 + 31) / 32);
-  P.part = take(n * slots_max * 256 * 2 * 4);
-  P.st = take(8 * n * 256 * 2 * 4);                // up to 8 live (mean, rstd) tables
+  P.st_ch = 2 * C > 256 ? 2 * C : 256;
+  P.part = take(n * slots_max * P.st_ch * 2 * 4);
+  P.st = take(8 * n * P.st_ch * 2 * 4);            // up to 8 live (mean, rstd) tables
   P.total = o;
   return P;
 }
@@ -76,7 +79,7 @@ static int encoder_run(const mvt_encoder_weights* w, const float* x4, const void
   char* base = (char*)workspace;
   float* part = (float*)(base + P.part);
   float* stb = (float*)(base + P.st);
-  const long long st_stride = (long long)n * 256 * 2;
+  const long long st_stride = (long long)n * P.st_ch * 2;
   int st_next = 0;
   auto new_st = [&]() { float* s = stb + (st_next % 8) * st_stride; ++st_next; return s; };
   const int BF = MVT_IO_IN_BF16 | MVT_IO_OUT_BF16;
