@@ -2,7 +2,8 @@
 // (SURVEY.md section 8b).  No kernels of its own: it sequences the library's bf16 kernels -- row-tile convolutions with the
 // InstanceNorm statistics taken in their epilogues and InstanceNorm + ReLU of the producer applied while a consumer loads its
 // patch, the per-tile statistics reduction, the residual InstanceNorm pass, the one-launch concat -- on the caller's stream over a
-// caller-provided workspace.  bf16 mode, bf16 activations (the configuration bench.py measures).  56 launches per call.
+// caller-provided workspace.  bf16 mode, bf16 activations (the configuration bench.py measures).  56 launches per call; beside
+// the tracking windows the half-resolution layers run a few images at a time (group_size below): 12 launches per further group.
 #include "common.h"
 #include <stdlib.h>
 
@@ -48,6 +49,25 @@ inline Plan plan(long long n, int H, int W, int C) {
   return P;
 }
 
+// Images per group of the half-resolution section (encoder_run): g = budget / live bytes per image, the live set being three
+// H/2 maps (skip, y, z).  Measured ("cache-sized image groups"): a call that has the chip to itself gains
+// nothing from groups -- its kernels take the same time with their maps resident, and every group adds launches -- so it makes
+// one pass; the calls marked short_workgroups run beside the tracking windows, and there groups of about 72 MiB shorten the
+// step.  A budget below one image's live set means one pass too.  MVT_ENC_GROUP=N forces groups of N images for every call
+// (unset or 0: the rule); read on every call (A/B runs, tests).  -> g in [1, n]; g == n is the single pass.
+constexpr long long GROUP_BUDGET_SHARED = 80LL << 20;
+inline int group_size(int n, int h2, int w2, int shared, int* g_out) {
+  long long g = shared ? GROUP_BUDGET_SHARED / (3LL * h2 * w2 * 64 * 2) : n;
+  if (g < 1) g = n;
+  if (const char* e = getenv("MVT_ENC_GROUP")) {
+    const long v = strtol(e, nullptr, 10);
+    if (v < 0) return MVT_ERR_ARG;
+    if (v > 0) g = v;
+  }
+  *g_out = (int)(g > n ? n : g);
+  return MVT_OK;
+}
+
 }  // namespace
 
 extern "C" long long mvt_encoder_workspace_bytes(int n, int H, int W, int C) {
@@ -83,93 +103,120 @@ static int encoder_run(const mvt_encoder_weights* w, const float* x4, const void
   int st_next = 0;
   auto new_st = [&]() { float* s = stb + (st_next % 8) * st_stride; ++st_next; return s; };
   const int BF = MVT_IO_IN_BF16 | MVT_IO_OUT_BF16;
+  const int h2 = H / 2, w2 = W / 2;
+  int g = n;
+  ENC_TRY(group_size(n, h2, w2, w->short_workgroups, &g));
 
-  // one convolution + the (mean, rstd) of its output
+  // The launches below act on images [ga, ga + gn) of the call.  Every buffer keeps the whole call's layout -- image i owns slice
+  // i of each activation buffer, of the partial sums of a launch and of a (mean, rstd) table -- so a group is the same launch
+  // with its pointers advanced by ga images and gn in place of n; (0, n) is the plain single pass.
+  int ga = 0, gn = n;
+  auto img = [&](const void* p, long long bytes_per_image) { return (char*)p + ga * bytes_per_image; };
+  auto rows_of = [&](const float* table, int ch) { return table ? table + (long long)ga * ch * 2 : nullptr; };
+
+  // one convolution + the (mean, rstd) of its output; *st_out is the whole call's table
   auto conv = [&](int ci, const void* in, int io_in, void* out, int hh, int ww, int cin, int cout, int k, int stride, int pad, int ld_out,
                   const float* in_stats, float** st_out, int io_out) -> int {
     const mvt_conv_weights& cw = w->conv[ci];
     const int ho = (hh + 2 * pad - k) / stride + 1, wo = (ww + 2 * pad - k) / stride + 1;
+    const long long in_img = (long long)hh * ww * cin * (io_in & MVT_IO_IN_BF16 ? 2 : 4);
+    const long long out_img = (long long)ho * wo * ld_out * (io_out & MVT_IO_OUT_BF16 ? 2 : 4);
     float* pp = nullptr;
     int slots = 0;
     if (st_out) {
       slots = mvt_conv2d_stat_slots(hh, ww, cin, k, k, stride, pad, 0);
       MVT_REQUIRE(slots > 0);
-      pp = part;
+      pp = part + (long long)ga * slots * cout * 2;
     }
-    ENC_TRY(mvt_conv2d_bf16(in, cw.w, nullptr, cw.b, out, n, hh, ww, cin, cout, k, k, stride, pad, ld_out, MVT_ACT_NONE,
-                            io_in | io_out | (w->short_workgroups ? MVT_IO_SHORT_WG : 0), in_stats, pp, stream));
+    ENC_TRY(mvt_conv2d_bf16(img(in, in_img), cw.w, nullptr, cw.b, img(out, out_img), gn, hh, ww, cin, cout, k, k, stride, pad, ld_out,
+                            MVT_ACT_NONE, io_in | io_out | (w->short_workgroups ? MVT_IO_SHORT_WG : 0), rows_of(in_stats, cin), pp, stream));
     if (st_out) {
       *st_out = new_st();
-      ENC_TRY(mvt_instnorm_finish_slots(pp, slots, *st_out, n, (long long)ho * wo, cout, stream));
+      ENC_TRY(mvt_instnorm_finish_slots(pp, slots, (float*)rows_of(*st_out, cout), gn, (long long)ho * wo, cout, stream));
     }
     return MVT_OK;
   };
 
   // stem: 7x7 / 2, its InstanceNorm + ReLU is applied by its two consumers (conv1 of layer1.0 and that block's skip)
-  const int h2 = H / 2, w2 = W / 2;
-  float* st_stem = nullptr;
-  if (x4) {
-    ENC_TRY(conv(0, x4, 0, base + P.stem, H, W, 4, 64, 7, 2, 3, 64, nullptr, &st_stem, MVT_IO_OUT_BF16));
-  } else {
+  auto stem = [&](float** st_stem) -> int {
+    if (x4) return conv(0, x4, 0, base + P.stem, H, W, 4, 64, 7, 2, 3, 64, nullptr, st_stem, MVT_IO_OUT_BF16);
     // the stem reads the clip's planar frames itself (normalisation on load): no [n][H][W][4] staging tensor, one launch less
     const mvt_conv_weights& cw = w->conv[0];
     const int slots = mvt_detail_conv_rows_slots(h2, w2, mvt_detail_conv_rows_tile_rows(7, 2, h2));
+    float* pp = part + (long long)ga * slots * 64 * 2;
     // (weight rows as mvt_conv2d_bf16 takes them: [64][round_up(7 * 32, 64)])
-    ENC_TRY(mvt_detail_stem7x7_rows_src(nullptr, rgb, rgb_u8, rgb_V, rgb_T, img0, cw.w, (7 * 32 + 63) & ~63, cw.b, base + P.stem, n, H, W, 64, 64,
-                                        MVT_IO_OUT_BF16, part, mvt_stream(stream)));
-    st_stem = new_st();
-    ENC_TRY(mvt_instnorm_finish_slots(part, slots, st_stem, n, (long long)h2 * w2, 64, stream));
-  }
+    ENC_TRY(mvt_detail_stem7x7_rows_src(nullptr, rgb, rgb_u8, rgb_V, rgb_T, img0 + ga, cw.w, (7 * 32 + 63) & ~63, cw.b,
+                                        img(base + P.stem, (long long)h2 * w2 * 64 * 2), gn, H, W, 64, 64, MVT_IO_OUT_BF16, pp, mvt_stream(stream)));
+    *st_stem = new_st();
+    return mvt_instnorm_finish_slots(pp, slots, (float*)rows_of(*st_stem, 64), gn, (long long)h2 * w2, 64, stream);
+  };
 
   // ResidualBlock (blocks.py:84-128): conv1 -> IN -> ReLU -> conv2 -> IN -> ReLU, + (downsampled, normalised) input, ReLU
   auto res_block = [&](int c1, int c2, int cd, const void* xin, const float* x_stats, int hh, int ww, int cin, int cout, int stride,
                        void* zout) -> int {
     const int ho = (hh + 2 - 3) / stride + 1, wo = (ww + 2 - 3) / stride + 1;
+    const long long in_img = (long long)hh * ww * cin * 2, out_img = (long long)ho * wo * cout * 2;
     float *s1 = nullptr, *s2 = nullptr, *sd = nullptr;
     static const bool no_fold = getenv("MVT_FOLD_DOWNSAMPLE") && atoi(getenv("MVT_FOLD_DOWNSAMPLE")) == 0;  // (A/B runs)
     const bool fold = cd >= 0 && stride == 2 && !x_stats && cout % 32 == 0 && !no_fold;  // conv1 + downsample[0] read the same x: one launch
     if (fold) {
       const int slots = mvt_conv2d_stat_slots(hh, ww, cin, 3, 3, 2, 1, 0);
       MVT_REQUIRE(slots > 0);
-      float* part_d = part + (long long)n * slots * cout * 2;  // (the partials buffer is sized for the stem: room for both)
-      ENC_TRY(mvt_conv3x3s2_down_bf16(xin, w->conv[c1].w, w->conv[c1].b, w->conv[cd].w, w->conv[cd].b, base + P.y, base + P.d, n, hh, ww, cin,
-                                      cout, cout, part, part_d, stream));
+      float* part_3 = part + (long long)ga * slots * cout * 2;
+      float* part_d = part_3 + (long long)n * slots * cout * 2;  // (the partials buffer is sized for the stem: room for both)
+      ENC_TRY(mvt_conv3x3s2_down_bf16(img(xin, in_img), w->conv[c1].w, w->conv[c1].b, w->conv[cd].w, w->conv[cd].b, img(base + P.y, out_img),
+                                      img(base + P.d, out_img), gn, hh, ww, cin, cout, cout, part_3, part_d, stream));
       s1 = new_st();
-      ENC_TRY(mvt_instnorm_finish_slots(part, slots, s1, n, (long long)ho * wo, cout, stream));
+      ENC_TRY(mvt_instnorm_finish_slots(part_3, slots, (float*)rows_of(s1, cout), gn, (long long)ho * wo, cout, stream));
       sd = new_st();
-      ENC_TRY(mvt_instnorm_finish_slots(part_d, slots, sd, n, (long long)ho * wo, cout, stream));
+      ENC_TRY(mvt_instnorm_finish_slots(part_d, slots, (float*)rows_of(sd, cout), gn, (long long)ho * wo, cout, stream));
     } else {
       ENC_TRY(conv(c1, xin, MVT_IO_IN_BF16, base + P.y, hh, ww, cin, cout, 3, stride, 1, cout, x_stats, &s1, MVT_IO_OUT_BF16));
     }
     ENC_TRY(conv(c2, base + P.y, MVT_IO_IN_BF16, zout, ho, wo, cout, cout, 3, 1, 1, cout, s1, &s2, MVT_IO_OUT_BF16));
     const void* skip = xin;
+    long long skip_img = in_img;
     const float* skip_stats = x_stats;
     int flags = BF | (x_stats ? MVT_APPLY_SKIP_RELU : 0);
     if (cd >= 0) {
       if (!fold) ENC_TRY(conv(cd, xin, MVT_IO_IN_BF16, base + P.d, hh, ww, cin, cout, 1, stride, 0, cout, nullptr, &sd, MVT_IO_OUT_BF16));
       skip = base + P.d;
+      skip_img = out_img;
       skip_stats = sd;
       flags = BF;
     }
-    return mvt_instnorm_apply(zout, s2, skip, skip_stats, zout, n, (long long)ho * wo, cout, flags, stream);
+    return mvt_instnorm_apply(img(zout, out_img), rows_of(s2, cout), img(skip, skip_img), rows_of(skip_stats, cout), img(zout, out_img), gn,
+                              (long long)ho * wo, cout, flags, stream);
   };
 
   // conv indices: 0 stem; layer l (1..4): 1 + 5 (l - 1) + {0: .0.conv1, 1: .0.conv2, 2: .0.downsample, 3: .1.conv1, 4: .1.conv2};
   // 21: conv2 (3x3, 416 -> 2C); 22: conv3 (1x1, 2C -> C)
-  const void* stage[4];
-  int sh[4], sw[4], sc[4];
-  const void* xin = base + P.stem;
-  const float* xst = st_stem;
-  int hh = h2, ww = w2, cin = 64;
   const int couts[4] = {64, 96, 128, 128}, strides[4] = {1, 2, 2, 2};
-  for (int l = 0; l < 4; ++l) {
+  auto layer = [&](int l, const void* xin, const float* xst, int hh, int ww, int cin) -> int {
     const int b0 = 1 + 5 * l, cout = couts[l], stride = strides[l];
     ENC_TRY(res_block(b0, b0 + 1, l == 0 ? -1 : b0 + 2, xin, xst, hh, ww, cin, cout, stride, base + P.z0));
     hh = (hh + 2 - 3) / stride + 1;
     ww = (ww + 2 - 3) / stride + 1;
-    ENC_TRY(res_block(b0 + 3, b0 + 4, -1, base + P.z0, nullptr, hh, ww, cout, cout, 1, base + P.s[l]));
-    stage[l] = base + P.s[l]; sh[l] = hh; sw[l] = ww; sc[l] = cout;
-    xin = base + P.s[l]; xst = nullptr; cin = cout;
+    return res_block(b0 + 3, b0 + 4, -1, base + P.z0, nullptr, hh, ww, cout, cout, 1, base + P.s[l]);
+  };
+
+  // The half-resolution section (stem and layer 1, the largest maps of the network) in groups of g images, up to where s[0] is
+  // complete.  A group reads and writes its own images' slices only.  The ring position is rewound for every group: each fills
+  // its images' rows of the same five tables an ungrouped call uses, so no group overwrites a row another group's consumer still
+  // has to read, and the tables of the later stages land where they always did.
+  for (ga = 0; ga < n; ga += g) {
+    gn = n - ga < g ? n - ga : g;
+    st_next = 0;
+    float* st_stem = nullptr;
+    ENC_TRY(stem(&st_stem));
+    ENC_TRY(layer(0, base + P.stem, st_stem, h2, w2, 64));
+  }
+  ga = 0, gn = n;
+  const void* stage[4] = {base + P.s[0]};
+  int sh[4] = {h2}, sw[4] = {w2}, sc[4] = {64};
+  for (int l = 1; l < 4; ++l) {
+    ENC_TRY(layer(l, base + P.s[l - 1], nullptr, sh[l - 1], sw[l - 1], sc[l - 1]));
+    stage[l] = base + P.s[l]; sh[l] = (sh[l - 1] - 1) / 2 + 1; sw[l] = (sw[l - 1] - 1) / 2 + 1; sc[l] = couts[l];
   }
   const int hs = H / 4, ws = W / 4;
   ENC_TRY(mvt_concat_resize_bilinear_ac(4, stage, sh, sw, sc, base + P.cat, n, hs, ws, 416, BF, stream));
