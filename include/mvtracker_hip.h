@@ -297,9 +297,16 @@ int mvt_unproject(const float* depth_s, const float* kinv, const float* einv, fl
  * kNN + correlation (reference: knn / PointcloudCorrBlock.corr_sample, mvtracker.py:26-90,
  * 800-846; feature init 1-NN, mvtracker.py:627-643).
  * --------------------------------------------------------------------------------------------- */
-/* Exact brute-force kNN.  For every (query n, slot s): candidates are the P points of frame
- * frame_of_slot = clamp(frame0 + s*frame_step, 0, T-1) of xyz [T][P][4] (frame_step may be negative:
- * the time-reversed pass of backward tracking runs its slots downwards and repeats frame 0); query = coords[(n*S+s)*3..].
+/* THE FRAME RULE of every entry below that takes `int base, int R, int lo, int hi` (the entries that map a window slot to a frame of
+ * the frame store).  The store tensors -- xyz [R][P][4], fvec [R][P][C], tile_box / group_box [R][..][8] -- hold R frame slots; frame
+ * f lives in slot (f - base) mod R and frames [lo, hi] are resident (0 <= base <= lo <= hi, hi - lo < R).  Slot s of a window reads
+ *   frame_of_slot = clamp(frame0 + s*frame_step, lo, hi)
+ * (frame_step may be negative: the time-reversed pass of backward tracking runs its slots downwards and repeats frame lo; hi = the
+ * last frame received is the repeat-last-frame padding at the clip's end).  frame0 itself must be resident; anything else is refused
+ * (MVT_ERR_ARG).  A linear store of T frames, the whole clip on the device, is (base, R, lo, hi) = (0, T, 0, T-1): slot = frame.
+ * A ring (streaming: device memory independent of the clip length) and a linear store that hold the same frames give the same bits.
+ *
+ * Exact brute-force kNN.  For every (query n, slot s): candidates are the P points of frame_of_slot; query = coords[(n*S+s)*3..].
  * d2 = fma(dz,dz,fma(dy,dy,dx*dx)), neighbours ascending by (d2, index).  The candidate range
  * is cut into nseg segments scanned by different waves; keys [N][S][nseg][K] receive
  * (d2 bits << 32 | index) per segment, ascending (KEY_MAX = ~0 pads a segment that holds fewer than K
@@ -322,8 +329,8 @@ int mvt_tile_aabb(const float* xyz, long long P, int T, int grid_w, int grid_h,
  * (same record layout).  Used by the single-segment searches below (clouds of 65..4096 tiles), which test the group boxes first
  * and skip whole runs of tiles; exactness is unaffected (a group box contains its tiles' boxes). */
 int mvt_tile_group_aabb(const float* box, long long P, int T, float* group_box, void* stream);
-int mvt_knn_scan(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step,
-                 int T, int K, int nseg, unsigned long long* keys, const int* seed_idx, int seed_k, int seed_cw,
+int mvt_knn_scan(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int base, int R,
+                 int lo, int hi, int K, int nseg, unsigned long long* keys, const int* seed_idx, int seed_k, int seed_cw,
                  int seed_ch, int seed_fw, int seed_fh, const float* tile_box, int grid_w, int grid_h, void* stream);
 /* Merge the nseg per-segment key lists of mvt_knn_scan: idx_out [N][S][K] int32 = the K nearest neighbour
  * indices, ascending by (d2, index); indices are clamped to [0, P) (only NaN queries can be out of range). */
@@ -333,15 +340,15 @@ int mvt_knn_merge(const unsigned long long* keys, int N, int S, int K, int nseg,
  * and its K neighbour indices go straight to idx_out [N][S][K] -- bit for bit the merged result of the two-launch form.  tile_box
  * required, group_box optional; seeds as in mvt_knn_scan (NULL: unseeded).  idx_out must not alias seed_idx when the seed comes
  * from another level (seed_cw > 0 reads other entries' indices only of the coarser tensor, never of idx_out). */
-int mvt_knn_search(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int T, int K,
-                   const int* seed_idx, int seed_k, int seed_cw, int seed_ch, int seed_fw, int seed_fh, const float* tile_box,
-                   const float* group_box, int grid_w, int grid_h, int* idx_out, void* stream);
+int mvt_knn_search(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int base, int R,
+                   int lo, int hi, int K, const int* seed_idx, int seed_k, int seed_cw, int seed_ch, int seed_fw, int seed_fh,
+                   const float* tile_box, const float* group_box, int grid_w, int grid_h, int* idx_out, void* stream);
 /* Scan / merge of several pyramid levels in ONE launch each (grid.y = level).  After the first refinement iteration every
  * level is seeded by its own previous neighbours (seed_idx [N][S][seed_k], same-level indices), so the scans are
  * independent; one launch removes three launch / tail latencies per iteration.  Semantics per level = mvt_knn_scan /
  * mvt_knn_merge.  seed_k == 0: unseeded (every seed_idx NULL). */
 typedef struct mvt_knn_level {
-  const float* xyz;         /* [T][P][4] */
+  const float* xyz;         /* [R][P][4] */
   long long P;
   unsigned long long* keys; /* [N][S][nseg][K] */
   const int* seed_idx;      /* [N][S][seed_k] or NULL */
@@ -351,7 +358,7 @@ typedef struct mvt_knn_level {
   const float* group_box;   /* from mvt_tile_group_aabb or NULL: coarse culling level of mvt_knn_search_levels */
 } mvt_knn_level;
 int mvt_knn_scan_levels(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
-                        int T, int K, int seed_k, void* stream);
+                        int base, int R, int lo, int hi, int K, int seed_k, void* stream);
 int mvt_knn_merge_levels(int levels, const mvt_knn_level* lv, int N, int S, int K, void* stream);
 /* Seeded scan + merge of all levels in ONE launch: every (track, slot) is searched by a single wave over the whole cloud
  * (tile boxes required; nseg and keys are ignored) and its K neighbour indices go straight to idx_out -- the result of
@@ -359,55 +366,28 @@ int mvt_knn_merge_levels(int levels, const mvt_knn_level* lv, int N, int S, int 
  * the seeds of its own entries before it writes them.  seed_k >= K, or seed_k == 0 with every seed_idx NULL: unseeded searches
  * (the initial threshold is the farthest-corner bound of the nearest tile with >= K finite points). */
 int mvt_knn_search_levels(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
-                          int T, int K, int seed_k, void* stream);
+                          int base, int R, int lo, int hi, int K, int seed_k, void* stream);
 /* Gather-dot correlation for `levels` pyramid levels in ONE launch (grid.y = level).  Host arrays of per-level
- * DEVICE pointers: xyz[l] [T][P_l][4], fvec[l] [T][P_l][C] (C in {32,64,128,256}, groups == 1), idx[l]
+ * DEVICE pointers: xyz[l] [R][P_l][4], fvec[l] [R][P_l][C] (C in {32,64,128,256}, groups == 1), idx[l]
  * [N][S][K] int32 from mvt_knn_merge, P[l].  For k < K:
  *   out[(n*S+s)*ldo + o_off + l*4K + 4k + {0,1,2,3}] = { <target, f_k>/sqrt(C), xyz_k - coord }
  * (mvtracker.py:827-842 with corr_add_neighbor_offset=True; the level-major concat of :374).  targets [N][S][C] fp32.
  * fvec_bf16: the feature rows are bf16 (256-B rows at C = 128; the dot accumulates in fp32). */
 int mvt_corr_gather_dot(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
-                        const int* const* idx, int C, const float* targets, const float* coords, int N, int S,
-                        int frame0, int frame_step, int T, int K, float* out, int ldo, int o_off, void* stream);
+                        const int* const* idx, int C, const float* targets, const float* coords, int N, int S, int frame0,
+                        int frame_step, int base, int R, int lo, int hi, int K, float* out, int ldo, int o_off, void* stream);
 /* The same operator with the reference's non-default correlation options (mvtracker.py:130-149, 832-846): `groups` grouped dots per
  * neighbour (each over C / groups channels, / sqrt(C / groups); a power of two dividing the lanes of a feature row), the neighbour
  * offset (add_offset) and / or the neighbour's coordinates (add_xyz) appended: OW = groups + 3 add_offset + 3 add_xyz values per
  * neighbour at out[(n*S+s)*ldo + o_off + (l*K + k)*OW ...]. */
 int mvt_corr_gather_dot_opts(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
                              const int* const* idx, int C, const float* targets, const float* coords, int N, int S, int frame0,
-                             int frame_step, int T, int K, int groups, int add_offset, int add_xyz, float* out, int ldo, int o_off,
-                             void* stream);
-/* 1-NN feature init: feat_out[n][C] (fp32) = fvec[frame][idx] with idx from keys [n][1][nseg][1]
- * (mvtracker.py:640-643); idx_out optional.  fvec_bf16: bf16 feature rows. */
+                             int frame_step, int base, int R, int lo, int hi, int K, int groups, int add_offset, int add_xyz,
+                             float* out, int ldo, int o_off, void* stream);
+/* 1-NN feature init: feat_out[n][C] (fp32) = fvec[slot of frame][idx] with idx from keys [n][1][nseg][1]
+ * (mvtracker.py:640-643); idx_out optional.  fvec_bf16: bf16 feature rows.  `frame` must be resident (the frame rule). */
 int mvt_knn1_gather(const void* fvec, int fvec_bf16, long long P, int C, const unsigned long long* keys, int n, int nseg,
-                    int frame, float* feat_out, int* idx_out, void* stream);
-
-/* Ring forms of the entries above that map a window slot to a store frame (streaming: device memory independent of the clip
- * length).  The store tensors -- xyz [R][P][4], fvec [R][P][C], tile_box / group_box [R][..][8] -- hold R frame slots; frame f
- * lives in slot (f - base) mod R and frames [lo, hi] are resident (base <= lo <= hi, hi - lo < R).  Slot s of a window reads frame
- *   clamp(frame0 + s*frame_step, lo, hi)
- * (hi = the last frame received: the repeat-last-frame padding at the clip's end), frame0 itself must be resident.  Everything else
- * -- arguments, results, tie rules -- is the linear entry's: on the same frames the two forms give the same bits. */
-int mvt_knn_scan_ring(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int base, int R,
-                      int lo, int hi, int K, int nseg, unsigned long long* keys, const int* seed_idx, int seed_k, int seed_cw,
-                      int seed_ch, int seed_fw, int seed_fh, const float* tile_box, int grid_w, int grid_h, void* stream);
-int mvt_knn_search_ring(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int base, int R,
-                        int lo, int hi, int K, const int* seed_idx, int seed_k, int seed_cw, int seed_ch, int seed_fw, int seed_fh,
-                        const float* tile_box, const float* group_box, int grid_w, int grid_h, int* idx_out, void* stream);
-int mvt_knn_scan_levels_ring(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
-                             int base, int R, int lo, int hi, int K, int seed_k, void* stream);
-int mvt_knn_search_levels_ring(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
-                               int base, int R, int lo, int hi, int K, int seed_k, void* stream);
-int mvt_corr_gather_dot_ring(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
-                             const int* const* idx, int C, const float* targets, const float* coords, int N, int S, int frame0,
-                             int frame_step, int base, int R, int lo, int hi, int K, float* out, int ldo, int o_off, void* stream);
-int mvt_corr_gather_dot_opts_ring(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
-                                  const int* const* idx, int C, const float* targets, const float* coords, int N, int S, int frame0,
-                                  int frame_step, int base, int R, int lo, int hi, int K, int groups, int add_offset, int add_xyz,
-                                  float* out, int ldo, int o_off, void* stream);
-/* mvt_knn1_gather of frame `frame` (resident: lo <= frame <= hi) of a ring store. */
-int mvt_knn1_gather_ring(const void* fvec, int fvec_bf16, long long P, int C, const unsigned long long* keys, int n, int nseg,
-                         int frame, int base, int R, int lo, int hi, float* feat_out, int* idx_out, void* stream);
+                    int frame, int base, int R, int lo, int hi, float* feat_out, int* idx_out, void* stream);
 
 /* Secondary operator: bilinear-window correlation (CorrBlock.corr_sample,
  * spatracker/blocks.py:492-533 + bilinear_sampler :604-619).  fmap_l channels-last

@@ -842,23 +842,63 @@ __global__ __launch_bounds__(256) void window_corr_levels_kernel(WinLevels lv, c
 
 }  // namespace
 
-// The FrameRing of a linear store of T frames, and of a ring store (frame f in slot (f - base) mod R, frames [lo, hi] resident):
-// false = arguments rejected.  frame0 must be a resident frame; every other slot is clamped into [lo, hi] by the kernels.
-static bool linear_frames(int T, int frame0, FrameRing* fr) {
-  if (T <= 0 || frame0 < 0 || frame0 >= T) return false;
-  *fr = FrameRing{0, T - 1, 0, T};
-  return true;
-}
-
+// The FrameRing of a frame store (the frame rule of include/mvtracker_hip.h: frame f in slot (f - base) mod R, frames [lo, hi]
+// resident; a linear store of T frames is (0, T, 0, T-1)): false = arguments rejected.  frame0 must be a resident frame; every
+// other slot is clamped into [lo, hi] by the kernels.
 static bool ring_frames(int base, int R, int lo, int hi, int frame0, FrameRing* fr) {
   if (R <= 0 || base < 0 || lo < base || hi < lo || hi - lo >= R || frame0 < lo || frame0 > hi) return false;
   *fr = FrameRing{lo, hi, base + (lo - base) / R * R, R};
   return true;
 }
 
+// Tiles of a cloud of P points: linear (grid_w = grid_h = 0) or 8x8 patches of per-view grids that make up the cloud.
+static bool tile_grid_ok(long long P, int grid_w, int grid_h) {
+  return (grid_w == 0 && grid_h == 0) ||
+         (grid_w > 0 && grid_h > 0 && grid_w % 8 == 0 && grid_h % 8 == 0 && P % ((long long)grid_w * grid_h) == 0);
+}
+
+// Queries per wave of the scans: 8 amortise the point loads of a brute-force scan; with boxes the scan is short and the per-query
+// selection work dominates, which spreads better over many small waves.  MVT_KNN_Q overrides the choice (1, 2, 4 or 8).
+static int knn_queries_per_wave(bool boxes) {
+  static const int q_env = getenv("MVT_KNN_Q") ? atoi(getenv("MVT_KNN_Q")) : 0;
+  return q_env ? q_env : (boxes ? 2 : 8);
+}
+
+// Launch KERNEL<Q> (256 threads, the entry's stream) for Q queries per wave; any other Q is refused.
+#define MVT_LAUNCH_Q1(KERNEL, QQ, GRID, ...) hipLaunchKernelGGL((KERNEL<QQ>), GRID, dim3(256), 0, mvt_stream(stream), __VA_ARGS__)
+#define MVT_LAUNCH_Q(KERNEL, Q, GRID, ...)                     \
+  switch (Q) {                                                 \
+    case 1: MVT_LAUNCH_Q1(KERNEL, 1, GRID, __VA_ARGS__); break; \
+    case 2: MVT_LAUNCH_Q1(KERNEL, 2, GRID, __VA_ARGS__); break; \
+    case 4: MVT_LAUNCH_Q1(KERNEL, 4, GRID, __VA_ARGS__); break; \
+    case 8: MVT_LAUNCH_Q1(KERNEL, 8, GRID, __VA_ARGS__); break; \
+    default: return MVT_ERR_ARG;                               \
+  }
+
+// Launch KERNEL<lanes per feature row, BF> for rows of C channels, bf16 (8 per lane) or fp32 (4 per lane); any other C is refused.
+#define MVT_LAUNCH_ROWS1(KERNEL, LPR, BF, GRID, ...) \
+  hipLaunchKernelGGL((KERNEL<LPR, BF>), GRID, dim3(256), 0, mvt_stream(stream), __VA_ARGS__)
+#define MVT_LAUNCH_ROWS(KERNEL, BF16, C, GRID, ...)                       \
+  if (BF16) {                                                             \
+    switch (C) {                                                          \
+      case 32: MVT_LAUNCH_ROWS1(KERNEL, 4, 1, GRID, __VA_ARGS__); break;   \
+      case 64: MVT_LAUNCH_ROWS1(KERNEL, 8, 1, GRID, __VA_ARGS__); break;   \
+      case 128: MVT_LAUNCH_ROWS1(KERNEL, 16, 1, GRID, __VA_ARGS__); break; \
+      case 256: MVT_LAUNCH_ROWS1(KERNEL, 32, 1, GRID, __VA_ARGS__); break; \
+      default: return MVT_ERR_ARG;                                        \
+    }                                                                     \
+  } else {                                                                \
+    switch (C) {                                                          \
+      case 32: MVT_LAUNCH_ROWS1(KERNEL, 8, 0, GRID, __VA_ARGS__); break;   \
+      case 64: MVT_LAUNCH_ROWS1(KERNEL, 16, 0, GRID, __VA_ARGS__); break;  \
+      case 128: MVT_LAUNCH_ROWS1(KERNEL, 32, 0, GRID, __VA_ARGS__); break; \
+      case 256: MVT_LAUNCH_ROWS1(KERNEL, 64, 0, GRID, __VA_ARGS__); break; \
+      default: return MVT_ERR_ARG;                                        \
+    }                                                                     \
+  }
+
 extern "C" int mvt_tile_aabb(const float* xyz, long long P, int T, int grid_w, int grid_h, float* box, void* stream) {
-  MVT_REQUIRE(xyz && box && P > 0 && T > 0 && P < (1LL << 31));
-  MVT_REQUIRE((grid_w == 0 && grid_h == 0) || (grid_w > 0 && grid_h > 0 && grid_w % 8 == 0 && grid_h % 8 == 0 && P % ((long long)grid_w * grid_h) == 0));
+  MVT_REQUIRE(xyz && box && P > 0 && T > 0 && P < (1LL << 31) && tile_grid_ok(P, grid_w, grid_h));
   const long long ntiles = (P + 63) / 64, total = ntiles * T;
   hipLaunchKernelGGL(tile_aabb_kernel, dim3((unsigned)mvt_cdiv(total, 4)), dim3(256), 0, mvt_stream(stream), xyz, P, ntiles, total, grid_w,
                      grid_h, box);
@@ -873,71 +913,56 @@ extern "C" int mvt_tile_group_aabb(const float* box, long long P, int T, float* 
   return mvt_launch_status();
 }
 
-static int knn_scan_launch(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, FrameRing fr, int K, int nseg,
-                           unsigned long long* keys, const int* seed_idx, int seed_k, int seed_cw, int seed_ch, int seed_fw, int seed_fh,
-                           const float* tile_box, int grid_w, int grid_h, int* idx_direct, const float* group_box, void* stream);
-
-extern "C" int mvt_knn_scan(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int T,
-                            int K, int nseg, unsigned long long* keys, const int* seed_idx, int seed_k, int seed_cw, int seed_ch,
-                            int seed_fw, int seed_fh, const float* tile_box, int grid_w, int grid_h, void* stream) {
+// mvt_knn_scan (keys, nseg segments) and mvt_knn_search (idx_direct, one segment): one kernel.
+static int knn_scan_launch(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int base, int R,
+                           int lo, int hi, int K, int nseg, unsigned long long* keys, const int* seed_idx, int seed_k, int seed_cw,
+                           int seed_ch, int seed_fw, int seed_fh, const float* tile_box, int grid_w, int grid_h, int* idx_direct,
+                           const float* group_box, void* stream) {
   FrameRing fr;
-  MVT_REQUIRE(keys && linear_frames(T, frame0, &fr));
-  return knn_scan_launch(xyz, P, coords, N, S, frame0, frame_step, fr, K, nseg, keys, seed_idx, seed_k, seed_cw, seed_ch, seed_fw, seed_fh,
-                         tile_box, grid_w, grid_h, nullptr, nullptr, stream);
-}
-
-extern "C" int mvt_knn_search(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int T, int K,
-                              const int* seed_idx, int seed_k, int seed_cw, int seed_ch, int seed_fw, int seed_fh, const float* tile_box,
-                              const float* group_box, int grid_w, int grid_h, int* idx_out, void* stream) {
-  FrameRing fr;
-  MVT_REQUIRE(idx_out && tile_box && linear_frames(T, frame0, &fr));
-  return knn_scan_launch(xyz, P, coords, N, S, frame0, frame_step, fr, K, 1, nullptr, seed_idx, seed_k, seed_cw, seed_ch, seed_fw, seed_fh,
-                         tile_box, grid_w, grid_h, idx_out, group_box, stream);
-}
-
-static int knn_scan_launch(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, FrameRing fr, int K, int nseg,
-                           unsigned long long* keys, const int* seed_idx, int seed_k, int seed_cw, int seed_ch, int seed_fw, int seed_fh,
-                           const float* tile_box, int grid_w, int grid_h, int* idx_direct, const float* group_box, void* stream) {
+  MVT_REQUIRE(ring_frames(base, R, lo, hi, frame0, &fr));
   MVT_REQUIRE(!seed_idx || (seed_k >= K && seed_k <= 64 && seed_cw >= 0));
   MVT_REQUIRE(!seed_idx || seed_cw == 0 || (seed_ch > 0 && seed_fw >= 2 * seed_cw && seed_fh >= 2 * seed_ch));
   MVT_REQUIRE(xyz && coords && (keys || idx_direct) && N > 0 && S > 0);
-  MVT_REQUIRE(K >= 1 && K <= 16 && nseg >= 1 && nseg * K <= 64 && P < (1LL << 31) && P >= K);
-  MVT_REQUIRE((grid_w == 0 && grid_h == 0) || (grid_w > 0 && grid_h > 0 && grid_w % 8 == 0 && grid_h % 8 == 0 && P % ((long long)grid_w * grid_h) == 0));
+  MVT_REQUIRE(K >= 1 && K <= 16 && nseg >= 1 && nseg * K <= 64 && P < (1LL << 31) && P >= K && tile_grid_ok(P, grid_w, grid_h));
   const long long ntiles = (P + 63) / 64, tper = (ntiles + nseg - 1) / nseg;
   MVT_REQUIRE(tper * (nseg - 1) < ntiles);  // no empty segment (a short one pads its key list with KEY_MAX)
-  // queries per wave: 8 amortise the point loads of a brute-force scan; with boxes the scan is short and the per-query
-  // selection work dominates, which spreads better over many small waves
-  static const int q_env = getenv("MVT_KNN_Q") ? atoi(getenv("MVT_KNN_Q")) : 0;
-  const int Q = q_env ? q_env : (tile_box ? 2 : 8);
+  const int Q = knn_queries_per_wave(tile_box != nullptr);
   const int qgroups = (N + Q - 1) / Q;
   const long long ntask = (long long)qgroups * S * nseg;
   MVT_REQUIRE(ntask < (1LL << 31));
-#define LAUNCH(QQ)                                                                                                                   \
-  hipLaunchKernelGGL((knn_scan_kernel<QQ>), dim3((unsigned)mvt_cdiv(ntask, 4)), dim3(256), 0, mvt_stream(stream), xyz, P, coords, N, S, \
-                     frame0, frame_step, fr, K, nseg, keys, qgroups, seed_idx, seed_k, seed_cw, seed_ch, seed_fw, seed_fh, tile_box,    \
-                     grid_w, grid_h, idx_direct, group_box)
-  switch (Q) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 4: LAUNCH(4); break;
-    case 8: LAUNCH(8); break;
-    default: return MVT_ERR_ARG;
-  }
-#undef LAUNCH
+  MVT_LAUNCH_Q(knn_scan_kernel, Q, dim3((unsigned)mvt_cdiv(ntask, 4)), xyz, P, coords, N, S, frame0, frame_step, fr, K, nseg, keys, qgroups,
+               seed_idx, seed_k, seed_cw, seed_ch, seed_fw, seed_fh, tile_box, grid_w, grid_h, idx_direct, group_box);
   return mvt_launch_status();
 }
 
+extern "C" int mvt_knn_scan(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int base, int R,
+                            int lo, int hi, int K, int nseg, unsigned long long* keys, const int* seed_idx, int seed_k, int seed_cw,
+                            int seed_ch, int seed_fw, int seed_fh, const float* tile_box, int grid_w, int grid_h, void* stream) {
+  MVT_REQUIRE(keys);
+  return knn_scan_launch(xyz, P, coords, N, S, frame0, frame_step, base, R, lo, hi, K, nseg, keys, seed_idx, seed_k, seed_cw, seed_ch,
+                         seed_fw, seed_fh, tile_box, grid_w, grid_h, nullptr, nullptr, stream);
+}
+
+extern "C" int mvt_knn_search(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int base,
+                              int R, int lo, int hi, int K, const int* seed_idx, int seed_k, int seed_cw, int seed_ch, int seed_fw,
+                              int seed_fh, const float* tile_box, const float* group_box, int grid_w, int grid_h, int* idx_out,
+                              void* stream) {
+  MVT_REQUIRE(idx_out && tile_box);
+  return knn_scan_launch(xyz, P, coords, N, S, frame0, frame_step, base, R, lo, hi, K, 1, nullptr, seed_idx, seed_k, seed_cw, seed_ch,
+                         seed_fw, seed_fh, tile_box, grid_w, grid_h, idx_out, group_box, stream);
+}
+
 static int knn_check_level(const mvt_knn_level& L, int K) {
-  MVT_REQUIRE(L.xyz && L.keys && L.P >= K && L.P < (1LL << 31) && L.nseg >= 1 && L.nseg * K <= 64);
-  MVT_REQUIRE((L.grid_w == 0 && L.grid_h == 0) ||
-              (L.grid_w > 0 && L.grid_h > 0 && L.grid_w % 8 == 0 && L.grid_h % 8 == 0 && L.P % ((long long)L.grid_w * L.grid_h) == 0));
+  MVT_REQUIRE(L.xyz && L.keys && L.P >= K && L.P < (1LL << 31) && L.nseg >= 1 && L.nseg * K <= 64 && tile_grid_ok(L.P, L.grid_w, L.grid_h));
   const long long ntiles = (L.P + 63) / 64, tper = (ntiles + L.nseg - 1) / L.nseg;
   MVT_REQUIRE(tper * (L.nseg - 1) < ntiles);
   return MVT_OK;
 }
 
-static int knn_scan_levels_impl(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
-                                   FrameRing fr, int K, int seed_k, void* stream) {
+extern "C" int mvt_knn_scan_levels(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
+                                   int base, int R, int lo, int hi, int K, int seed_k, void* stream) {
+  FrameRing fr;
+  MVT_REQUIRE(ring_frames(base, R, lo, hi, frame0, &fr));
   MVT_REQUIRE(levels >= 1 && levels <= 8 && lv && coords && N > 0 && S > 0);
   MVT_REQUIRE(K >= 1 && K <= 16 && (seed_k == 0 || (seed_k >= K && seed_k <= 64)));
   KnnLevels a{};
@@ -950,22 +975,11 @@ static int knn_scan_levels_impl(int levels, const mvt_knn_level* lv, const float
     max_nseg = lv[l].nseg > max_nseg ? lv[l].nseg : max_nseg;
     boxes = boxes && lv[l].tile_box;
   }
-  static const int q_env = getenv("MVT_KNN_Q") ? atoi(getenv("MVT_KNN_Q")) : 0;
-  const int Q = q_env ? q_env : (boxes ? 2 : 8);
+  const int Q = knn_queries_per_wave(boxes);
   const int qgroups = (N + Q - 1) / Q;
   MVT_REQUIRE((long long)qgroups * S * max_nseg < (1LL << 31));
   const dim3 grid((unsigned)mvt_cdiv((long long)qgroups * S * max_nseg, 4), (unsigned)levels);
-#define LAUNCH(QQ)                                                                                                              \
-  hipLaunchKernelGGL((knn_scan_levels_kernel<QQ>), grid, dim3(256), 0, mvt_stream(stream), a, coords, N, S, frame0, frame_step, fr, K, \
-                     qgroups, seed_k)
-  switch (Q) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 4: LAUNCH(4); break;
-    case 8: LAUNCH(8); break;
-    default: return MVT_ERR_ARG;
-  }
-#undef LAUNCH
+  MVT_LAUNCH_Q(knn_scan_levels_kernel, Q, grid, a, coords, N, S, frame0, frame_step, fr, K, qgroups, seed_k);
   return mvt_launch_status();
 }
 
@@ -983,34 +997,24 @@ extern "C" int mvt_knn_merge_levels(int levels, const mvt_knn_level* lv, int N, 
   return mvt_launch_status();
 }
 
-static int knn_search_levels_impl(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
-                                     FrameRing fr, int K, int seed_k, void* stream) {
+extern "C" int mvt_knn_search_levels(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
+                                     int base, int R, int lo, int hi, int K, int seed_k, void* stream) {
+  FrameRing fr;
+  MVT_REQUIRE(ring_frames(base, R, lo, hi, frame0, &fr));
   MVT_REQUIRE(levels >= 1 && levels <= 8 && lv && coords && N > 0 && S > 0);
   MVT_REQUIRE(K >= 1 && K <= 16 && (seed_k == 0 || (seed_k >= K && seed_k <= 64)));
   KnnLevels a{};
   for (int l = 0; l < levels; ++l) {
     const mvt_knn_level& L = lv[l];
     MVT_REQUIRE(L.xyz && L.idx_out && L.tile_box && L.P >= K && L.P < (1LL << 31) && (L.seed_idx != nullptr) == (seed_k > 0));
-    MVT_REQUIRE((L.grid_w == 0 && L.grid_h == 0) ||
-                (L.grid_w > 0 && L.grid_h > 0 && L.grid_w % 8 == 0 && L.grid_h % 8 == 0 && L.P % ((long long)L.grid_w * L.grid_h) == 0));
+    MVT_REQUIRE(tile_grid_ok(L.P, L.grid_w, L.grid_h));
     a.lv[l] = L;
   }
-  static const int q_env = getenv("MVT_KNN_Q") ? atoi(getenv("MVT_KNN_Q")) : 0;
-  const int Q = q_env ? q_env : 2;
+  const int Q = knn_queries_per_wave(true);  // tile boxes are required
   const int qgroups = (N + Q - 1) / Q;
   MVT_REQUIRE((long long)qgroups * S < (1LL << 31));
   const dim3 grid((unsigned)mvt_cdiv((long long)qgroups * S, 4), (unsigned)levels);
-#define LAUNCH(QQ)                                                                                                                \
-  hipLaunchKernelGGL((knn_search_levels_kernel<QQ>), grid, dim3(256), 0, mvt_stream(stream), a, coords, N, S, frame0, frame_step, fr, K, \
-                     qgroups, seed_k)
-  switch (Q) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 4: LAUNCH(4); break;
-    case 8: LAUNCH(8); break;
-    default: return MVT_ERR_ARG;
-  }
-#undef LAUNCH
+  MVT_LAUNCH_Q(knn_search_levels_kernel, Q, grid, a, coords, N, S, frame0, frame_step, fr, K, qgroups, seed_k);
   return mvt_launch_status();
 }
 
@@ -1022,56 +1026,51 @@ extern "C" int mvt_knn_merge(const unsigned long long* keys, int N, int S, int K
   return mvt_launch_status();
 }
 
-static int corr_gather_dot_impl(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
-                                   const int* const* idx, int C, const float* targets, const float* coords, int N, int S,
-                                   int frame0, int frame_step, FrameRing fr, int K, float* out, int ldo, int o_off, void* stream) {
-  MVT_REQUIRE(levels >= 1 && levels <= 8 && xyz && fvec && P && idx && targets && coords && out);
-  MVT_REQUIRE((fvec_bf16 == 0 || fvec_bf16 == 1));
-  MVT_REQUIRE(N > 0 && S > 0 && K >= 1 && K <= 16);
-  MVT_REQUIRE(o_off >= 0 && ldo >= o_off + levels * 4 * K);
-  CorrLevels lv{};
+// The per-level device pointers of the two gather-dot entries, checked: every level has its cloud, feature rows and K neighbours.
+static int corr_levels(int levels, const float* const* xyz, const void* const* fvec, const long long* P, const int* const* idx, int K,
+                       CorrLevels* lv) {
+  MVT_REQUIRE(levels >= 1 && levels <= 8 && xyz && fvec && P && idx);
   for (int l = 0; l < levels; ++l) {
     MVT_REQUIRE(xyz[l] && fvec[l] && idx[l] && P[l] >= K && P[l] < (1LL << 31));
-    lv.xyz[l] = xyz[l];
-    lv.fvec[l] = (const float*)fvec[l];
-    lv.idx[l] = idx[l];
-    lv.P[l] = P[l];
+    lv->xyz[l] = xyz[l];
+    lv->fvec[l] = (const float*)fvec[l];
+    lv->idx[l] = idx[l];
+    lv->P[l] = P[l];
   }
+  return MVT_OK;
+}
+
+extern "C" int mvt_corr_gather_dot(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
+                                   const int* const* idx, int C, const float* targets, const float* coords, int N, int S, int frame0,
+                                   int frame_step, int base, int R, int lo, int hi, int K, float* out, int ldo, int o_off,
+                                   void* stream) {
+  FrameRing fr;
+  MVT_REQUIRE(ring_frames(base, R, lo, hi, frame0, &fr));
+  MVT_REQUIRE(targets && coords && out && (fvec_bf16 == 0 || fvec_bf16 == 1));
+  MVT_REQUIRE(N > 0 && S > 0 && K >= 1 && K <= 16);
+  CorrLevels lv{};
+  if (int rc = corr_levels(levels, xyz, fvec, P, idx, K, &lv)) return rc;
+  MVT_REQUIRE(o_off >= 0 && ldo >= o_off + levels * 4 * K);
   const dim3 grid((unsigned)mvt_cdiv((long long)N * S, 4), (unsigned)levels);
-#define LAUNCH(LPR, BF)                                                                                                              \
-  hipLaunchKernelGGL((corr_gather_dot_kernel<LPR, BF>), grid, dim3(256), 0, mvt_stream(stream), lv, (const float*)targets, coords, N, S, \
-                     frame0, frame_step, fr, K, out, ldo, o_off)
-  if (fvec_bf16) {
-    switch (C) {
-      case 32: LAUNCH(4, 1); break;
-      case 64: LAUNCH(8, 1); break;
-      case 128: LAUNCH(16, 1); break;
-      case 256: LAUNCH(32, 1); break;
-      default: return MVT_ERR_ARG;
-    }
-  } else {
-    switch (C) {
-      case 32: LAUNCH(8, 0); break;
-      case 64: LAUNCH(16, 0); break;
-      case 128: LAUNCH(32, 0); break;
-      case 256: LAUNCH(64, 0); break;
-      default: return MVT_ERR_ARG;
-    }
-  }
-#undef LAUNCH
+  MVT_LAUNCH_ROWS(corr_gather_dot_kernel, fvec_bf16, C, grid, lv, (const float*)targets, coords, N, S, frame0, frame_step, fr, K, out, ldo,
+                  o_off);
   return mvt_launch_status();
 }
 
+// (the 1-NN gather reads one frame: the frame rule only turns it into its slot)
 extern "C" int mvt_knn1_gather(const void* fvec, int fvec_bf16, long long P, int C, const unsigned long long* keys, int n, int nseg,
-                               int frame, float* feat_out, int* idx_out, void* stream) {
-  MVT_REQUIRE(fvec && keys && feat_out && n > 0 && nseg >= 1 && nseg <= 64 && C > 0 && C % 4 == 0 && P > 0 && frame >= 0);
+                               int frame, int base, int R, int lo, int hi, float* feat_out, int* idx_out, void* stream) {
+  FrameRing fr;
+  MVT_REQUIRE(ring_frames(base, R, lo, hi, frame, &fr));
+  MVT_REQUIRE(fvec && keys && feat_out && n > 0 && nseg >= 1 && nseg <= 64 && C > 0 && C % 4 == 0 && P > 0);
   MVT_REQUIRE(fvec_bf16 == 0 || fvec_bf16 == 1);
+  const int slot = (frame - fr.off) % R;
   if (fvec_bf16)
     hipLaunchKernelGGL(knn1_gather_kernel<1>, dim3((unsigned)mvt_cdiv(n, 4)), dim3(256), 0, mvt_stream(stream), (const float*)fvec, P, C, keys,
-                       n, nseg, frame, feat_out, idx_out);
+                       n, nseg, slot, feat_out, idx_out);
   else
     hipLaunchKernelGGL(knn1_gather_kernel<0>, dim3((unsigned)mvt_cdiv(n, 4)), dim3(256), 0, mvt_stream(stream), (const float*)fvec, P, C, keys,
-                       n, nseg, frame, feat_out, idx_out);
+                       n, nseg, slot, feat_out, idx_out);
   return mvt_launch_status();
 }
 
@@ -1108,169 +1107,31 @@ extern "C" int mvt_window_corr_levels(int levels, const void* const* fmaps, int 
   }
   MVT_REQUIRE((uintptr_t)targets % 16 == 0);
   const dim3 grid((unsigned)mvt_cdiv((long long)BS * N, 4), (unsigned)levels);
-#define LAUNCH(LPR, BF)                                                                                                                  \
-  hipLaunchKernelGGL((window_corr_levels_kernel<LPR, BF>), grid, dim3(256), 0, mvt_stream(stream), lv, targets, coords, out, BS, N, radius, \
-                     ldo, o_off)
-  if (fmap_bf16) {
-    switch (C) {
-      case 32: LAUNCH(4, 1); break;
-      case 64: LAUNCH(8, 1); break;
-      case 128: LAUNCH(16, 1); break;
-      case 256: LAUNCH(32, 1); break;
-      default: return MVT_ERR_ARG;
-    }
-  } else {
-    switch (C) {
-      case 32: LAUNCH(8, 0); break;
-      case 64: LAUNCH(16, 0); break;
-      case 128: LAUNCH(32, 0); break;
-      case 256: LAUNCH(64, 0); break;
-      default: return MVT_ERR_ARG;
-    }
-  }
-#undef LAUNCH
+  MVT_LAUNCH_ROWS(window_corr_levels_kernel, fmap_bf16, C, grid, lv, targets, coords, out, BS, N, radius, ldo, o_off);
   return mvt_launch_status();
-}
-
-static int corr_gather_dot_opts_impl(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
-                                        const int* const* idx, int C, const float* targets, const float* coords, int N, int S, int frame0,
-                                        int frame_step, FrameRing fr, int K, int groups, int add_offset, int add_xyz, float* out, int ldo, int o_off,
-                                        void* stream) {
-  MVT_REQUIRE(levels >= 1 && levels <= 8 && xyz && fvec && P && idx && targets && coords && out);
-  MVT_REQUIRE((fvec_bf16 == 0 || fvec_bf16 == 1) && (add_offset == 0 || add_offset == 1) && (add_xyz == 0 || add_xyz == 1));
-  MVT_REQUIRE(N > 0 && S > 0 && K >= 1 && K <= 16);
-  const int lpr = fvec_bf16 ? C / 8 : C / 4;  // lanes per feature row
-  MVT_REQUIRE(groups >= 1 && (groups & (groups - 1)) == 0 && lpr >= 1 && groups <= lpr && lpr % groups == 0);
-  const int OW = groups + 3 * add_offset + 3 * add_xyz;
-  MVT_REQUIRE(o_off >= 0 && ldo >= o_off + levels * K * OW);
-  CorrLevels lv{};
-  for (int l = 0; l < levels; ++l) {
-    MVT_REQUIRE(xyz[l] && fvec[l] && idx[l] && P[l] >= K && P[l] < (1LL << 31));
-    lv.xyz[l] = xyz[l];
-    lv.fvec[l] = (const float*)fvec[l];
-    lv.idx[l] = idx[l];
-    lv.P[l] = P[l];
-  }
-  const dim3 grid((unsigned)mvt_cdiv((long long)N * S, 4), (unsigned)levels);
-#define LAUNCH(LPR, BF)                                                                                                                   \
-  hipLaunchKernelGGL((corr_gather_dot_opts_kernel<LPR, BF>), grid, dim3(256), 0, mvt_stream(stream), lv, (const float*)targets, coords, N, S, \
-                     frame0, frame_step, fr, K, out, ldo, o_off, groups, add_offset, add_xyz)
-  if (fvec_bf16) {
-    switch (C) {
-      case 32: LAUNCH(4, 1); break;
-      case 64: LAUNCH(8, 1); break;
-      case 128: LAUNCH(16, 1); break;
-      case 256: LAUNCH(32, 1); break;
-      default: return MVT_ERR_ARG;
-    }
-  } else {
-    switch (C) {
-      case 32: LAUNCH(8, 0); break;
-      case 64: LAUNCH(16, 0); break;
-      case 128: LAUNCH(32, 0); break;
-      case 256: LAUNCH(64, 0); break;
-      default: return MVT_ERR_ARG;
-    }
-  }
-#undef LAUNCH
-  return mvt_launch_status();
-}
-
-// ------------------------------------------------------------------------------------------------
-// The entries that map window slots to store frames, in their linear form (a store of T frames) and their ring form (frames
-// [lo, hi] resident, frame f in slot (f - base) mod R): one kernel each, the FrameRing is the only difference.
-#define MVT_LINEAR(T) \
-  FrameRing fr;       \
-  MVT_REQUIRE(linear_frames(T, frame0, &fr))
-#define MVT_RING()  \
-  FrameRing fr;     \
-  MVT_REQUIRE(ring_frames(base, R, lo, hi, frame0, &fr))
-
-extern "C" int mvt_knn_scan_ring(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int base,
-                                 int R, int lo, int hi, int K, int nseg, unsigned long long* keys, const int* seed_idx, int seed_k,
-                                 int seed_cw, int seed_ch, int seed_fw, int seed_fh, const float* tile_box, int grid_w, int grid_h,
-                                 void* stream) {
-  MVT_REQUIRE(keys);
-  MVT_RING();
-  return knn_scan_launch(xyz, P, coords, N, S, frame0, frame_step, fr, K, nseg, keys, seed_idx, seed_k, seed_cw, seed_ch, seed_fw, seed_fh,
-                         tile_box, grid_w, grid_h, nullptr, nullptr, stream);
-}
-
-extern "C" int mvt_knn_search_ring(const float* xyz, long long P, const float* coords, int N, int S, int frame0, int frame_step, int base,
-                                   int R, int lo, int hi, int K, const int* seed_idx, int seed_k, int seed_cw, int seed_ch, int seed_fw,
-                                   int seed_fh, const float* tile_box, const float* group_box, int grid_w, int grid_h, int* idx_out,
-                                   void* stream) {
-  MVT_REQUIRE(idx_out && tile_box);
-  MVT_RING();
-  return knn_scan_launch(xyz, P, coords, N, S, frame0, frame_step, fr, K, 1, nullptr, seed_idx, seed_k, seed_cw, seed_ch, seed_fw, seed_fh,
-                         tile_box, grid_w, grid_h, idx_out, group_box, stream);
-}
-
-extern "C" int mvt_knn_scan_levels(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
-                                   int T, int K, int seed_k, void* stream) {
-  MVT_LINEAR(T);
-  return knn_scan_levels_impl(levels, lv, coords, N, S, frame0, frame_step, fr, K, seed_k, stream);
-}
-
-extern "C" int mvt_knn_scan_levels_ring(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0,
-                                        int frame_step, int base, int R, int lo, int hi, int K, int seed_k, void* stream) {
-  MVT_RING();
-  return knn_scan_levels_impl(levels, lv, coords, N, S, frame0, frame_step, fr, K, seed_k, stream);
-}
-
-extern "C" int mvt_knn_search_levels(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0, int frame_step,
-                                     int T, int K, int seed_k, void* stream) {
-  MVT_LINEAR(T);
-  return knn_search_levels_impl(levels, lv, coords, N, S, frame0, frame_step, fr, K, seed_k, stream);
-}
-
-extern "C" int mvt_knn_search_levels_ring(int levels, const mvt_knn_level* lv, const float* coords, int N, int S, int frame0,
-                                          int frame_step, int base, int R, int lo, int hi, int K, int seed_k, void* stream) {
-  MVT_RING();
-  return knn_search_levels_impl(levels, lv, coords, N, S, frame0, frame_step, fr, K, seed_k, stream);
-}
-
-extern "C" int mvt_corr_gather_dot(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
-                                   const int* const* idx, int C, const float* targets, const float* coords, int N, int S,
-                                   int frame0, int frame_step, int T, int K, float* out, int ldo, int o_off, void* stream) {
-  MVT_LINEAR(T);
-  return corr_gather_dot_impl(levels, xyz, fvec, fvec_bf16, P, idx, C, targets, coords, N, S, frame0, frame_step, fr, K, out, ldo, o_off,
-                              stream);
-}
-
-extern "C" int mvt_corr_gather_dot_ring(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
-                                        const int* const* idx, int C, const float* targets, const float* coords, int N, int S,
-                                        int frame0, int frame_step, int base, int R, int lo, int hi, int K, float* out, int ldo,
-                                        int o_off, void* stream) {
-  MVT_RING();
-  return corr_gather_dot_impl(levels, xyz, fvec, fvec_bf16, P, idx, C, targets, coords, N, S, frame0, frame_step, fr, K, out, ldo, o_off,
-                              stream);
 }
 
 extern "C" int mvt_corr_gather_dot_opts(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16, const long long* P,
                                         const int* const* idx, int C, const float* targets, const float* coords, int N, int S, int frame0,
-                                        int frame_step, int T, int K, int groups, int add_offset, int add_xyz, float* out, int ldo, int o_off,
-                                        void* stream) {
-  MVT_LINEAR(T);
-  return corr_gather_dot_opts_impl(levels, xyz, fvec, fvec_bf16, P, idx, C, targets, coords, N, S, frame0, frame_step, fr, K, groups,
-                                   add_offset, add_xyz, out, ldo, o_off, stream);
+                                        int frame_step, int base, int R, int lo, int hi, int K, int groups, int add_offset, int add_xyz,
+                                        float* out, int ldo, int o_off, void* stream) {
+  FrameRing fr;
+  MVT_REQUIRE(ring_frames(base, R, lo, hi, frame0, &fr));
+  MVT_REQUIRE(targets && coords && out);
+  MVT_REQUIRE((fvec_bf16 == 0 || fvec_bf16 == 1) && (add_offset == 0 || add_offset == 1) && (add_xyz == 0 || add_xyz == 1));
+  MVT_REQUIRE(N > 0 && S > 0 && K >= 1 && K <= 16);
+  const int lpr = fvec_bf16 ? C / 8 : C / 4;  // lanes per feature row
+  MVT_REQUIRE(groups >= 1 && (groups & (groups - 1)) == 0 && lpr >= 1 && groups <= lpr && lpr % groups == 0);
+  CorrLevels lv{};
+  if (int rc = corr_levels(levels, xyz, fvec, P, idx, K, &lv)) return rc;
+  const int OW = groups + 3 * add_offset + 3 * add_xyz;
+  MVT_REQUIRE(o_off >= 0 && ldo >= o_off + levels * K * OW);
+  const dim3 grid((unsigned)mvt_cdiv((long long)N * S, 4), (unsigned)levels);
+  MVT_LAUNCH_ROWS(corr_gather_dot_opts_kernel, fvec_bf16, C, grid, lv, (const float*)targets, coords, N, S, frame0, frame_step, fr, K, out,
+                  ldo, o_off, groups, add_offset, add_xyz);
+  return mvt_launch_status();
 }
-
-extern "C" int mvt_corr_gather_dot_opts_ring(int levels, const float* const* xyz, const void* const* fvec, int fvec_bf16,
-                                             const long long* P, const int* const* idx, int C, const float* targets, const float* coords,
-                                             int N, int S, int frame0, int frame_step, int base, int R, int lo, int hi, int K, int groups,
-                                             int add_offset, int add_xyz, float* out, int ldo, int o_off, void* stream) {
-  MVT_RING();
-  return corr_gather_dot_opts_impl(levels, xyz, fvec, fvec_bf16, P, idx, C, targets, coords, N, S, frame0, frame_step, fr, K, groups,
-                                   add_offset, add_xyz, out, ldo, o_off, stream);
-}
-
-// (the 1-NN gather reads one frame: its ring form only turns the frame into its slot)
-extern "C" int mvt_knn1_gather_ring(const void* fvec, int fvec_bf16, long long P, int C, const unsigned long long* keys, int n, int nseg,
-                                    int frame, int base, int R, int lo, int hi, float* feat_out, int* idx_out, void* stream) {
-  const int frame0 = frame;
-  MVT_RING();
-  return mvt_knn1_gather(fvec, fvec_bf16, P, C, keys, n, nseg, (frame - fr.off) % R, feat_out, idx_out, stream);
-}
-#undef MVT_LINEAR
-#undef MVT_RING
+#undef MVT_LAUNCH_Q
+#undef MVT_LAUNCH_Q1
+#undef MVT_LAUNCH_ROWS
+#undef MVT_LAUNCH_ROWS1

@@ -54,26 +54,19 @@ SIGNATURES = {
     "mvt_avgpool2": [P, P, LL, I, I, I, I, P],
     "mvt_unproject": [P, P, P, P, I, I, I, I, I, I, P],
     "mvt_tile_aabb": [P, LL, I, I, I, P, P],
-    "mvt_knn_scan": [P, LL, P, I, I, I, I, I, I, I, P, P, I, I, I, I, I, P, I, I, P],
+    "mvt_knn_scan": [P, LL, P, I, I, I, I, I, I, I, I, I, I, P, P, I, I, I, I, I, P, I, I, P],
     "mvt_knn_merge": [P, I, I, I, I, LL, P, P],
     "mvt_ln_proj_bf16": [P, I, P, I, LL, I, P],
     "mvt_input_proj_bf16": [P, I, I, LL, P, P, P, I, P, I, P, I, LL, I, P],
     "mvt_adapter_best_view": [P, P, P, P, I, I, I, I, I, P, P, P],
-    "mvt_knn_scan_levels": [I, P, P, I, I, I, I, I, I, I, P],
-    "mvt_knn_search_levels": [I, P, P, I, I, I, I, I, I, I, P],
-    "mvt_knn_search": [P, LL, P, I, I, I, I, I, I, P, I, I, I, I, I, P, P, I, I, P, P],
+    "mvt_knn_scan_levels": [I, P, P, I, I, I, I, I, I, I, I, I, I, P],
+    "mvt_knn_search_levels": [I, P, P, I, I, I, I, I, I, I, I, I, I, P],
+    "mvt_knn_search": [P, LL, P, I, I, I, I, I, I, I, I, I, P, I, I, I, I, I, P, P, I, I, P, P],
     "mvt_tile_group_aabb": [P, LL, I, P, P],
     "mvt_knn_merge_levels": [I, P, I, I, I, P],
-    "mvt_corr_gather_dot": [I, P, P, I, P, P, I, P, P, I, I, I, I, I, I, P, I, I, P],
-    "mvt_corr_gather_dot_opts": [I, P, P, I, P, P, I, P, P, I, I, I, I, I, I, I, I, I, P, I, I, P],
-    "mvt_knn1_gather": [P, I, LL, I, P, I, I, I, P, P, P],
-    "mvt_knn_scan_ring": [P, LL, P, I, I, I, I, I, I, I, I, I, I, P, P, I, I, I, I, I, P, I, I, P],
-    "mvt_knn_search_ring": [P, LL, P, I, I, I, I, I, I, I, I, I, P, I, I, I, I, I, P, P, I, I, P, P],
-    "mvt_knn_scan_levels_ring": [I, P, P, I, I, I, I, I, I, I, I, I, I, P],
-    "mvt_knn_search_levels_ring": [I, P, P, I, I, I, I, I, I, I, I, I, I, P],
-    "mvt_corr_gather_dot_ring": [I, P, P, I, P, P, I, P, P, I, I, I, I, I, I, I, I, I, P, I, I, P],
-    "mvt_corr_gather_dot_opts_ring": [I, P, P, I, P, P, I, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, I, I, P],
-    "mvt_knn1_gather_ring": [P, I, LL, I, P, I, I, I, I, I, I, I, P, P, P],
+    "mvt_corr_gather_dot": [I, P, P, I, P, P, I, P, P, I, I, I, I, I, I, I, I, I, P, I, I, P],
+    "mvt_corr_gather_dot_opts": [I, P, P, I, P, P, I, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, I, I, P],
+    "mvt_knn1_gather": [P, I, LL, I, P, I, I, I, I, I, I, I, P, P, P],
     "mvt_window_store_chunk": [P, P, P, I, I, I, I, I, I, I, P, P, P, P],
     "mvt_window_corr": [P, P, P, P, I, I, I, I, I, I, I, I, I, P],
     "mvt_window_corr_levels": [I, P, I, P, P, P, P, P, I, I, I, I, I, I, P],
@@ -388,12 +381,23 @@ def tile_aabb(xyz, Pn, T, box, grid=(0, 0)):
     _call("mvt_tile_aabb", _ptr(xyz), Pn, T, grid[0], grid[1], _ptr(box), _stream())
 
 
+def _frames(T):
+    """The frame rule of include/mvtracker_hip.h, (base, R, lo, hi), from what the slot-mapped wrappers take where ``T`` stands: an
+    int is a linear store of T frames, (0, T, 0, T-1); a ring store's (base, R, lo, hi) passes through (the store tensors hold R
+    frame slots, frame f in slot (f - base) mod R, frames [lo, hi] resident, a window slot reads clamp(frame0 + s * frame_step, lo, hi))."""
+    if isinstance(T, int):
+        return (0, T, 0, T - 1)
+    if isinstance(T, (tuple, list)) and len(T) == 4:
+        return tuple(T)
+    raise HipError(f"frames must be a frame count T or (base, R, lo, hi), got {T!r}")
+
+
 def knn_scan(xyz, Pn, coords, N, S, frame0, frame_step, T, K, nseg, keys, seed_idx=None, seed_k=0, seed_dims=(0, 0, 0, 0), box=None,
              grid=(0, 0)):
-    """seed_dims = (coarse_w, coarse_h, fine_w, fine_h) per-view grids when the seed comes from the coarser level;
+    """T: the store's frames (``_frames``), here and in every wrapper below that takes it.  seed_dims = (coarse_w, coarse_h, fine_w, fine_h) per-view grids when the seed comes from the coarser level;
     box / grid: tile bounding boxes from ``tile_aabb`` (same grid) for culling."""
-    _call("mvt_knn_scan", _ptr(xyz), Pn, _ptr(coords), N, S, frame0, frame_step, T, K, nseg, _ptr(keys), _ptr(seed_idx), seed_k,
-          *seed_dims, _ptr(box), grid[0], grid[1], _stream())
+    _call("mvt_knn_scan", _ptr(xyz), Pn, _ptr(coords), N, S, frame0, frame_step, *_frames(T), K, nseg, _ptr(keys), _ptr(seed_idx),
+          seed_k, *seed_dims, _ptr(box), grid[0], grid[1], _stream())
 
 
 class KnnLevel(C.Structure):
@@ -414,7 +418,8 @@ def _knn_levels(levels):
 def knn_scan_levels(levels, coords, N, S, frame0, frame_step, T, K, seed_k=0):
     """levels: list of dicts(xyz, P, keys, nseg[, seed_idx, box, grid, idx_out]); one launch for all of them."""
     arr = _knn_levels(levels)
-    _call("mvt_knn_scan_levels", len(levels), C.cast(arr, C.c_void_p), _ptr(coords), N, S, frame0, frame_step, T, K, seed_k, _stream())
+    _call("mvt_knn_scan_levels", len(levels), C.cast(arr, C.c_void_p), _ptr(coords), N, S, frame0, frame_step, *_frames(T), K, seed_k,
+          _stream())
 
 
 def tile_group_aabb(box, Pn, T, group_box):
@@ -425,14 +430,15 @@ def tile_group_aabb(box, Pn, T, group_box):
 def knn_search(xyz, Pn, coords, N, S, frame0, frame_step, T, K, idx_out, box, grid=(0, 0), gbox=None, seed_idx=None, seed_k=0,
                seed_dims=(0, 0, 0, 0)):
     """``knn_scan`` (one segment) + ``knn_merge`` in one launch: neighbour indices straight to idx_out (N,S,K) int32."""
-    _call("mvt_knn_search", _ptr(xyz), Pn, _ptr(coords), N, S, frame0, frame_step, T, K, _ptr(seed_idx), seed_k, *seed_dims, _ptr(box),
-          _ptr(gbox), grid[0], grid[1], _ptr(idx_out), _stream())
+    _call("mvt_knn_search", _ptr(xyz), Pn, _ptr(coords), N, S, frame0, frame_step, *_frames(T), K, _ptr(seed_idx), seed_k, *seed_dims,
+          _ptr(box), _ptr(gbox), grid[0], grid[1], _ptr(idx_out), _stream())
 
 
 def knn_search_levels(levels, coords, N, S, frame0, frame_step, T, K, seed_k):
     """Seeded scan + merge in one launch: levels of dicts(xyz, P, seed_idx, box, grid, idx_out[, gbox]); idx_out may alias seed_idx."""
     arr = _knn_levels([dict(lv, keys=None, nseg=1) for lv in levels])
-    _call("mvt_knn_search_levels", len(levels), C.cast(arr, C.c_void_p), _ptr(coords), N, S, frame0, frame_step, T, K, seed_k, _stream())
+    _call("mvt_knn_search_levels", len(levels), C.cast(arr, C.c_void_p), _ptr(coords), N, S, frame0, frame_step, *_frames(T), K, seed_k,
+          _stream())
 
 
 def knn_merge_levels(levels, N, S, K):
@@ -449,83 +455,43 @@ def knn_merge(keys, N, S, K, nseg, Pn, idx_out):
     _call("mvt_knn_merge", _ptr(keys), N, S, K, nseg, Pn, _ptr(idx_out), _stream())
 
 
-def corr_gather_dot(xyz_l, fvec_l, P_l, idx_l, Cc, targets, coords, N, S, frame0, frame_step, T, K, out, ldo, o_off):
-    """xyz_l / fvec_l / idx_l: lists of per-level device tensors; P_l: list of point counts."""
+def _corr_levels(xyz_l, fvec_l, P_l, idx_l):
+    """The leading arguments of the two gather-dot entries: level count, per-level pointer arrays, the feature rows' type."""
     n = len(xyz_l)
     pa = (C.c_void_p * n)
     bf = fvec_l[0].dtype == torch.bfloat16
     assert all((t.dtype == torch.bfloat16) == bf for t in fvec_l)
-    _call("mvt_corr_gather_dot", n, pa(*[_ptr(t) for t in xyz_l]), pa(*[_ptr(t) for t in fvec_l]), 1 if bf else 0, (C.c_longlong * n)(*P_l),
-          pa(*[_ptr(t) for t in idx_l]), Cc, _ptr(targets), _ptr(coords), N, S, frame0, frame_step, T, K, _ptr(out), ldo, o_off,
-          _stream())
+    return (n, pa(*[_ptr(t) for t in xyz_l]), pa(*[_ptr(t) for t in fvec_l]), 1 if bf else 0, (C.c_longlong * n)(*P_l),
+            pa(*[_ptr(t) for t in idx_l]))
+
+
+def corr_gather_dot(xyz_l, fvec_l, P_l, idx_l, Cc, targets, coords, N, S, frame0, frame_step, T, K, out, ldo, o_off):
+    """xyz_l / fvec_l / idx_l: lists of per-level device tensors; P_l: list of point counts."""
+    _call("mvt_corr_gather_dot", *_corr_levels(xyz_l, fvec_l, P_l, idx_l), Cc, _ptr(targets), _ptr(coords), N, S, frame0, frame_step,
+          *_frames(T), K, _ptr(out), ldo, o_off, _stream())
 
 
 def corr_gather_dot_opts(xyz_l, fvec_l, P_l, idx_l, Cc, targets, coords, N, S, frame0, frame_step, T, K, groups, add_offset, add_xyz, out, ldo,
                          o_off):
     """``corr_gather_dot`` with the non-default correlation options: groups + 3 add_offset + 3 add_xyz values per neighbour."""
-    n = len(xyz_l)
-    pa = (C.c_void_p * n)
-    bf = fvec_l[0].dtype == torch.bfloat16
-    assert all((t.dtype == torch.bfloat16) == bf for t in fvec_l)
-    _call("mvt_corr_gather_dot_opts", n, pa(*[_ptr(t) for t in xyz_l]), pa(*[_ptr(t) for t in fvec_l]), 1 if bf else 0, (C.c_longlong * n)(*P_l),
-          pa(*[_ptr(t) for t in idx_l]), Cc, _ptr(targets), _ptr(coords), N, S, frame0, frame_step, T, K, groups, 1 if add_offset else 0,
-          1 if add_xyz else 0, _ptr(out), ldo, o_off, _stream())
+    _call("mvt_corr_gather_dot_opts", *_corr_levels(xyz_l, fvec_l, P_l, idx_l), Cc, _ptr(targets), _ptr(coords), N, S, frame0, frame_step,
+          *_frames(T), K, groups, 1 if add_offset else 0, 1 if add_xyz else 0, _ptr(out), ldo, o_off, _stream())
 
 
-def knn1_gather(fvec, Pn, Cc, keys, n, nseg, frame, feat_out, idx_out=None):
-    _call("mvt_knn1_gather", _ptr(fvec), 1 if fvec.dtype == torch.bfloat16 else 0, Pn, Cc, _ptr(keys), n, nseg, frame, _ptr(feat_out),
-          _ptr(idx_out), _stream())
+def knn1_gather(fvec, Pn, Cc, keys, n, nseg, frame, feat_out, idx_out=None, frames=None):
+    """frames: the store's frames (``_frames``); None = ``frame`` is the slot itself (a linear store that holds it)."""
+    _call("mvt_knn1_gather", _ptr(fvec), 1 if fvec.dtype == torch.bfloat16 else 0, Pn, Cc, _ptr(keys), n, nseg, frame,
+          *((0, frame + 1, 0, frame) if frames is None else _frames(frames)), _ptr(feat_out), _ptr(idx_out), _stream())
 
 
-# ---- ring forms (streaming): ``ring`` = (base, R, lo, hi) stands where the linear wrapper takes T -- the store tensors hold R frame
-# slots, frame f in slot (f - base) mod R, frames [lo, hi] resident, a window slot reads clamp(frame0 + s * frame_step, lo, hi)
-def knn_scan_ring(xyz, Pn, coords, N, S, frame0, frame_step, ring, K, nseg, keys, seed_idx=None, seed_k=0, seed_dims=(0, 0, 0, 0), box=None,
-                  grid=(0, 0)):
-    _call("mvt_knn_scan_ring", _ptr(xyz), Pn, _ptr(coords), N, S, frame0, frame_step, *ring, K, nseg, _ptr(keys), _ptr(seed_idx), seed_k,
-          *seed_dims, _ptr(box), grid[0], grid[1], _stream())
-
-
-def knn_search_ring(xyz, Pn, coords, N, S, frame0, frame_step, ring, K, idx_out, box, grid=(0, 0), gbox=None, seed_idx=None, seed_k=0,
-                    seed_dims=(0, 0, 0, 0)):
-    _call("mvt_knn_search_ring", _ptr(xyz), Pn, _ptr(coords), N, S, frame0, frame_step, *ring, K, _ptr(seed_idx), seed_k, *seed_dims,
-          _ptr(box), _ptr(gbox), grid[0], grid[1], _ptr(idx_out), _stream())
-
-
-def knn_scan_levels_ring(levels, coords, N, S, frame0, frame_step, ring, K, seed_k=0):
-    arr = _knn_levels(levels)
-    _call("mvt_knn_scan_levels_ring", len(levels), C.cast(arr, C.c_void_p), _ptr(coords), N, S, frame0, frame_step, *ring, K, seed_k, _stream())
-
-
-def knn_search_levels_ring(levels, coords, N, S, frame0, frame_step, ring, K, seed_k):
-    arr = _knn_levels([dict(lv, keys=None, nseg=1) for lv in levels])
-    _call("mvt_knn_search_levels_ring", len(levels), C.cast(arr, C.c_void_p), _ptr(coords), N, S, frame0, frame_step, *ring, K, seed_k,
-          _stream())
-
-
-def corr_gather_dot_ring(xyz_l, fvec_l, P_l, idx_l, Cc, targets, coords, N, S, frame0, frame_step, ring, K, out, ldo, o_off):
-    n = len(xyz_l)
-    pa = (C.c_void_p * n)
-    bf = fvec_l[0].dtype == torch.bfloat16
-    assert all((t.dtype == torch.bfloat16) == bf for t in fvec_l)
-    _call("mvt_corr_gather_dot_ring", n, pa(*[_ptr(t) for t in xyz_l]), pa(*[_ptr(t) for t in fvec_l]), 1 if bf else 0,
-          (C.c_longlong * n)(*P_l), pa(*[_ptr(t) for t in idx_l]), Cc, _ptr(targets), _ptr(coords), N, S, frame0, frame_step, *ring, K,
-          _ptr(out), ldo, o_off, _stream())
-
-
-def corr_gather_dot_opts_ring(xyz_l, fvec_l, P_l, idx_l, Cc, targets, coords, N, S, frame0, frame_step, ring, K, groups, add_offset, add_xyz,
-                              out, ldo, o_off):
-    n = len(xyz_l)
-    pa = (C.c_void_p * n)
-    bf = fvec_l[0].dtype == torch.bfloat16
-    assert all((t.dtype == torch.bfloat16) == bf for t in fvec_l)
-    _call("mvt_corr_gather_dot_opts_ring", n, pa(*[_ptr(t) for t in xyz_l]), pa(*[_ptr(t) for t in fvec_l]), 1 if bf else 0,
-          (C.c_longlong * n)(*P_l), pa(*[_ptr(t) for t in idx_l]), Cc, _ptr(targets), _ptr(coords), N, S, frame0, frame_step, *ring, K,
-          groups, 1 if add_offset else 0, 1 if add_xyz else 0, _ptr(out), ldo, o_off, _stream())
+# The names under which the tracker reads a ring store (streaming), and under which the host tests put their stand-ins for it:
+# the wrappers above, with ``ring`` = (base, R, lo, hi) in T's place.
+knn_scan_ring, knn_search_ring, knn_scan_levels_ring, knn_search_levels_ring = knn_scan, knn_search, knn_scan_levels, knn_search_levels
+corr_gather_dot_ring, corr_gather_dot_opts_ring = corr_gather_dot, corr_gather_dot_opts
 
 
 def knn1_gather_ring(fvec, Pn, Cc, keys, n, nseg, frame, ring, feat_out, idx_out=None):
-    _call("mvt_knn1_gather_ring", _ptr(fvec), 1 if fvec.dtype == torch.bfloat16 else 0, Pn, Cc, _ptr(keys), n, nseg, frame, *ring,
-          _ptr(feat_out), _ptr(idx_out), _stream())
+    knn1_gather(fvec, Pn, Cc, keys, n, nseg, frame, feat_out, idx_out, frames=ring)
 
 
 def window_corr(fmap, targets, coords, out, BS, N, Cc, h, w, level, radius, ldo, o_off):

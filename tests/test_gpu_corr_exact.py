@@ -482,6 +482,48 @@ def test_knn_refusals(hip):
     assert bool((keys == SENT_K).all()) and bool((idx == SENT_I).all())
 
 
+@gpu
+def test_linear_frames_refusals(hip):
+    """A frame count T is the ring (0, T, 0, T-1): T = 0, frame0 = -1 and frame0 = T are refused by every slot-mapped wrapper
+    (and by knn1_gather with frames=T) before anything is launched, on the cloud of test_knn_refusals; with T = 1, frame0 = 0
+    the same calls are accepted."""
+    r = R.rng("refuse")
+    dev, P, N, K, Cc = DEV, 320, 2, 4, 32
+    xyz, coords = T_(cloud4(lattice(r, 1, P, 3)), dev), T_(lattice(r, N, 1, 3), dev)
+    fvec, tg = T_(small(r, 1, P, Cc), dev), T_(small(r, N, 1, Cc), dev)
+    box = torch.zeros(1, 5, 8, device=dev)
+    hip.tile_aabb(xyz, P, 1, box)
+    nbr = torch.arange(N * K, dtype=torch.int32, device=dev)
+
+    def calls(T, f0, keys, idx, out, feat):
+        lv = [dict(xyz=xyz, P=P, keys=keys, nseg=1, box=box, idx_out=idx)]
+        return [lambda: hip.knn_scan(xyz, P, coords, N, 1, f0, 1, T, K, 1, keys),
+                lambda: hip.knn_search(xyz, P, coords, N, 1, f0, 1, T, K, idx, box),
+                lambda: hip.knn_scan_levels(lv, coords, N, 1, f0, 1, T, K),
+                lambda: hip.knn_search_levels(lv, coords, N, 1, f0, 1, T, K, 0),
+                lambda: hip.corr_gather_dot([xyz], [fvec], [P], [nbr], Cc, tg, coords, N, 1, f0, 1, T, K, out, 4 * K, 0),
+                lambda: hip.corr_gather_dot_opts([xyz], [fvec], [P], [nbr], Cc, tg, coords, N, 1, f0, 1, T, K, 1, True, False, out, 4 * K, 0),
+                lambda: hip.knn1_gather(fvec, P, Cc, keys, N, 1, f0, feat, idx, frames=T)]
+
+    def bufs():
+        return (torch.full((N * K,), SENT_K, dtype=torch.int64, device=dev), torch.full((N * K,), SENT_I, dtype=torch.int32, device=dev),
+                torch.full((N, 4 * K), NAN, device=dev), torch.full((N, Cc), NAN, device=dev))
+
+    good = bufs()
+    for f in calls(1, 0, *good):
+        f()
+    torch.cuda.synchronize()
+    assert all(not bool(((b == SENT_K) | (b == SENT_I) | torch.isnan(b)).any()) for b in good)
+    keys, idx, out, feat = bufs()
+    for T, f0 in ((0, 0), (1, -1), (1, 1)):
+        for i, f in enumerate(calls(T, f0, keys, idx, out, feat)):
+            with pytest.raises(hip.HipError, match="arguments rejected"):
+                f()
+            assert i >= 0
+    torch.cuda.synchronize()
+    assert bool((keys == SENT_K).all()) and bool((idx == SENT_I).all()) and bool(torch.isnan(out).all()) and bool(torch.isnan(feat).all())
+
+
 def test_knn_reference_is_the_oracle():
     """The lattice restatement picks the oracle's neighbours (knn_exact, and corr_sample's own search) on NaN-free cases."""
     for c in [shape_cases(133)[-1], order_case("ties", "boxed"), order_case("same", "patch"), order_case("desc", "free")]:

@@ -154,6 +154,17 @@ def test_ring_slot_arithmetic_against_a_linear_store():
             assert hi == Tn - 1 and torch.equal(ring.index_select(0, hip_mock_ring.ring_slots((sc.base, sc.R, w, hi))), linear[w:Tn])
 
 
+def test_frames_of_a_count_and_of_a_ring():
+    """What the slot-mapped wrappers accept where T stands: a frame count is the ring (0, T, 0, T-1), a ring passes through,
+    anything else is refused."""
+    from mvtracker_amd import hip
+    assert hip._frames(12) == (0, 12, 0, 11) and hip._frames(1) == (0, 1, 0, 0) and hip._frames(0) == (0, 0, 0, -1)
+    assert hip._frames((95, 18, 107, 118)) == (95, 18, 107, 118) and hip._frames([7, 24, 1009, 1020]) == (7, 24, 1009, 1020)
+    for bad in ((0, 12, 0), (0, 12, 0, 11, 0), (), None, 12.0, "12"):
+        with pytest.raises(hip.HipError, match="frames"):
+            hip._frames(bad)
+
+
 # ------------------------------------------------------------------ the session on mocked kernels
 @pytest.fixture()
 def model(monkeypatch):
