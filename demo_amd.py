@@ -91,6 +91,16 @@ def build_parser():
                          "(mvtracker_amd.estimate_normals, the reference's estimate_normals)")
     ap.add_argument("--align-normal-radius", type=float, default=None, help="PCA normals: neighbour radius (default: --align-max-distance)")
     ap.add_argument("--align-normal-max-nn", type=int, default=30, help="PCA normals: neighbours per point, at most")
+    ap.add_argument("--reprojection-check", action="store_true",
+                    help="render every view from the other views' depth maps and score the render against the view's own frame and depth "
+                         "(mvtracker_amd.reprojection_report, the reference's reproject_depth_into_videos.py and "
+                         "compare_photometric_error.py on the device); with --align-cameras both tables and their difference are printed")
+    ap.add_argument("--reproject-frames", type=int, nargs="+", default=[0], metavar="F", help="frames that are rendered and scored")
+    ap.add_argument("--reproject-sources", choices=("others", "all"), default="others",
+                    help="a view is rendered from every other view, or from every view (what the reference script renders)")
+    ap.add_argument("--reproject-splat", type=int, choices=(1, 3, 5), default=1, help="side of the depth-tested sprite a point is drawn as")
+    ap.add_argument("--reproject-depth-tol", type=float, default=0.05,
+                    help="a rendered depth within this of the view's own depth counts as close, in the clip's own units")
     return ap
 
 
@@ -114,6 +124,15 @@ def camera_alignment_from_args(args):
     if args.align_normals == "pca":
         return PcaCameraAlignment(normal_radius=args.align_normal_radius, normal_max_nn=args.align_normal_max_nn, **kw)
     return CameraAlignment(**kw)
+
+
+def reprojection_check_from_args(args):
+    """The ReprojectionCheck of --reprojection-check and the --reproject-* flags, or None."""
+    if not args.reprojection_check:
+        return None
+    from mvtracker_amd import ReprojectionCheck
+    return ReprojectionCheck(frames=tuple(args.reproject_frames), sources=args.reproject_sources, splat=args.reproject_splat,
+                             depth_tol=args.reproject_depth_tol)
 
 
 def main():
@@ -148,9 +167,14 @@ def main():
     # sampled, the saved mask is cleaned and the scene is normalised with the corrected cameras, which are also what is saved
     cleaning, alignment, keep = depth_cleaning_from_args(args), camera_alignment_from_args(args), None
     norm_depths = s["depths"]
-    if cleaning is not None and alignment is not None:
+    check, before = reprojection_check_from_args(args), None
+    if cleaning is not None and (alignment is not None or check is not None):  # (the check reports on what the predictor would track with)
         from mvtracker_amd import clean_depths
         norm_depths = clean_depths(s["depths"].float(), s["intrs"], s["extrs"], cleaning)[0]
+    if check is not None and alignment is not None:  # the reference's "no ICP" side
+        from mvtracker_amd import reprojection_report
+        before = reprojection_report(s["rgbs"], norm_depths.float(), s["intrs"], s["extrs"], check, depths_conf=s.get("depths_conf"))
+        print(before.table("no_icp"))
     if alignment is not None:  # once, here: the warm-up and the timed call both get the corrected cameras
         from mvtracker_amd import align_cameras
         correction = align_cameras(norm_depths.float(), s["intrs"], s["extrs"], alignment, depths_conf=s.get("depths_conf"))
@@ -158,6 +182,13 @@ def main():
         s["camera_corrections"] = correction.transforms.cpu().numpy()
         print(f"camera alignment: fitness {np.round(correction.fitness.cpu().numpy(), 3).tolist()}, rmse "
               f"{np.round(correction.rmse.cpu().numpy(), 4).tolist()}, iterations {correction.iterations.cpu().tolist()}")
+    if check is not None:
+        from mvtracker_amd import compare_reports, reprojection_report
+        report = reprojection_report(s["rgbs"], norm_depths.float(), s["intrs"], s["extrs"], check, depths_conf=s.get("depths_conf"))
+        print(report.table("icp" if before is not None else "reprojection"))
+        if before is not None:
+            print("improvement (positive = the corrected cameras are better)")
+            print(compare_reports(before, report))
     if cleaning is not None:  # (the predictor cleans the raw depths itself; this call is for the saved mask and the normalisation)
         from mvtracker_amd import clean_depths
         norm_depths, keep = clean_depths(s["depths"].float(), s["intrs"], s["extrs"], cleaning)

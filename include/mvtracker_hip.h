@@ -926,6 +926,81 @@ int mvt_voxel_insert(const float* xyz, long long P, long long* state, long long*
 int mvt_voxel_emit(const float* xyz, long long P, const long long* state, long long* table, long long capacity, int* block_counts,
                    float* points, int* counts, int* first, int* labels, int* n_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Reprojection check: a z-buffered render of points into cameras, and scores of the render against the camera's own frame and
+ * depth map (reference: conversions/droid/reproject_depth_into_videos.py render_dense_pointcloud, and
+ * conversions/droid/debug/compare_photometric_error.py compute_mse / compute_psnr / compute_mae / compute_ssim).
+ *
+ * THE RENDERING RULE.  A source point is three fp32 world coordinates X = (x, y, z); a camera is fp32 intr K (3,3) and extr E (3,4),
+ * world -> camera.  All arithmetic is fp64 with every product, sum and quotient rounded on its own (no fused multiply-add):
+ *   c_r = ((E[r][0] x + E[r][1] y) + E[r][2] z) + E[r][3]                      r = 0, 1, 2
+ *   uf  = (c_0 fx) / c_2 + cx,   vf = (c_1 fy) / c_2 + cy                       fx, fy, cx, cy = K00, K11, K02, K12 (skew ignored)
+ * The point is drawn when X is finite, c_2 > (double)min_depth (strict), uf and vf are finite with |uf|, |vf| < 2^31, and with
+ * u = (int)uf, v = (int)vf (truncation TOWARD ZERO, the reference's astype(int32): uf in (-1, 0) lands in column 0) 0 <= u < W and
+ * 0 <= v < H.  A pixel's value is the minimum over its points of the 64-bit key (bits of (float)c_2) << 32 | source index: the
+ * nearest point, and among points of equal fp32 depth the lowest index; one unsigned 64-bit atomicMin per point and pixel, so the
+ * result does not depend on the order of arrival.  An empty pixel keeps the key ~0.  (A c_2 beyond the fp32 range is drawn with
+ * depth +inf, behind every finite one.)  splat = s in {1, 3, 5}: the same key goes to the s x s pixels centred on (u, v), clipped to
+ * the image -- a depth-tested point sprite (the centre must lie in the image).
+ * keys: [n_targets][H W] 64-bit words, set to ~0 by mvt_reproject_clear before the splats that share them.
+ * One render is  mvt_reproject_clear (a memset, no launch) -> mvt_reproject_splat_* (1 launch) -> mvt_reproject_resolve (1 launch).
+ * --------------------------------------------------------------------------------------------- */
+#define MVT_REPROJECT_MAX_TARGETS 16
+/* keys[0..n) = ~0 (hipMemsetAsync of 0xFF on the stream). */
+int mvt_reproject_clear(unsigned long long* keys, long long n, void* stream);
+/* The clip form: the source points are the pixels of frame t of depths [V][T][1][H][W], read in place (conf: the same layout or
+ * NULL), each valid as in mvt_clean_points (depth finite and > 0, conf > conf_thresh, point finite) with exactly its point bits
+ * (mvt_unproject at stride 1 through kinv / einv [V T][9] / [V T][12] of mvt_invert_cameras); no cloud is materialised.  Rendered
+ * into n_targets cameras at once: target k is view target_views[k] (HOST array) with the camera intrs [k][9], extrs [k][12] (device,
+ * fp32).  exclude_self: target k takes no point of source view target_views[k] ("others", the leave-one-out of the alignment);
+ * otherwise every view's ("all").  Source index = view H W + y W + x.  V H W < 2^31, 1 <= n_targets <= MVT_REPROJECT_MAX_TARGETS,
+ * min_depth finite and >= 0.  1 launch: one thread per source pixel, a loop over the targets. */
+int mvt_reproject_splat_depths(const float* depths, const float* conf, const float* kinv, const float* einv, int V, int T, int t, int H,
+                               int W, float conf_thresh, const int* target_views, int n_targets, const float* intrs, const float* extrs,
+                               int exclude_self, float min_depth, int splat, unsigned long long* keys, void* stream);
+/* The list form: points [M][3] fp32 into n_targets cameras; source index = row.  0 < M < 2^31.  1 launch. */
+int mvt_reproject_splat_points(const float* points, long long M, int n_targets, const float* intrs, const float* extrs, int H, int W,
+                               float min_depth, int splat, unsigned long long* keys, void* stream);
+/* Per pixel of target k: index (int32; -1: empty), depth (fp32: the key's high word; 0: empty, the project's "no depth") and color
+ * (uint8, planar [3][H W]; (0,0,0): empty), target k at image k * target_stride of each output (index / depth [.][H W], color
+ * [.][3][H W]).  The colour is gathered from frame t of rgbs [V][T][3][H][W] in place (clip form; uint8 when rgb_u8, else fp32, a
+ * value becoming min(max(rintf(x), 0), 255)) or from colors [M][3] uint8 (list form; rgbs NULL).  1 launch. */
+int mvt_reproject_resolve(const unsigned long long* keys, int n_targets, int H, int W, const void* rgbs, int rgb_u8, int V, int T, int t,
+                          const unsigned char* colors, long long M, long long target_stride, int* index, float* depth, unsigned char* color,
+                          void* stream);
+/* Scores of n image pairs: a [n][3][H W] the renders, b [n][3][H W] the real frames (each uint8 or fp32 by its flag, an fp32 value
+ * converted by the rule above), with the renders' index / depth [n][H W] and the targets' own depth maps target_depth [n][H W].
+ * scores [n][MVT_SCORE_WORDS] 64-bit words:
+ *   N = H W; COVERED = pixels with index >= 0 (int64); SSE, SAE = sums over pixels and the 3 channels of (a - b)^2 and |a - b|
+ *   (uint64, exact); SSE_COV, SAE_COV the same over the covered pixels; SSIM, SSIM_COV = the sum of the SSIM map over all / the
+ *   covered pixels (double); N_DEPTH = covered pixels whose target depth is finite and > 0; N_CLOSE = of those,
+ *   fabs((double)zr - (double)zt) <= (double)depth_tol; DEPTH_SAE, DEPTH_SAE_CLOSE = the sum of |zr - zt| over the N_DEPTH / the
+ *   N_CLOSE pixels (double).  Words 12..15 are 0.
+ * SSIM is the reference's compute_ssim with OpenCV's parameters: grey Y = (4899 R + 9617 G + 1868 B + 8192) >> 14 on the 8-bit
+ * values; the maps x, y, x^2, y^2, xy blurred in fp64 with the separable 11-tap Gaussian exp(-(i - 5)^2 / 4.5) normalised to sum 1,
+ * border reflect-101; C1 = 6.5025, C2 = 58.5225; ssim = ((2 mu1 mu2 + C1)(2 s12 + C2)) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)).
+ * One workgroup per 16 x 16 tile (a 5-pixel halo in LDS) writes one record to partial [n][mvt_photometric_blocks(H, W)]
+ * [MVT_SCORE_WORDS]; a second launch adds an image's records in an order fixed by their number (no float atomics: the same bits in
+ * every run).  H, W >= 6 (one reflection reaches the halo), n <= 65535.  2 launches. */
+#define MVT_SCORE_WORDS 16
+#define MVT_SCORE_N 0
+#define MVT_SCORE_COVERED 1
+#define MVT_SCORE_SSE 2
+#define MVT_SCORE_SAE 3
+#define MVT_SCORE_SSE_COV 4
+#define MVT_SCORE_SAE_COV 5
+#define MVT_SCORE_SSIM 6
+#define MVT_SCORE_SSIM_COV 7
+#define MVT_SCORE_N_DEPTH 8
+#define MVT_SCORE_N_CLOSE 9
+#define MVT_SCORE_DEPTH_SAE 10
+#define MVT_SCORE_DEPTH_SAE_CLOSE 11
+/* Records per image of mvt_photometric_score's workspace (host arithmetic, no launch); -1 for a size it refuses. */
+int mvt_photometric_blocks(int H, int W);
+int mvt_photometric_score(const void* a, int a_u8, const void* b, int b_u8, const int* index, const float* depth,
+                          const float* target_depth, int n, int H, int W, float depth_tol, unsigned long long* partial,
+                          unsigned long long* scores, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,12 @@ SIGNATURES = {
     "mvt_voxel_bounds": [P, LL, C.c_double, P, P, P],
     "mvt_voxel_insert": [P, LL, P, P, LL, P],
     "mvt_voxel_emit": [P, LL, P, P, LL, P, P, P, P, P, P, P],
+    "mvt_reproject_clear": [P, LL, P],
+    "mvt_reproject_splat_depths": [P, P, P, P, I, I, I, I, I, F, P, I, P, P, I, F, I, P, P],
+    "mvt_reproject_splat_points": [P, LL, I, P, P, I, I, F, I, P, P],
+    "mvt_reproject_resolve": [P, I, I, I, P, I, I, I, I, P, LL, LL, P, P, P, P],
+    "mvt_photometric_blocks": [I, I],
+    "mvt_photometric_score": [P, I, P, I, P, P, P, I, I, I, F, P, P, P],
 }
 _RET = {"mvt_build_arch": C.c_char_p, "mvt_encoder_workspace_bytes": C.c_longlong, "mvt_updateformer_workspace_bytes": C.c_longlong,
         "mvt_updateformer_grouped_workspace_bytes": C.c_longlong}
@@ -1056,3 +1062,87 @@ def voxel_emit(xyz, Pn, state, table, capacity, block_counts, points, counts, fi
     assert labels is None or (labels.dtype == torch.int32 and labels.numel() >= Pn)
     _call("mvt_voxel_emit", _ptr(xyz), Pn, _ptr(state), _ptr(table), capacity, _ptr(block_counts), _ptr(points), _ptr(counts), _ptr(first),
           _ptr(labels), _ptr(n_out), _stream())
+
+
+# ------------------------------------------------------------------ reprojection check (mvtracker_amd/reproject.py drives these)
+REPROJECT_MAX_TARGETS, SCORE_WORDS = 16, 16  # MVT_REPROJECT_MAX_TARGETS, MVT_SCORE_WORDS
+(SCORE_N, SCORE_COVERED, SCORE_SSE, SCORE_SAE, SCORE_SSE_COV, SCORE_SAE_COV, SCORE_SSIM, SCORE_SSIM_COV, SCORE_N_DEPTH, SCORE_N_CLOSE,
+ SCORE_DEPTH_SAE, SCORE_DEPTH_SAE_CLOSE) = range(12)  # MVT_SCORE_*
+SCORE_DOUBLES = (SCORE_SSIM, SCORE_SSIM_COV, SCORE_DEPTH_SAE, SCORE_DEPTH_SAE_CLOSE)
+
+
+def _cams_check(intrs, extrs, n):
+    assert intrs.dtype == extrs.dtype == torch.float32 and intrs.is_contiguous() and extrs.is_contiguous()
+    assert intrs.numel() >= n * 9 and extrs.numel() >= n * 12
+
+
+def reproject_clear(keys, n):
+    """keys[:n] = ~0: the empty z-buffer (int64 words, a memset on the stream)."""
+    assert keys.dtype == torch.int64 and keys.is_contiguous() and keys.numel() >= n
+    _call("mvt_reproject_clear", _ptr(keys), n, _stream())
+
+
+def reproject_splat_depths(depths, conf, kinv, einv, V, T, t, H, W, conf_thresh, target_views, intrs, extrs, exclude_self, min_depth, splat,
+                           keys):
+    """Frame t of depths (V,T,1,H,W) [conf: the same layout or None] into the cameras intrs (n, 9) / extrs (n, 12) of the views
+    ``target_views`` (host integers): keys (n, H*W) int64 words take the minimum."""
+    n = len(target_views)
+    assert depths.is_contiguous() and depths.dtype == torch.float32 and depths.numel() == V * T * H * W
+    assert conf is None or (conf.is_contiguous() and conf.dtype == torch.float32 and conf.numel() == V * T * H * W)
+    assert keys.dtype == torch.int64 and keys.is_contiguous() and keys.numel() >= n * H * W
+    _cams_check(intrs, extrs, n)
+    tv = (C.c_int * max(1, n))(*[int(v) for v in target_views])
+    _call("mvt_reproject_splat_depths", _ptr(depths), _ptr(conf), _ptr(_f32c(kinv)), _ptr(_f32c(einv)), V, T, t, H, W,
+          0.0 if conf_thresh is None else conf_thresh, C.cast(tv, C.c_void_p), n, _ptr(intrs), _ptr(extrs), int(exclude_self), min_depth, splat,
+          _ptr(keys), _stream())
+
+
+def reproject_splat_points(points, M, n_targets, intrs, extrs, H, W, min_depth, splat, keys):
+    """points (M, 3) fp32 into n_targets cameras: keys (n_targets, H*W) int64 words take the minimum; the index is the row."""
+    assert points.dtype == torch.float32 and points.is_contiguous() and points.numel() >= M * 3
+    assert keys.dtype == torch.int64 and keys.is_contiguous() and keys.numel() >= n_targets * H * W
+    _cams_check(intrs, extrs, n_targets)
+    _call("mvt_reproject_splat_points", _ptr(points), M, n_targets, _ptr(intrs), _ptr(extrs), H, W, min_depth, splat, _ptr(keys), _stream())
+
+
+def reproject_resolve(keys, n_targets, H, W, index, depth, color, target_stride=1, rgbs=None, V=0, T=0, t=0, colors=None):
+    """keys -> index (int32), depth (fp32), color (uint8, planar), target k at image k * target_stride of each; the colour from frame t
+    of rgbs (V,T,3,H,W) uint8 / fp32 (clip form) or from colors (M, 3) uint8 (list form)."""
+    need = ((n_targets - 1) * target_stride + 1) * H * W
+    assert keys.dtype == torch.int64 and keys.is_contiguous() and keys.numel() >= n_targets * H * W
+    assert index.dtype == torch.int32 and depth.dtype == torch.float32 and color.dtype == torch.uint8
+    assert index.is_contiguous() and depth.is_contiguous() and color.is_contiguous()
+    assert index.numel() >= need and depth.numel() >= need and color.numel() >= 3 * need
+    assert (rgbs is None) != (colors is None)
+    M = 0
+    if colors is not None:
+        assert colors.dtype == torch.uint8 and colors.is_contiguous() and colors.dim() == 2 and colors.shape[1] == 3
+        M = colors.shape[0]
+    else:
+        assert rgbs.dtype in (torch.uint8, torch.float32) and rgbs.is_contiguous() and rgbs.numel() == V * T * 3 * H * W
+    _call("mvt_reproject_resolve", _ptr(keys), n_targets, H, W, _ptr(rgbs), int(rgbs is not None and rgbs.dtype == torch.uint8), V, T, t,
+          _ptr(colors), M, target_stride, _ptr(index), _ptr(depth), _ptr(color), _stream())
+
+
+def photometric_blocks(H, W):
+    """Workspace records per image of ``photometric_score``; raises for a size it refuses (H, W >= 6)."""
+    n = _lib.mvt_photometric_blocks(H, W)
+    if n <= 0:
+        raise HipError(f"mvt_photometric_blocks refused {H} x {W} (the SSIM window needs H, W >= 6)")
+    return n
+
+
+def photometric_score(a, b, index, depth, target_depth, n, H, W, depth_tol, scores, partial=None):
+    """scores (n, SCORE_WORDS) int64 words (the SCORE_DOUBLES are doubles: ``scores.view(torch.float64)``) of the renders a against
+    the frames b, both (n, 3, H, W) uint8 / fp32, with the renders' index / depth (n, H, W) and the targets' depth maps."""
+    for img in (a, b):
+        assert img.dtype in (torch.uint8, torch.float32) and img.is_contiguous() and img.numel() >= n * 3 * H * W
+    assert index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n * H * W
+    assert depth.dtype == target_depth.dtype == torch.float32 and depth.is_contiguous() and target_depth.is_contiguous()
+    assert depth.numel() >= n * H * W and target_depth.numel() >= n * H * W
+    assert scores.dtype == torch.int64 and scores.is_contiguous() and scores.numel() >= n * SCORE_WORDS
+    if partial is None:
+        partial = torch.empty(n * photometric_blocks(H, W) * SCORE_WORDS, dtype=torch.int64, device=scores.device)
+    assert partial.dtype == torch.int64 and partial.is_contiguous() and partial.numel() >= n * max(1, _lib.mvt_photometric_blocks(H, W)) * SCORE_WORDS
+    _call("mvt_photometric_score", _ptr(a), int(a.dtype == torch.uint8), _ptr(b), int(b.dtype == torch.uint8), _ptr(index), _ptr(depth),
+          _ptr(target_depth), n, H, W, depth_tol, _ptr(partial), _ptr(scores), _stream())

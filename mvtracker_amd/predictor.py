@@ -107,6 +107,8 @@ class EvaluationPredictor(torch.nn.Module):
         self._stream_pool = {}
         self.last_scene_transform = None  # the SceneTransform of the last forward / open_stream (None: the scene went in as it was)
         self.last_camera_correction = None  # the CameraCorrection of the last forward (None: the cameras went in as they were)
+        # the ReprojectionReport of the cameras the last forward tracked with, and of the uncorrected ones when it also aligned them
+        self.last_reprojection_report = self.last_reprojection_report_before = None
         self.model.eval()
 
     # ---- helpers -------------------------------------------------------------------------
@@ -172,9 +174,14 @@ class EvaluationPredictor(torch.nn.Module):
             depths_conf=None,
             depth_cleaning=None,
             camera_alignment=None,
+            reprojection_check=None,
             **kwargs,
     ):
-        """``camera_alignment``: a ``CameraAlignment`` (the views are refined against each other by ``mvtracker_amd.align_cameras`` on
+        """``reprojection_check``: a ``ReprojectionCheck``: the cameras the tracker is about to use (after depth cleaning and camera
+        alignment, before normalisation and resize) are judged by ``mvtracker_amd.reprojection_report`` and the report is kept as
+        ``last_reprojection_report``; with ``camera_alignment`` the report of the uncorrected cameras is kept too, as
+        ``last_reprojection_report_before``.  Nothing the tracker reads is changed.  None: not one launch.
+        ``camera_alignment``: a ``CameraAlignment`` (the views are refined against each other by ``mvtracker_amd.align_cameras`` on
         the raw inputs after depth cleaning, so ``max_distance`` is in the caller's units) or a ready ``CameraCorrection``; everything
         below sees ``correction.apply(extrs)``, and the correction is kept as ``last_camera_correction``.  None: not one launch.
         ``depth_cleaning``: a ``DepthCleaning``: every (view, frame) depth map is cleaned of outliers first
@@ -218,7 +225,14 @@ class EvaluationPredictor(torch.nn.Module):
             else:
                 raise ValueError(f"camera_alignment must be None, a CameraAlignment or a CameraCorrection, got {camera_alignment!r}")
             self.last_camera_correction = correction
-            extrs = correction.apply(extrs)
+            extrs_uncorrected, extrs = extrs, correction.apply(extrs)
+        self.last_reprojection_report = self.last_reprojection_report_before = None
+        if reprojection_check is not None:  # after the cleaning and the alignment, before the normalisation and the resize
+            from . import reproject
+            if camera_alignment is not None:
+                self.last_reprojection_report_before = reproject.reprojection_report(rgbs, depths, intrs, extrs_uncorrected, reprojection_check,
+                                                                                     depths_conf=depths_conf)
+            self.last_reprojection_report = reproject.reprojection_report(rgbs, depths, intrs, extrs, reprojection_check, depths_conf=depths_conf)
         # scene normalisation, from the raw inputs (a nearest resize with rescaled intrinsics keeps world points); the support
         # points below are built from the transformed depths and cameras, so they need nothing of their own
         xf = self._scene_transform(scene_transform, (depths, intrs, extrs, depths_conf))
