@@ -49,6 +49,15 @@ def build_parser():
     ap.add_argument("--num-queries", type=int, default=1000, metavar="N", help="queries drawn by --sample-queries")
     ap.add_argument("--region", type=float, nargs=3, default=(2.1, -0.1, 4.2), metavar=("R", "ZMIN", "ZMAX"),
                     help="cylinder of --sample-queries around the z axis: radius and z range")
+    ap.add_argument("--query-region-box", type=float, nargs=6, default=None, metavar=("XLO", "XHI", "YLO", "YHI", "ZLO", "ZHI"),
+                    help="with --sample-queries: draw the queries from the largest cluster of points inside this box around "
+                         "--query-region-pose, per view (mvtracker_amd.region_masks, the reference's classify_gripper_points on the device)")
+    ap.add_argument("--query-region-pose", type=float, nargs=16, default=None, metavar="M",
+                    help="world_T_region, 16 numbers row by row (default: the identity)")
+    ap.add_argument("--query-region-pose-key", default=None, metavar="NAME",
+                    help="name of an array (T, 4, 4) or (4, 4) world_T_region in the sample NPZ, instead of --query-region-pose")
+    ap.add_argument("--query-region-eps", type=float, default=0.03, help="DBSCAN neighbourhood radius, in the clip's own units")
+    ap.add_argument("--query-region-min-samples", type=int, default=12, help="DBSCAN: neighbours (itself included) of a core point")
     ap.add_argument("--normalize-scene", choices=["none", "auto"], default="none",
                     help="auto: centre the scene, lift its floor to z = 0 and rescale it to the size the weights were trained on "
                          "(mvtracker_amd.auto_scene_normalization on frame 0); tracks are saved in the clip's own world")
@@ -135,8 +144,37 @@ def reprojection_check_from_args(args):
                              depth_tol=args.reproject_depth_tol)
 
 
+def query_region_from_args(args, temporal_stride=1):
+    """(RegionCluster, world_T_region poses) of the --query-region-* flags, or (None, None)."""
+    given = args.query_region_box is not None or args.query_region_pose is not None or args.query_region_pose_key is not None
+    if not given:
+        return None, None
+    if args.sample_queries is None:
+        raise SystemExit("--query-region-* flags need --sample-queries")
+    if args.query_region_box is None:
+        raise SystemExit("--query-region-pose / --query-region-pose-key need --query-region-box")
+    if args.query_region_pose is not None and args.query_region_pose_key is not None:
+        raise SystemExit("give --query-region-pose or --query-region-pose-key, not both")
+    from mvtracker_amd import RegionCluster
+    b = args.query_region_box
+    region = RegionCluster(box=((b[0], b[1]), (b[2], b[3]), (b[4], b[5])), eps=args.query_region_eps, min_samples=args.query_region_min_samples)
+    if args.query_region_pose_key is not None:
+        if not args.sample_path:
+            raise SystemExit("--query-region-pose-key needs --sample-path")
+        with np.load(args.sample_path) as f:
+            if args.query_region_pose_key not in f.files:
+                raise SystemExit(f"{args.sample_path} has no array {args.query_region_pose_key!r}")
+            poses = np.asarray(f[args.query_region_pose_key], np.float64)
+        if poses.ndim == 3:
+            poses = poses[::temporal_stride]
+    else:
+        poses = np.eye(4) if args.query_region_pose is None else np.asarray(args.query_region_pose, np.float64).reshape(4, 4)
+    return region, poses
+
+
 def main():
     args = build_parser().parse_args()
+    region, region_poses = query_region_from_args(args, args.temporal_stride)  # (flag errors before any work)
     if not torch.cuda.is_available():
         raise SystemExit("demo_amd.py needs an MI355X: the tracker has no CPU path")
     from mvtracker_amd import sample_io, synth
@@ -196,8 +234,13 @@ def main():
     if args.sample_queries is not None:
         from mvtracker_amd import sample_queries
         r, zmin, zmax = args.region
-        s["query_points_3d"] = sample_queries(s["depths"], s["intrs"], s["extrs"],
-                                              [(0, zmin, zmax, r, args.num_queries, "kmeans" if args.sample_queries == "kmeans" else "")])
+        spec = [(0, zmin, zmax, r, args.num_queries, "kmeans" if args.sample_queries == "kmeans" else "")]
+        reports = {}
+        s["query_points_3d"] = sample_queries(s["depths"], s["intrs"], s["extrs"], spec, region=region, region_poses=region_poses,
+                                              region_reports=reports)
+        for t, report in sorted(reports.items()):
+            print(f"query region, frame {t}:", report.summary())
+            print(report.table())
     elif args.random_query_points or s["query_points_3d"].shape[1] == 0:
         s["query_points_3d"] = random_queries(s["depths"].float(), s["intrs"], s["extrs"])
     xf = None

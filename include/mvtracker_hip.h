@@ -1001,6 +1001,45 @@ int mvt_photometric_score(const void* a, int a_u8, const void* b, int b_u8, cons
                           const float* target_depth, int n, int H, int W, float depth_tol, unsigned long long* partial,
                           unsigned long long* scores, void* stream);
 
+/* ---- region clustering (csrc/cloud_cluster.hip; mvtracker_amd/cluster.py drives these) ----
+ * DBSCAN of C clouds xyz (C, P, 4) fp32 per launch, NaN rows taking no part; grid = (w, h) of organised clouds padded to whole 8x8
+ * patches (w * h = P) or (0, 0) for point lists; tile_box / group_box from mvt_tile_aabb / mvt_tile_group_aabb of the same
+ * clouds (after the crop).  Two points are neighbours when the scan's fp32 d2 <= r2 (a point is its own neighbour); r2 is given
+ * as such, rounded once by the caller.  A point is core with >= min_samples neighbours; clusters are the connected components of
+ * the core points, numbered in ascending order of their lowest core index; a non-core point with core neighbours takes the lowest
+ * cluster number among them; every other point is -1.  The results depend on the clouds alone: the same bits in every run.
+ * state: MVT_CLUSTER_STATE_WORDS int64 per cloud on the device. */
+#define MVT_CLUSTER_CANDIDATES 0   /* points taking part */
+#define MVT_CLUSTER_CORE 1         /* core points */
+#define MVT_CLUSTER_CLUSTERS 2     /* clusters */
+#define MVT_CLUSTER_CHOSEN 3       /* id of the largest cluster (the lowest id among equal sizes), -1 without one */
+#define MVT_CLUSTER_CHOSEN_SIZE 4  /* its points, border points included */
+#define MVT_CLUSTER_NOISE 5        /* points taking part with label -1 */
+#define MVT_CLUSTER_FALLBACK 6     /* 0, or why `select` is not the largest cluster: */
+#define MVT_CLUSTER_STATUS 7       /* MVT_CLUSTER_BOUND: a union-find loop exceeded its bound (written by mvt_cluster_link) */
+#define MVT_CLUSTER_STATE_WORDS 8
+#define MVT_CLUSTER_FEW 1    /* fewer than min_samples points: all of them are selected */
+#define MVT_CLUSTER_NONE 2   /* no cluster: every point taking part is selected */
+#define MVT_CLUSTER_EMPTY 3  /* no point takes part: nothing is selected */
+#define MVT_CLUSTER_BOUND 1
+/* In place: a point of cloud c whose coordinates region_T_world[c] (3x4 fp32 rows on the device, fused multiply-adds x, y, z in
+ * turn onto the translation) are not strictly inside bounds (6 floats on the HOST: lo, hi per axis) becomes a NaN row. */
+int mvt_cluster_crop(float* xyz, int C, long long P, const float* region_T_world, const float* bounds, void* stream);
+/* core (C, P) uint8: 1 where the point has >= min_samples neighbours (the count stops there), 0 elsewhere and on NaN rows. */
+int mvt_cluster_count(const float* xyz, int C, long long P, int grid_w, int grid_h, float r2, int min_samples, const float* tile_box,
+                      const float* group_box, unsigned char* core, void* stream);
+/* parent (C, P) int32: for core points the lowest core index of their component (a lock-free min-index union-find over the core
+ * neighbours, then flattened); state rows are cleared and word MVT_CLUSTER_STATUS written.  3 launches. */
+int mvt_cluster_link(const float* xyz, int C, long long P, int grid_w, int grid_h, float r2, const float* tile_box, const float* group_box,
+                     const unsigned char* core, int* parent, long long* state, void* stream);
+/* root (C, P) int32: parent for core points, the lowest parent among the core neighbours for the others, -1 without one. */
+int mvt_cluster_border(const float* xyz, int C, long long P, int grid_w, int grid_h, float r2, const float* tile_box, const float* group_box,
+                       const unsigned char* core, const int* parent, int* root, void* stream);
+/* labels (C, P) int32, select (C, P) uint8 (the largest cluster, or the fallback's points) and words 0..6 of the state rows.
+ * sizes: workspace (C, P) int32, cleared here. */
+int mvt_cluster_finish(const float* xyz, int C, long long P, int min_samples, const unsigned char* core, const int* root, int* sizes,
+                       int* labels, unsigned char* select, long long* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

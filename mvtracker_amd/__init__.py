@@ -1,6 +1,6 @@
 """MI355X-native multi-view point-tracking forward path (drop-in for mvtracker.models' predictor).
 
-    from mvtracker_amd import MVTracker, EvaluationPredictor, load_mvtracker, sample_queries, auto_scene_normalization, DepthCleaning, clean_depths, CameraAlignment, align_cameras, estimate_normals, voxel_downsample, ReprojectionCheck, reprojection_report
+    from mvtracker_amd import MVTracker, EvaluationPredictor, load_mvtracker, sample_queries, auto_scene_normalization, DepthCleaning, clean_depths, CameraAlignment, align_cameras, estimate_normals, voxel_downsample, ReprojectionCheck, reprojection_report, RegionCluster, region_masks, cluster_points
 
 ``synth`` (numpy only) can be imported without the HIP library; everything else loads
 libmvtracker_hip.so on import and raises if it is missing -- there is no CPU fallback.
@@ -9,7 +9,8 @@ __all__ = ["MVTracker", "EvaluationPredictor", "load_mvtracker", "hip", "synth",
            "sample_queries", "kmeans_centres", "DEFAULT_SPEC", "scene", "SceneTransform", "auto_scene_normalization", "clean", "DepthCleaning", "clean_depths",
            "clean_point_cloud", "align", "CameraAlignment", "PcaCameraAlignment", "CameraCorrection", "align_cameras", "align_point_clouds", "cloud",
            "estimate_normals", "voxel_downsample", "reproject", "ReprojectionCheck", "ReprojectionReport", "reprojection_report", "reproject_views",
-           "render_point_cloud", "compare_reports"]
+           "render_point_cloud", "compare_reports", "cluster", "RegionCluster", "RegionReport", "cluster_points", "select_region_points",
+           "region_masks"]
 
 
 def __getattr__(name):
@@ -40,7 +41,10 @@ def __getattr__(name):
     if name in ("ReprojectionCheck", "ReprojectionReport", "reprojection_report", "reproject_views", "render_point_cloud", "compare_reports"):
         from . import reproject
         return getattr(reproject, name)
-    if name in ("hip", "synth", "sample_io", "adapter", "geometry", "parallel", "queries", "scene", "clean", "align", "cloud", "reproject"):
+    if name in ("RegionCluster", "RegionReport", "cluster_points", "select_region_points", "region_masks"):
+        from . import cluster
+        return getattr(cluster, name)
+    if name in ("hip", "synth", "sample_io", "adapter", "geometry", "parallel", "queries", "scene", "clean", "align", "cloud", "reproject", "cluster"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

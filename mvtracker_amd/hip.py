@@ -127,6 +127,11 @@ SIGNATURES = {
     "mvt_reproject_resolve": [P, I, I, I, P, I, I, I, I, P, LL, LL, P, P, P, P],
     "mvt_photometric_blocks": [I, I],
     "mvt_photometric_score": [P, I, P, I, P, P, P, I, I, I, F, P, P, P],
+    "mvt_cluster_crop": [P, I, LL, P, P, P],
+    "mvt_cluster_count": [P, I, LL, I, I, F, I, P, P, P, P],
+    "mvt_cluster_link": [P, I, LL, I, I, F, P, P, P, P, P, P],
+    "mvt_cluster_border": [P, I, LL, I, I, F, P, P, P, P, P, P],
+    "mvt_cluster_finish": [P, I, LL, I, P, P, P, P, P, P, P],
 }
 _RET = {"mvt_build_arch": C.c_char_p, "mvt_encoder_workspace_bytes": C.c_longlong, "mvt_updateformer_workspace_bytes": C.c_longlong,
         "mvt_updateformer_grouped_workspace_bytes": C.c_longlong}
@@ -1146,3 +1151,59 @@ def photometric_score(a, b, index, depth, target_depth, n, H, W, depth_tol, scor
     assert partial.dtype == torch.int64 and partial.is_contiguous() and partial.numel() >= n * max(1, _lib.mvt_photometric_blocks(H, W)) * SCORE_WORDS
     _call("mvt_photometric_score", _ptr(a), int(a.dtype == torch.uint8), _ptr(b), int(b.dtype == torch.uint8), _ptr(index), _ptr(depth),
           _ptr(target_depth), n, H, W, depth_tol, _ptr(partial), _ptr(scores), _stream())
+
+
+# ------------------------------------------------------------------ region clustering (mvtracker_amd/cluster.py drives these)
+CLUSTER_CANDIDATES, CLUSTER_CORE, CLUSTER_CLUSTERS, CLUSTER_CHOSEN, CLUSTER_CHOSEN_SIZE, CLUSTER_NOISE, CLUSTER_FALLBACK, CLUSTER_STATUS = range(8)
+CLUSTER_STATE_WORDS = 8  # MVT_CLUSTER_*
+CLUSTER_FEW, CLUSTER_NONE, CLUSTER_EMPTY = 1, 2, 3
+
+
+def _cluster_check(xyz, Cn, Pn, box, gbox, core):
+    nt = (Pn + 63) // 64
+    assert xyz.dtype == torch.float32 and xyz.is_contiguous() and xyz.numel() >= Cn * Pn * 4
+    assert box.dtype == torch.float32 and box.numel() >= Cn * nt * 8 and gbox.dtype == torch.float32 and gbox.numel() >= Cn * ((nt + 63) // 64) * 8
+    assert core.dtype == torch.uint8 and core.is_contiguous() and core.numel() >= Cn * Pn
+
+
+def cluster_crop(xyz, Cn, Pn, region_T_world, bounds):
+    """In place: points of the Cn clouds xyz (Cn, Pn, 4) that are not strictly inside ``bounds`` = (xlo, xhi, ylo, yhi, zlo, zhi)
+    in the frame region_T_world (Cn, 3, 4) fp32 become NaN rows."""
+    assert xyz.dtype == torch.float32 and xyz.is_contiguous() and xyz.numel() >= Cn * Pn * 4
+    assert region_T_world.dtype == torch.float32 and region_T_world.is_contiguous() and region_T_world.numel() >= Cn * 12
+    b = (C.c_float * 6)(*[float(v) for v in bounds])
+    _call("mvt_cluster_crop", _ptr(xyz), Cn, Pn, _ptr(region_T_world), b, _stream())
+
+
+def cluster_count(xyz, Cn, Pn, grid, r2, min_samples, box, gbox, core):
+    """core (Cn, Pn) uint8 <- 1 where a point of xyz (Cn, Pn, 4) has at least min_samples points (itself included) with d2 <= r2."""
+    _cluster_check(xyz, Cn, Pn, box, gbox, core)
+    _call("mvt_cluster_count", _ptr(xyz), Cn, Pn, grid[0], grid[1], r2, min_samples, _ptr(box), _ptr(gbox), _ptr(core), _stream())
+
+
+def cluster_link(xyz, Cn, Pn, grid, r2, box, gbox, core, parent, state):
+    """parent (Cn, Pn) int32 <- for core points the lowest core index of their component; state (Cn, CLUSTER_STATE_WORDS) int64 is
+    cleared and its status word written."""
+    _cluster_check(xyz, Cn, Pn, box, gbox, core)
+    assert parent.dtype == torch.int32 and parent.is_contiguous() and parent.numel() >= Cn * Pn
+    assert state.dtype == torch.int64 and state.is_contiguous() and state.numel() >= Cn * CLUSTER_STATE_WORDS
+    _call("mvt_cluster_link", _ptr(xyz), Cn, Pn, grid[0], grid[1], r2, _ptr(box), _ptr(gbox), _ptr(core), _ptr(parent), _ptr(state), _stream())
+
+
+def cluster_border(xyz, Cn, Pn, grid, r2, box, gbox, core, parent, root):
+    """root (Cn, Pn) int32 <- parent for core points, the lowest parent among the core neighbours for the others, -1 without one."""
+    _cluster_check(xyz, Cn, Pn, box, gbox, core)
+    for t in (parent, root):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= Cn * Pn
+    _call("mvt_cluster_border", _ptr(xyz), Cn, Pn, grid[0], grid[1], r2, _ptr(box), _ptr(gbox), _ptr(core), _ptr(parent), _ptr(root), _stream())
+
+
+def cluster_finish(xyz, Cn, Pn, min_samples, core, root, sizes, labels, select, state):
+    """labels (Cn, Pn) int32, select (Cn, Pn) uint8 and words 0..6 of state; sizes (Cn, Pn) int32 is workspace."""
+    assert xyz.dtype == torch.float32 and xyz.is_contiguous() and xyz.numel() >= Cn * Pn * 4
+    assert core.dtype == torch.uint8 and core.numel() >= Cn * Pn and select.dtype == torch.uint8 and select.numel() >= Cn * Pn
+    for t in (root, sizes, labels):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= Cn * Pn
+    assert state.dtype == torch.int64 and state.is_contiguous() and state.numel() >= Cn * CLUSTER_STATE_WORDS
+    _call("mvt_cluster_finish", _ptr(xyz), Cn, Pn, min_samples, _ptr(core), _ptr(root), _ptr(sizes), _ptr(labels), _ptr(select), _ptr(state),
+          _stream())

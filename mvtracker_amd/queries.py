@@ -112,20 +112,59 @@ def kmeans_centres(points, count, seed=0, max_iter=300, tol=1e-4):
     return w["centres"], info
 
 
+def _region_mask(d, conf, intrs, extrs, t, region, poses):
+    """(mask (V,1,1,H,W) bool, RegionReport) of frame t: ``cluster.region_clip`` on that frame alone."""
+    from . import cluster
+    pose = None
+    if region.box is not None:
+        p = torch.as_tensor(poses)
+        pose = p if p.dim() == 2 else p[t]
+    return cluster.region_clip(d[:, t:t + 1], intrs[:, t:t + 1], extrs[:, t:t + 1], pose, region, None if conf is None else conf[:, t:t + 1])
+
+
+def _region_pool(d, conf, mask, kinv, einv, t, conf_threshold, centre, radius, z_min, z_max, radius_inclusive):
+    """``frame_pool`` of frame t with the pixels outside ``mask`` taken out: the frame is copied with depth 0 (and confidence -inf)
+    there, so the pool's rule and order are the unrestricted pool's."""
+    V, T = d.shape[:2]
+    d_t = torch.where(mask, d[:, t:t + 1], torch.zeros((), device=d.device)).contiguous()
+    conf_t = None if conf is None else torch.where(mask, conf[:, t:t + 1], torch.full((), -math.inf, device=d.device)).contiguous()
+    return frame_pool(d_t, kinv.reshape(V, T, 9)[:, t].contiguous(), einv.reshape(V, T, 12)[:, t].contiguous(), 0, conf_t, conf_threshold, centre,
+                      radius, z_min, z_max, radius_inclusive)
+
+
 @hip.guarded
-def sample_queries(depths, intrs, extrs, spec, depths_conf=None, conf_threshold=0.9, centre=(0.0, 0.0), seed=0, radius_inclusive=False):
+def sample_queries(depths, intrs, extrs, spec, depths_conf=None, conf_threshold=0.9, centre=(0.0, 0.0), seed=0, radius_inclusive=False,
+                   region=None, region_poses=None, region_reports=None):
     """Query points (1, N, 4) = (t, x, y, z) in world space for a clip depths (1,V,T,1,H,W), intrs (1,V,T,3,3), extrs (1,V,T,3,4).
 
     ``spec``: the reference's rows (t, z_min, z_max, radius, count, method).  A row's pool: the pixels of frame t of all views whose
     confidence exceeds ``conf_threshold`` (``depths_conf`` (1,V,T,1,H,W); without it: whose depth is positive) and that lie in the
     cylinder (x-cx)^2 + (y-cy)^2 < radius^2 (``radius_inclusive``: <=, demo.py's rule), z_min <= z <= z_max around ``centre``.
     method "": a seeded permutation of the pool (CPU generator), its first ``count`` rows; "kmeans": the k-means centres, a pool of
-    at most ``count`` points whole.  Rows with t >= T or an empty pool are skipped; rows are concatenated in spec order."""
+    at most ``count`` points whole.  Rows with t >= T or an empty pool are skipped; rows are concatenated in spec order.
+
+    ``region`` (a ``cluster.RegionCluster``) with ``region_poses`` ((4, 4) or (T, 4, 4) world_T_region): a row's pool is restricted,
+    before the draw or the k-means, to the pixels of frame t that ``cluster.region_masks`` selects: the largest cluster inside the
+    region's box, per view.  The two confidence rules are applied one after the other: which pixels enter the clustered cloud is the
+    region's own rule (depth > 0, and with ``region.conf_thresh`` set: conf > region.conf_thresh), so with ``region.conf_thresh``
+    None the cluster forms over pixels of any confidence; ``conf_threshold`` then drops pixels from the pool as it does without a
+    region.  A frame's mask is computed once, whatever the number of rows that name it; ``region_reports``: a dict that receives
+    {t: RegionReport} of those frames.  Without a region nothing of that runs."""
     if depths.dim() != 6 or depths.shape[0] != 1 or depths.shape[3] != 1:
         raise ValueError(f"depths must be (1, V, T, 1, H, W), got {tuple(depths.shape)}")
     for row in spec:
         if row[5] not in ("", "kmeans"):
             raise NotImplementedError(f"sampling method {row[5]!r} (the reference knows '' and 'kmeans')")
+    if region is not None:  # (refused before any launch)
+        from . import cluster
+        if not isinstance(region, cluster.RegionCluster):
+            raise ValueError(f"region must be a RegionCluster, got {region!r}")
+        if region.box is not None:
+            if region_poses is None:
+                raise ValueError("a region with a box needs region_poses: (4, 4) or (T, 4, 4) world_T_region")
+            cluster.invert_poses(region_poses, depths.shape[2])
+    elif region_poses is not None:
+        raise ValueError("region_poses without a region")
     hip.require_device(depths)
     _, V, T, _, H, W = depths.shape
     dev = depths.device
@@ -139,10 +178,18 @@ def sample_queries(depths, intrs, extrs, spec, depths_conf=None, conf_threshold=
                        kinv, einv, V * T)
     g = torch.Generator(device="cpu").manual_seed(int(seed))
     out = []
+    masks = {}  # frame -> (mask, report): rows that share a frame share the mask
     for i, (t, z_min, z_max, radius, count, method) in enumerate(spec):
         if t >= T:
             continue
-        pool = frame_pool(d, kinv, einv, t, conf, conf_threshold, centre, radius, z_min, z_max, radius_inclusive)
+        if region is None:
+            pool = frame_pool(d, kinv, einv, t, conf, conf_threshold, centre, radius, z_min, z_max, radius_inclusive)
+        else:
+            if t not in masks:
+                masks[t] = _region_mask(d, conf, intrs[0], extrs[0], t, region, region_poses)
+                if region_reports is not None:
+                    region_reports[t] = masks[t][1]
+            pool = _region_pool(d, conf, masks[t][0], kinv, einv, t, conf_threshold, centre, radius, z_min, z_max, radius_inclusive)
         if pool.shape[0] == 0:
             continue
         if method == "":
