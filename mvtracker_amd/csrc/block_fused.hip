@@ -56,6 +56,7 @@ template <int NMB> struct Cfg {
   static_assert(BM * LDA <= 2 * BM * LDH, "attention tile fits the H buffers");
 };
 constexpr int YLD = 40;   // bf16 row stride of the projection staging tile (32 columns + 8 pad)
+constexpr int NBIAS_DEAL = 4 * 256 + 256;  // bias floats of a tile's projections side by side (the product's 576 + 288 + 288)
 constexpr int FS = 512;   // elements per (32-row block, k-step) weight fragment: [64 lanes][8 bf16], see mvt_pack_frag_bf16
 
 // Diagnostic build only (-DMVT_STAMPS, tools/stamp_block.py): s_memtime at the phase boundaries of workgroups 0 and 100, one
@@ -112,6 +113,9 @@ struct BlockArgs {
   int ldw1, ldw2, H;
   mvt_block_next next[MVT_BLOCK_MAX_NEXT];    // follow-up projections of LayerNorm(x)
   int n_next;
+  // the follow-up projections as one work list over the waves (plan_deal, section 3 of the kernel): deal = 0 keeps the sequential
+  // loop; deal_img[q] = LayerNorm image (0 / 1) of projection q, deal_rep[k] = a projection that carries image k's parameters
+  int deal, deal_img[MVT_BLOCK_MAX_NEXT], deal_rep[2];
   int att_bf16;              // att is a bf16 tensor
   long long M;
   float* ws;                 // split path (small M): [M][C] x after the projection, then [H/256][M][C] partial MLP outputs
@@ -537,7 +541,7 @@ __device__ __forceinline__ void attn_compute(const AttnFrags<NMBQ, NKB>& f, int 
 // of a block normalise the same x with different eps / affine: the statistics exchange and its barrier run once).
 template <int NMB>
 __device__ __forceinline__ void ln_to_lds(const f32x16 (&v)[NMB], unsigned short* Xs, float* st, int wave, int lane, float eps,
-                                          const float* lnw, const float* lnb, float (&ms)[NMB][2], bool have) {
+                                          const float* lnw, const float* lnb, float (&ms)[NMB][2], bool have, bool sync = true) {
   constexpr int BM = 32 * NMB;
   const int r = lane & 31, h = lane >> 5;
   // the affine parameters of this wave's channel slice are requested first: their memory round trip passes under the statistics
@@ -597,7 +601,33 @@ __device__ __forceinline__ void ln_to_lds(const f32x16 (&v)[NMB], unsigned short
       *reinterpret_cast<u32x2*>(&Xs[(mb * 32 + r) * LDX + n]) = __builtin_bit_cast(u32x2, b);
     }
   }
-  lds_barrier();
+  if (sync) lds_barrier();  // (!sync: the caller writes a second image first, one barrier for both)
+}
+
+// One 32-column block of a follow-up projection, all rows of the tile: + bias, bf16, out through the wave's staging tile
+// (token on the lane -> 16 bytes per lane, a row's 32 columns leave as one 64-B piece).  grow(row): global row of a tile row or -1.
+template <int NM, class GR>
+__device__ __forceinline__ void proj_store(const f32x16 (&acc)[NM], unsigned short* tile, const float* bias, unsigned short* yb,
+                                           int ldy, long long row_lo, long long row_hi, GR grow, int lane) {
+  const int r = lane & 31, h = lane >> 5;
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+  for (int mb = 0; mb < NM; ++mb)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      f32x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = acc[mb][4 * g + e] + bias[8 * g + 4 * h + e];
+      *reinterpret_cast<u32x2*>(&tile[(mb * 32 + r) * YLD + 8 * g + 4 * h]) = __builtin_bit_cast(u32x2, __builtin_convertvector(o, bf16x4));
+    }
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+  for (int k = 0; k < NM * 2; ++k) {
+    const int pc = lane + 64 * k, row = pc >> 2, c = pc & 3;
+    const long long m = grow(row);
+    if (m >= row_lo && m < row_hi)
+      *reinterpret_cast<u32x4*>(yb + m * (long long)ldy + c * 8) = *reinterpret_cast<const u32x4*>(&tile[row * YLD + c * 8]);
+  }
 }
 
 // MODE 0: the whole block in one workgroup per row tile.
@@ -625,7 +655,12 @@ __global__ __launch_bounds__(NT) void block_fused_bf16(BlockArgs p) {
   __shared__ __attribute__((aligned(16))) unsigned short Xs[BM * LDX];
   __shared__ __attribute__((aligned(16))) unsigned short Hs[2][HSZ];
   __shared__ float st[8 * BM * 2];
-  __shared__ __attribute__((aligned(16))) float b1s[4 * C];
+  // DEAL: the forms whose follow-up projections run as ONE work list over the 8 waves (section 3): a second LayerNorm image next to
+  // Xs, and room for the biases of every projection of a tile side by side (the product's mixed tile: 576 + 288 + 288 columns)
+  constexpr bool DEAL = MODE == 0 || MODE == 3;
+  constexpr int NBIAS = DEAL ? NBIAS_DEAL : 4 * C;
+  __shared__ __attribute__((aligned(16))) unsigned short Xs2[DEAL ? BM * LDX : 8];
+  __shared__ __attribute__((aligned(16))) float b1s[NBIAS];
   __shared__ __attribute__((aligned(16))) float cbs[CTX ? 2 * 288 : 4];  // bias of the context's k|v projection
 
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
@@ -679,6 +714,24 @@ __global__ __launch_bounds__(NT) void block_fused_bf16(BlockArgs p) {
   auto ws_off = [&](int chunk, int g) -> long long { return ((((long long)chunk * ws_ntile + ws_tile) * 8 + wave) * 4 + g) * 256 + lane * 4; };
   // a projection runs in this workgroup when its row range meets the workgroup's rows (workgroup-uniform)
   auto active = [&](int q) { return q < p.n_next && rlo < p.next[q].row_hi && rhi > p.next[q].row_lo; };
+  // What section 3's work list needs of the projections' arguments, gathered HERE into one scalar: read where they are used, behind
+  // the first LayerNorm, these argument loads were a chain of dependent scalar loads (~2 k cycles in the stamps) in front of the
+  // MLP; here they leave together, with the kernel's other arguments.  Bits 8q..8q+7: 32-column blocks of projection q if it meets the tile's
+  // rows, 24 / 25: the tile needs LayerNorm image 0 / 1, 26: the list applies (plan_deal on the host).
+  static_assert(MVT_BLOCK_MAX_NEXT == 3, "three projections in the packed scalar and in the selects of section 3");
+  unsigned d_pack = 0;
+  if constexpr (DEAL) {
+#pragma unroll
+    for (int q = 0; q < MVT_BLOCK_MAX_NEXT; ++q) {  // (static indices, see section 3)
+      // active(q), branch-free and on unconditional loads (unused projections are zero-filled): as `a && b && c` every term was its
+      // own load - wait - branch, seven dependent scalar loads at the start of the kernel
+      const long long lo = p.next[q].row_lo, hi = p.next[q].row_hi;
+      const unsigned nb = (unsigned)(p.next[q].N >> 5) & 0xFFu, im = p.deal_img[q] ? 1u << 25 : 1u << 24;
+      const bool on = (q < p.n_next) & (rlo < hi) & (rhi > lo);
+      d_pack |= ((nb << (8 * q)) | im) & (0u - (unsigned)on);  // (a mask, not a select: a select put the loads behind a branch again)
+    }
+    d_pack |= p.deal ? 1u << 26 : 0u;
+  }
   bf16x8 wq[PFQ];  // the weight-fragment queue, chained through the MLP and the follow-up projections
   // 32-row tiles (the 768 virtual-token rows, pure latency chains) have registers to spare: the first 16 weight fragments the
   // wave will consume are requested HERE, so their memory round trip (the ~40 MB of updater weights do not live in L2) overlaps
@@ -1199,7 +1252,49 @@ __global__ __launch_bounds__(NT) void block_fused_bf16(BlockArgs p) {
   float ln_ms[NMB][2];
   if (HAS_MLP) ln_to_lds<NMB>(v, Xs, st, wave, lane, 1e-6f, nullptr, nullptr, ln_ms, false);  // ends with a barrier: Hs is free again
   STAMP(6);
-  const bool tail_next = MODE == 0 && active(0) && wave < (p.next[0].N + 31) / 32;
+  // The follow-up projections of the tile as ONE flat list of (projection, 32-column block) items, dealt to the 8 waves: item wave,
+  // wave + 8, ...  Dealt projection by projection (the sequential loop below) the time block's point tile ran 3 + 2 rounds for
+  // 18 + 9 blocks, with a barrier, a bias restage and a LayerNorm restage in between; as one list its 27 items are 4 rounds.
+  // (Cutting the last round's items by 32-row block to fill more waves was measured and bought nothing: a round costs the same
+  // 3-4 k cycles whatever its fill)  Every item is the same gemm_wq chain over K = 256 as before: the outputs
+  // do not change by a bit.
+  // The host decides whether the list applies and groups the projections by LayerNorm image (plan_deal); what depends on the tile
+  // -- which projections meet its rows -- is in d_pack (kernel start).
+  const int wv = __builtin_amdgcn_readfirstlane(wave);
+  int d_nb[MVT_BLOCK_MAX_NEXT], d_first[MVT_BLOCK_MAX_NEXT];  // column blocks of projection q in this tile (0: not here), its first item
+  int d_T = 0;
+#pragma unroll
+  for (int q = 0; q < MVT_BLOCK_MAX_NEXT; ++q) {
+    d_nb[q] = (int)((d_pack >> (8 * q)) & 0xFFu);
+    d_first[q] = d_T;
+    d_T += d_nb[q];
+  }
+  const bool d_im0 = (d_pack >> 24) & 1u, d_im1 = (d_pack >> 25) & 1u;  // the images the tile needs
+  // (a tile with ONE projection keeps the sequential loop: its deal is the same wave, wave + 8, ... and the list's extra scalar work
+  //  measured 1 us slower per launch there -- the input projection and the point<-virtual block)
+  const bool dealt = DEAL && ((d_pack >> 26) & 1u) && (d_nb[0] > 0) + (d_nb[1] > 0) + (d_nb[2] > 0) >= 2;
+  // item i -> its projection and column block
+  auto item_q = [&](int i, int& nb) {
+    int q = 0;
+    nb = i;
+#pragma unroll
+    for (int qq = 0; qq + 1 < MVT_BLOCK_MAX_NEXT; ++qq)
+      if (q == qq && nb >= d_nb[qq]) {
+        nb -= d_nb[qq];
+        q = qq + 1;
+      }
+    return q;
+  };
+  auto item_wrow = [&](int i) {
+    int nb;
+    const int q = item_q(i, nb);
+    const unsigned short* w = q == 0 ? p.next[0].w : q == 1 ? p.next[1].w : p.next[2].w;
+    return w + ((long long)nb * (C / 16) * 64 + lane) * 8;
+  };
+  // this wave's items: wv, wv + 8, ... (d_full of them)
+  const int d_full = (d_T >> 3) + (wv < (d_T & 7) ? 1 : 0);
+  const int d_head = d_full > 0 ? wv : -1;  // first item (-1: none)
+  const bool tail_next = !dealt && MODE == 0 && active(0) && wave < (p.next[0].N + 31) / 32;
   if (HAS_MLP) {
     f32x16 acc2[NMB];
 #pragma unroll
@@ -1212,7 +1307,7 @@ __global__ __launch_bounds__(NT) void block_fused_bf16(BlockArgs p) {
     const unsigned short* w1row = p.w1 + ((long long)jb * (C / 16) * 64 + lane) * 8;                 // + c * 4 blocks
     const unsigned short* w2row = p.w2 + ((long long)wave * (p.H / 16) * 64 + lane) * 8;             // + c * (HC/16) k-steps
     static_assert(HC / 16 == PFQ && C / 16 == PFQ, "every GEMM segment is exactly one queue length");
-    const unsigned short* tail = tail_next ? p.next[0].w + ((long long)wave * (C / 16) * 64 + lane) * 8 : w1row;
+    const unsigned short* tail = dealt && d_head >= 0 ? item_wrow(d_head) : tail_next ? p.next[0].w + ((long long)wave * (C / 16) * 64 + lane) * 8 : w1row;
     // ONE fragment queue for the whole MLP: the wave consumes fc1(c0), fc2(c0), fc1(c1), ... strictly in this order, 16
     // k-steps each, so the queue always holds the next 16 fragments of that sequence (>= 16 MFMA k-steps of lookahead,
     // which is what an L2 round trip needs; two half-depth queues left every fragment ~250 cycles short)
@@ -1295,9 +1390,68 @@ __global__ __launch_bounds__(NT) void block_fused_bf16(BlockArgs p) {
   // ---- 3. optional follow-up projections: y_i = LayerNorm_i(x) . Wn_i^T + bn_i
   bool have = tail_next || early_have;  // the queue already holds this wave's first block of the projection
   bool have_ms = false;
+  if (dealt) {
+    if constexpr (DEAL) {
+      lds_barrier();  // every wave is done reading Xs / Hs
+      // the biases go through LDS (see below), side by side: the 32 values of item i at b1s[32 i]
+#pragma unroll
+      for (int q = 0; q < MVT_BLOCK_MAX_NEXT; ++q)
+        if (d_nb[q] > 0)
+          for (int i = t; i < p.next[q].N; i += NT) b1s[d_first[q] * 32 + i] = p.next[q].b[i];
+      // (MODE 0: fc2 left the queue holding the first item's fragments)
+      if (MODE != 0 && d_head >= 0) fill_wq(wq, item_wrow(d_head));
+      STAMP(32);
+      // the tile's LayerNorm images at once: one statistics exchange, one barrier after the last image
+      if (d_im0) {
+        const int q0 = p.deal_rep[0];
+        const float* lnw = q0 == 0 ? p.next[0].lnw : q0 == 1 ? p.next[1].lnw : p.next[2].lnw;
+        const float* lnb = q0 == 0 ? p.next[0].lnb : q0 == 1 ? p.next[1].lnb : p.next[2].lnb;
+        const float eps = q0 == 0 ? p.next[0].eps : q0 == 1 ? p.next[1].eps : p.next[2].eps;
+        ln_to_lds<NMB>(v, Xs, st, wave, lane, eps, lnw, lnb, ln_ms, false, !d_im1);
+      }
+      if (d_im1) {  // (never projection 0: the first projection has image 0)
+        const int q1 = p.deal_rep[1];
+        const float* lnw = q1 == 1 ? p.next[1].lnw : p.next[2].lnw;
+        const float* lnb = q1 == 1 ? p.next[1].lnb : p.next[2].lnb;
+        const float eps = q1 == 1 ? p.next[1].eps : p.next[2].eps;
+        ln_to_lds<NMB>(v, Xs2, st, wave, lane, eps, lnw, lnb, ln_ms, d_im0, true);
+      }
+      STAMP(33);
+      unsigned short* tile = &Hs[0][0] + wave * (NMB * 32 * YLD);  // wave-private staging tile
+      // per item: the projection's y, row range and image (wave-uniform selects, static indices)
+      auto item_y = [&](int q, int nb) {
+        float* y = q == 0 ? p.next[0].y : q == 1 ? p.next[1].y : p.next[2].y;
+        return reinterpret_cast<unsigned short*>(y) + nb * 32;
+      };
+      auto item_ldy = [&](int q) { return q == 0 ? p.next[0].ldy : q == 1 ? p.next[1].ldy : p.next[2].ldy; };
+      auto item_lo = [&](int q) { return q == 0 ? p.next[0].row_lo : q == 1 ? p.next[1].row_lo : p.next[2].row_lo; };
+      auto item_hi = [&](int q) { return q == 0 ? p.next[0].row_hi : q == 1 ? p.next[1].row_hi : p.next[2].row_hi; };
+      auto item_xs = [&](int q) {
+        const int im = q == 0 ? p.deal_img[0] : q == 1 ? p.deal_img[1] : p.deal_img[2];
+        return (im ? &Xs2[0] : &Xs[0]) + r * LDX + 8 * h;
+      };
+#pragma unroll 1
+      for (int k = 0; k < d_full; ++k) {
+        const int i = wv + 8 * k;
+        int nb;
+        const int q = item_q(i, nb);
+        const int inext = k + 1 < d_full ? i + 8 : -1;
+        const unsigned short* row = item_wrow(i);
+        f32x16 acc[NMB];
+#pragma unroll
+        for (int mb = 0; mb < NMB; ++mb)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) acc[mb][e] = 0.f;
+        gemm_wq<C / 16, NMB>(acc, wq, row, inext >= 0 ? item_wrow(inext) : row, item_xs(q), LDX, 0);
+        STAMP(34 + (k < 4 ? k : 4));
+        proj_store<NMB>(acc, tile, &b1s[32 * i], item_y(q, nb), item_ldy(q), item_lo(q), item_hi(q), grow, lane);
+      }
+      STAMP(39);
+    }
+  }
 #pragma unroll
   for (int q = 0; q < MVT_BLOCK_MAX_NEXT; ++q) {  // static indices: a dynamically indexed kernel-argument array would live in scratch
-    if (q >= p.n_next) break;
+    if (q >= p.n_next || dealt) break;
     if (!active(q)) continue;  // (have is false here: a chain is only set up towards an active projection)
     const mvt_block_next nx = p.next[q];
     lds_barrier();  // every wave is done reading Xs / Hs
@@ -1406,6 +1560,35 @@ extern "C" int mvt_debug_clear_stamps() {
 }
 #endif
 
+// MVT_PROJ_SEQ=1: the follow-up projections one after another instead of dealt as one work list (A/B runs; read on every call)
+static inline int proj_seq_switch() {
+  const char* e = getenv("MVT_PROJ_SEQ");
+  return e && atoi(e) != 0;
+}
+// Plans the dealt pass of a launch's follow-up projections (a.next filled): every projection on the staged bf16 store path (whole
+// 32-column blocks, 16-byte rows), at most two distinct LayerNorm images (lnw, lnb, eps) -- the kernels hold two -- and all the
+// biases side by side in LDS.  Otherwise, and in the forms that do not deal (pass 2 of the split path), the sequential loop runs.
+static void plan_deal(BlockArgs& a) {
+  a.deal = 0;
+  if (proj_seq_switch() || a.n_next == 0) return;
+  int nimg = 0, total = 0;
+  for (int q = 0; q < a.n_next; ++q) {
+    const mvt_block_next& nx = a.next[q];
+    if (!nx.y_bf16 || (nx.N & 31) || (nx.ldy & 7) || ((uintptr_t)nx.y & 15)) return;
+    int im = -1;
+    for (int qq = 0; qq < q && im < 0; ++qq)
+      if (a.next[qq].lnw == nx.lnw && a.next[qq].lnb == nx.lnb && a.next[qq].eps == nx.eps) im = a.deal_img[qq];
+    if (im < 0) {
+      if (nimg == 2) return;
+      im = nimg++;
+      a.deal_rep[im] = q;
+    }
+    a.deal_img[q] = im;
+    total += nx.N;
+  }
+  if (total <= NBIAS_DEAL) a.deal = 1;
+}
+
 extern "C" int mvt_pack_frag_bf16(const unsigned short* w, int ld, int N, int K, unsigned short* out, void* stream) {
   MVT_REQUIRE(w && out && N > 0 && K > 0 && K % 16 == 0 && ld % 8 == 0 && ld >= K);
   MVT_REQUIRE(((uintptr_t)w % 16 == 0) && ((uintptr_t)out % 16 == 0));
@@ -1436,6 +1619,7 @@ extern "C" int mvt_block_fused_bf16(float* x, int ldx, const void* att, int att_
     a.next[q] = nx;
     if (nx.row_hi == 0) a.next[q].row_hi = M;
   }
+  plan_deal(a);
   static const char* force = getenv("MVT_BLOCK_NMB");  // tuning override
   const int nmb = force ? atoi(force) : (M >= 4096 ? 2 : 1);  // 64-row workgroups measured 1.6x faster than 128-row ones at M = 12288
   static const bool no_split = getenv("MVT_BLOCK_NOSPLIT") != nullptr;
@@ -1479,6 +1663,7 @@ extern "C" int mvt_attn_block_fused_bf16(float* x, int ldx, const mvt_block_attn
     a.next[q] = nx;
     if (nx.row_hi == 0) a.next[q].row_hi = M;
   }
+  plan_deal(a);
   const int S = attn->S;
   if (attn->kind == MVT_ATTN_TIME) {
     // tiles of whole tracks: S <= 32 keys per track (one MFMA key block), 64 / S tracks per 64-row tile
@@ -1516,7 +1701,7 @@ extern "C" int mvt_attn_block_fused_bf16(float* x, int ldx, const mvt_block_attn
     // sooner -- a whole updater call 929 -> 882 us (tools/time_updater.py 512).  MVT_FRAME_NMB1=0: the 64-token tiles.
     // Only while the 32-token tiles still fit ONE round of workgroups at one per CU (680 tracks: 264 workgroups, 927 -> 1 026 us).
     static const bool small_tiles = !(getenv("MVT_FRAME_NMB1") && atoi(getenv("MVT_FRAME_NMB1")) == 0);
-    if (ntok * S >= 4096 && small_tiles && mvt_cdiv(ntok, 32) * S <= 256) {
+    if (small_tiles && mvt_frame_small_tiles(ntok, S)) {
       MVT_REQUIRE(!workspace);
       hipLaunchKernelGGL((block_fused_bf16<1, 0, 2>), dim3((unsigned)mvt_cdiv(ntok, 32), 1, (unsigned)S), dim3(NT), 0, mvt_stream(stream), a);
     } else if (ntok * S >= 4096) {
@@ -1576,6 +1761,7 @@ extern "C" int mvt_input_proj_bf16(const float* tokens, int ldtok, int token_dim
     a.next[q] = nx;
     if (nx.row_hi == 0) a.next[q].row_hi = M;
   }
+  plan_deal(a);
   hipLaunchKernelGGL((block_fused_bf16<2, 3, 4>), dim3((unsigned)mvt_cdiv(M, 64)), dim3(NT), 0, mvt_stream(stream), a);
   return mvt_launch_status();
 }
@@ -1604,6 +1790,7 @@ extern "C" int mvt_token_input_proj_bf16(const float* coords, const float* fcorr
     a.next[q] = nx;
     if (nx.row_hi == 0) a.next[q].row_hi = M;
   }
+  plan_deal(a);
   hipLaunchKernelGGL((block_fused_bf16<2, 3, 4>), dim3((unsigned)mvt_cdiv(M, 64)), dim3(NT), 0, mvt_stream(stream), a);
   return mvt_launch_status();
 }
@@ -1625,6 +1812,7 @@ extern "C" int mvt_ln_proj_bf16(const float* x, int ldx, const mvt_block_next* n
     if (nx.row_hi == 0) a.next[q].row_hi = M;
     maxblk = (nx.N + 31) / 32 > maxblk ? (nx.N + 31) / 32 : maxblk;
   }
+  plan_deal(a);
   if (M >= 4096)  // whole 64-row tiles, every column block in the workgroup: x and its LayerNorm are read / computed once per tile
     hipLaunchKernelGGL((block_fused_bf16<2, 3, 0>), dim3((unsigned)mvt_cdiv(M, 64)), dim3(NT), 0, mvt_stream(stream), a);
   else

@@ -24,6 +24,11 @@ static inline hipStream_t mvt_stream(void* s) { return (hipStream_t)s; }
 
 static inline long long mvt_cdiv(long long a, long long b) { return (a + b - 1) / b; }
 
+// The small-M rule of the point<-virtual block (mvt_attn_block_fused_bf16, MVT_ATTN_FRAME), in one place for the kernel's entry and
+// for the updater's launch sequence, which must agree on it: 32-token tiles while the block has at least 4 096 rows and the tiles
+// still fit ONE round of workgroups at one per CU.
+static inline bool mvt_frame_small_tiles(long long ntok, long long S) { return ntok * S >= 4096 && mvt_cdiv(ntok, 32) * S <= 256; }
+
 __device__ __forceinline__ float mvt_gelu_tanh(float x) {
   // 0.5 x (1 + tanh(k)) = x * sigmoid(2k), k = sqrt(2/pi) (x + 0.044715 x^3).  ocml tanhf costs ~150 instructions
   // and dominated the fc1 epilogue; v_exp_f32 + v_rcp_f32 are 1-ulp hardware ops (relative error ~2e-7).

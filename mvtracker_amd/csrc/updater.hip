@@ -175,7 +175,7 @@ static int updater_run(const mvt_updater_weights* w, const float* x, int ldx, co
   //  the same rule as in mvt_attn_block_fused_bf16 -- that block runs on them, twice the workgroups, and the virtual-self block keeps
   //  its own second launch: measured faster at 400 / 512 tracks, 958 -> 906 / 929 -> 882 us per call)
   static const bool small_m = !(getenv("MVT_FRAME_NMB1") && atoi(getenv("MVT_FRAME_NMB1")) == 0);
-  const bool small_form = small_m && (long long)n * S >= 4096 && (long long)((n + 31) / 32) * S <= 256;
+  const bool small_form = small_m && mvt_frame_small_tiles(n, S);
   const bool fold_vs = (w->fuse_attention & 32) && !grouped && fuse_p2v && fuse_vs && (long long)n * S >= 4096 && !small_form && MLP / 256 <= 4 &&
                        8 * ((n + 63) / 64) >= (3 * INNER + 31) / 32;
 
