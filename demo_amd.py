@@ -58,6 +58,17 @@ def build_parser():
                     help="name of an array (T, 4, 4) or (4, 4) world_T_region in the sample NPZ, instead of --query-region-pose")
     ap.add_argument("--query-region-eps", type=float, default=0.03, help="DBSCAN neighbourhood radius, in the clip's own units")
     ap.add_argument("--query-region-min-samples", type=int, default=12, help="DBSCAN: neighbours (itself included) of a core point")
+    ap.add_argument("--query-motion", choices=["moving", "static"], default=None,
+                    help="with --sample-queries: draw the queries from the pixels that move (or from the static background), found from "
+                         "the frames alone (mvtracker_amd.motion_masks, the reference's _static_bg_mask_from_window on the device)")
+    ap.add_argument("--query-motion-window", type=int, default=None, metavar="W",
+                    help="frames to either side of the query frame whose differences count (default: the whole clip)")
+    ap.add_argument("--query-motion-radius", type=int, default=None, metavar="R", help="a pixel moves when one within R pixels does (default 7)")
+    ap.add_argument("--query-motion-thresh", type=float, default=None, metavar="D",
+                    help="channel-mean frame difference from which a pixel moves, in the frames' own units (default 10, for 0..255 frames)")
+    ap.add_argument("--print-motion", action="store_true",
+                    help="print the clip's motion report (static share per view and frame, mean frame differences) and its static "
+                         "prefix: the leading frames before anything moves (the reference demo's _detect_static_prefix_frames)")
     ap.add_argument("--normalize-scene", choices=["none", "auto"], default="none",
                     help="auto: centre the scene, lift its floor to z = 0 and rescale it to the size the weights were trained on "
                          "(mvtracker_amd.auto_scene_normalization on frame 0); tracks are saved in the clip's own world")
@@ -172,9 +183,27 @@ def query_region_from_args(args, temporal_stride=1):
     return region, poses
 
 
+def query_motion_from_args(args):
+    """(MotionMask, which side the queries are drawn from) of the --query-motion* flags, or (None, "moving")."""
+    details = (args.query_motion_window, args.query_motion_radius, args.query_motion_thresh)
+    if args.query_motion is None:
+        if any(v is not None for v in details):
+            raise SystemExit("--query-motion-window / -radius / -thresh need --query-motion")
+        return None, "moving"
+    if args.sample_queries is None:
+        raise SystemExit("--query-motion needs --sample-queries")
+    from mvtracker_amd import MotionMask
+    kw = {k: v for k, v in zip(("window", "patch_radius", "diff_thresh"), details) if v is not None}
+    try:
+        return MotionMask(**kw), args.query_motion
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+
+
 def main():
     args = build_parser().parse_args()
     region, region_poses = query_region_from_args(args, args.temporal_stride)  # (flag errors before any work)
+    motion, motion_keep = query_motion_from_args(args)
     if not torch.cuda.is_available():
         raise SystemExit("demo_amd.py needs an MI355X: the tracker has no CPU path")
     from mvtracker_amd import sample_io, synth
@@ -231,16 +260,25 @@ def main():
         from mvtracker_amd import clean_depths
         norm_depths, keep = clean_depths(s["depths"].float(), s["intrs"], s["extrs"], cleaning)
         print(f"depth cleaning ({args.clean_depths}): {int((~keep & (s['depths'] > 0)).sum())} of {int((s['depths'] > 0).sum())} valid pixels removed")
+    if args.print_motion:
+        from mvtracker_amd import MotionMask, motion_masks
+        report = motion_masks(s["rgbs"], motion if motion is not None else MotionMask())[1]
+        print("motion:", report.summary())
+        print(report.table())
+        print("static prefix frames:", report.static_prefix_frames())
     if args.sample_queries is not None:
         from mvtracker_amd import sample_queries
         r, zmin, zmax = args.region
         spec = [(0, zmin, zmax, r, args.num_queries, "kmeans" if args.sample_queries == "kmeans" else "")]
-        reports = {}
+        reports, motion_reports = {}, {}
         s["query_points_3d"] = sample_queries(s["depths"], s["intrs"], s["extrs"], spec, region=region, region_poses=region_poses,
-                                              region_reports=reports)
+                                              region_reports=reports, motion=motion, rgbs=s["rgbs"] if motion is not None else None,
+                                              motion_keep=motion_keep, motion_reports=motion_reports)
         for t, report in sorted(reports.items()):
             print(f"query region, frame {t}:", report.summary())
             print(report.table())
+        for report in motion_reports.values():
+            print(f"query motion ({motion_keep} pixels):", report.summary())
     elif args.random_query_points or s["query_points_3d"].shape[1] == 0:
         s["query_points_3d"] = random_queries(s["depths"].float(), s["intrs"], s["extrs"])
     xf = None

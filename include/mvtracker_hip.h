@@ -1040,6 +1040,34 @@ int mvt_cluster_border(const float* xyz, int C, long long P, int grid_w, int gri
 int mvt_cluster_finish(const float* xyz, int C, long long P, int min_samples, const unsigned char* core, const int* root, int* sizes,
                        int* labels, unsigned char* select, long long* state, void* stream);
 
+/* ---- motion masks (csrc/motion.hip; mvtracker_amd/motion.py drives these) ----
+ * Static-background detection on a clip rgbs (V, T, 3, H, W), planar, uint8 or fp32 (reference:
+ * mvtracker/datasets/generic_scene_dataset.py _static_bg_mask_from_window, demo.py _detect_static_prefix_frames).  The diff of
+ * boundary b (frames b, b + 1) at a pixel is d_b = ((|dc0| + |dc1|) + |dc2|) / 3.0f in fp32 with an IEEE division, uint8 values
+ * converted first; change[v, t, y, x] is the maximum of d_b over b in [t - win, t + win - 1] n [0, T - 2] and over the patch
+ * |dy|, |dx| <= r clipped to the image; a pixel is static when change < thresh.  A NaN diff wins every maximum.
+ * T >= 2, V * T <= 65535, H * W < 2^31 - 1024.  No atomics: the same bits in every run. */
+#define MVT_MOTION_BLOCK_PIXELS 1024 /* pixels of one plane per workgroup of mvt_motion_temporal */
+#define MVT_MOTION_TILE_W 64         /* mask pixels per workgroup of mvt_motion_mask */
+#define MVT_MOTION_TILE_H 32
+#define MVT_MOTION_MAX_RADIUS 15
+/* Workgroups per view of mvt_motion_temporal / tiles per image of mvt_motion_mask (host arithmetic, no launch); -1 for a size
+ * they refuse. */
+int mvt_motion_blocks(int H, int W);
+int mvt_motion_tiles(int H, int W);
+/* One pass over the frames, each read once.  all_mode: out (V, H, W) = the maximum of d_b over every boundary; otherwise out
+ * (V, T-1, H, W) = every d_b.  partial (V * mvt_motion_blocks, T-1) fp64: per workgroup and boundary the sum of
+ * |dc0| + |dc1| + |dc2| over its pixels (exact on integer-valued frames). */
+int mvt_motion_temporal(const void* rgbs, int is_u8, int V, int T, int H, int W, int all_mode, float* out, double* partial, void* stream);
+/* mask (V, T, H, W) one byte per pixel, 1 = static.  win >= 1: src = the (V, T-1, H, W) diffs, the window's maximum is taken
+ * while a tile is staged; win == 0: src = the (V, H, W) maximum of all_mode, pooled once and written to all T frames.
+ * 0 <= r <= MVT_MOTION_MAX_RADIUS.  counts (V * T or, win == 0, V; mvt_motion_tiles) int32: static pixels per tile. */
+int mvt_motion_mask(const float* src, int V, int T, int H, int W, int win, int r, float thresh, unsigned char* mask, int* counts,
+                    void* stream);
+/* report (T-1 + V * T) fp64: the T-1 sums of partial's columns, then the static pixels of every (view, frame) from counts (laid
+ * out as mvt_motion_mask wrote them: all_mode = its win == 0), each added in an order fixed by the number of terms. */
+int mvt_motion_report(const double* partial, const int* counts, int V, int T, int H, int W, int all_mode, double* report, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,11 @@ SIGNATURES = {
     "mvt_cluster_link": [P, I, LL, I, I, F, P, P, P, P, P, P],
     "mvt_cluster_border": [P, I, LL, I, I, F, P, P, P, P, P, P],
     "mvt_cluster_finish": [P, I, LL, I, P, P, P, P, P, P, P],
+    "mvt_motion_blocks": [I, I],
+    "mvt_motion_tiles": [I, I],
+    "mvt_motion_temporal": [P, I, I, I, I, I, I, P, P, P],
+    "mvt_motion_mask": [P, I, I, I, I, I, I, F, P, P, P],
+    "mvt_motion_report": [P, P, I, I, I, I, I, P, P],
 }
 _RET = {"mvt_build_arch": C.c_char_p, "mvt_encoder_workspace_bytes": C.c_longlong, "mvt_updateformer_workspace_bytes": C.c_longlong,
         "mvt_updateformer_grouped_workspace_bytes": C.c_longlong}
@@ -1207,3 +1212,49 @@ def cluster_finish(xyz, Cn, Pn, min_samples, core, root, sizes, labels, select, 
     assert state.dtype == torch.int64 and state.is_contiguous() and state.numel() >= Cn * CLUSTER_STATE_WORDS
     _call("mvt_cluster_finish", _ptr(xyz), Cn, Pn, min_samples, _ptr(core), _ptr(root), _ptr(sizes), _ptr(labels), _ptr(select), _ptr(state),
           _stream())
+
+
+# ------------------------------------------------------------------ motion masks (mvtracker_amd/motion.py drives these)
+MOTION_MAX_RADIUS = 15  # MVT_MOTION_MAX_RADIUS
+
+
+def motion_blocks(H, W):
+    """Rows per view of ``motion_temporal``'s partial sums; raises for a size it refuses."""
+    n = _lib.mvt_motion_blocks(H, W)
+    if n <= 0:
+        raise HipError(f"mvt_motion_blocks refused {H} x {W}")
+    return n
+
+
+def motion_tiles(H, W):
+    """Counts per image of ``motion_mask``; raises for a size it refuses."""
+    n = _lib.mvt_motion_tiles(H, W)
+    if n <= 0:
+        raise HipError(f"mvt_motion_tiles refused {H} x {W}")
+    return n
+
+
+def motion_temporal(rgbs, V, T, H, W, all_mode, out, partial):
+    """One pass over rgbs (V, T, 3, H, W) uint8 / fp32: out (V, H, W) <- the largest boundary diff (``all_mode``) or out
+    (V, T-1, H, W) <- every boundary's diff; partial (V * motion_blocks(H, W), T-1) fp64 <- the workgroups' sums of |dc0|+|dc1|+|dc2|."""
+    assert rgbs.dtype in (torch.uint8, torch.float32) and rgbs.is_contiguous() and rgbs.numel() == V * T * 3 * H * W
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= V * (1 if all_mode else T - 1) * H * W
+    assert partial.dtype == torch.float64 and partial.is_contiguous() and partial.numel() >= V * motion_blocks(H, W) * (T - 1)
+    _call("mvt_motion_temporal", _ptr(rgbs), int(rgbs.dtype == torch.uint8), V, T, H, W, int(bool(all_mode)), _ptr(out), _ptr(partial), _stream())
+
+
+def motion_mask(src, V, T, H, W, win, r, thresh, mask, counts):
+    """mask (V, T, H, W) bool <- static pixels.  win >= 1: src is ``motion_temporal``'s (V, T-1, H, W); win == 0: its all_mode
+    (V, H, W), pooled once and written to every frame.  counts (V * T or V, motion_tiles(H, W)) int32 <- static pixels per tile."""
+    assert src.dtype == torch.float32 and src.is_contiguous() and src.numel() >= V * (T - 1 if win > 0 else 1) * H * W
+    assert mask.dtype == torch.bool and mask.is_contiguous() and mask.numel() == V * T * H * W
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= V * (T if win > 0 else 1) * motion_tiles(H, W)
+    _call("mvt_motion_mask", _ptr(src), V, T, H, W, win, r, thresh, _ptr(mask), _ptr(counts), _stream())
+
+
+def motion_report(partial, counts, V, T, H, W, all_mode, report):
+    """report (T-1 + V*T) fp64 <- the boundary sums, then the static pixels of every (view, frame), added in a fixed order."""
+    assert partial.dtype == torch.float64 and partial.is_contiguous() and partial.numel() >= V * motion_blocks(H, W) * (T - 1)
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= V * (1 if all_mode else T) * motion_tiles(H, W)
+    assert report.dtype == torch.float64 and report.is_contiguous() and report.numel() >= T - 1 + V * T
+    _call("mvt_motion_report", _ptr(partial), _ptr(counts), V, T, H, W, int(bool(all_mode)), _ptr(report), _stream())

@@ -387,7 +387,9 @@ class EvaluationPredictor(torch.nn.Module):
         """Query points for a clip without labels (``mvtracker_amd.queries.sample_queries``; the evaluator's sampling,
         evaluation/evaluator_3dpt.py:286-388): a (1, N, 4) tensor for ``forward(query_points_3d=...)``, ``open_stream(...)`` or a
         session's ``add_queries(...)``.  The inputs are the clip as ``forward`` takes it; ``interp_shape`` plays no part (a nearest
-        resize with rescaled intrinsics keeps world points, and the queries are in world space)."""
+        resize with rescaled intrinsics keeps world points, and the queries are in world space).  Keyword arguments go through as
+        they are: ``region=`` / ``region_poses=`` put the queries on the thing at a pose, ``motion=`` / ``rgbs=`` / ``motion_keep=`` on
+        what moves (or on the static background)."""
         from . import queries
         return queries.sample_queries(depths, intrs, extrs, queries.DEFAULT_SPEC if spec is None else spec, **kw)
 

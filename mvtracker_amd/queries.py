@@ -134,7 +134,7 @@ def _region_pool(d, conf, mask, kinv, einv, t, conf_threshold, centre, radius, z
 
 @hip.guarded
 def sample_queries(depths, intrs, extrs, spec, depths_conf=None, conf_threshold=0.9, centre=(0.0, 0.0), seed=0, radius_inclusive=False,
-                   region=None, region_poses=None, region_reports=None):
+                   region=None, region_poses=None, region_reports=None, motion=None, rgbs=None, motion_keep="moving", motion_reports=None):
     """Query points (1, N, 4) = (t, x, y, z) in world space for a clip depths (1,V,T,1,H,W), intrs (1,V,T,3,3), extrs (1,V,T,3,4).
 
     ``spec``: the reference's rows (t, z_min, z_max, radius, count, method).  A row's pool: the pixels of frame t of all views whose
@@ -149,7 +149,13 @@ def sample_queries(depths, intrs, extrs, spec, depths_conf=None, conf_threshold=
     region's own rule (depth > 0, and with ``region.conf_thresh`` set: conf > region.conf_thresh), so with ``region.conf_thresh``
     None the cluster forms over pixels of any confidence; ``conf_threshold`` then drops pixels from the pool as it does without a
     region.  A frame's mask is computed once, whatever the number of rows that name it; ``region_reports``: a dict that receives
-    {t: RegionReport} of those frames.  Without a region nothing of that runs."""
+    {t: RegionReport} of those frames.  Without a region nothing of that runs.
+
+    ``motion`` (a ``motion.MotionMask``) with ``rgbs`` (the clip's frames, (1,V,T,3,H,W) or (V,T,3,H,W), uint8 or float): a row's
+    pool is restricted, before the draw or the k-means, to the pixels of frame t that ``motion.motion_masks`` calls moving
+    (``motion_keep="static"``: static).  With a region as well a pixel must pass both.  The clip's mask is computed once per call,
+    whatever the number of rows; ``motion_reports``: a dict that receives {"clip": MotionReport}.  Without ``motion`` nothing of that
+    runs."""
     if depths.dim() != 6 or depths.shape[0] != 1 or depths.shape[3] != 1:
         raise ValueError(f"depths must be (1, V, T, 1, H, W), got {tuple(depths.shape)}")
     for row in spec:
@@ -165,6 +171,20 @@ def sample_queries(depths, intrs, extrs, spec, depths_conf=None, conf_threshold=
             cluster.invert_poses(region_poses, depths.shape[2])
     elif region_poses is not None:
         raise ValueError("region_poses without a region")
+    frames = None
+    if motion is not None:  # (refused before any launch)
+        from . import motion as motion_
+        if not isinstance(motion, motion_.MotionMask):
+            raise ValueError(f"motion must be a MotionMask, got {motion!r}")
+        if motion_keep not in ("moving", "static"):
+            raise ValueError(f"motion_keep must be 'moving' or 'static', got {motion_keep!r}")
+        if rgbs is None:
+            raise ValueError("motion needs rgbs: the clip's frames (1, V, T, 3, H, W)")
+        frames = motion_.clip_frames(rgbs)
+        if (frames.shape[0], frames.shape[1], frames.shape[3], frames.shape[4]) != (depths.shape[1], depths.shape[2], depths.shape[4], depths.shape[5]):
+            raise ValueError(f"rgbs {tuple(rgbs.shape)} and depths {tuple(depths.shape)} differ in (V, T, H, W)")
+    elif rgbs is not None:
+        raise ValueError("rgbs without motion")
     hip.require_device(depths)
     _, V, T, _, H, W = depths.shape
     dev = depths.device
@@ -179,17 +199,28 @@ def sample_queries(depths, intrs, extrs, spec, depths_conf=None, conf_threshold=
     g = torch.Generator(device="cpu").manual_seed(int(seed))
     out = []
     masks = {}  # frame -> (mask, report): rows that share a frame share the mask
+    static = None  # (V,T,H,W) of the whole clip, computed at the first row that needs it
     for i, (t, z_min, z_max, radius, count, method) in enumerate(spec):
         if t >= T:
             continue
-        if region is None:
-            pool = frame_pool(d, kinv, einv, t, conf, conf_threshold, centre, radius, z_min, z_max, radius_inclusive)
-        else:
+        mask = None
+        if region is not None:
             if t not in masks:
                 masks[t] = _region_mask(d, conf, intrs[0], extrs[0], t, region, region_poses)
                 if region_reports is not None:
                     region_reports[t] = masks[t][1]
-            pool = _region_pool(d, conf, masks[t][0], kinv, einv, t, conf_threshold, centre, radius, z_min, z_max, radius_inclusive)
+            mask = masks[t][0]
+        if motion is not None:
+            if static is None:
+                static, report = motion_.motion_clip(frames, motion)
+                if motion_reports is not None:
+                    motion_reports["clip"] = report
+            keep = (static[:, t] if motion_keep == "static" else ~static[:, t])[:, None, None]  # (V,1,1,H,W)
+            mask = keep if mask is None else mask & keep
+        if mask is None:
+            pool = frame_pool(d, kinv, einv, t, conf, conf_threshold, centre, radius, z_min, z_max, radius_inclusive)
+        else:
+            pool = _region_pool(d, conf, mask, kinv, einv, t, conf_threshold, centre, radius, z_min, z_max, radius_inclusive)
         if pool.shape[0] == 0:
             continue
         if method == "":
