@@ -1149,7 +1149,11 @@ __attribute__((visibility("hidden"))) int mvt_detail_conv_rows(const void* in, c
   const int nw8 = rows_nw8();
   // wide 3x3 / stride-1 layers without normalise-on-load (conv2): one 512-thread workgroup per 8 x 32 pixel tile and 256-channel
   // block, LDS-DMA staging (conv3x3_big_bf16).  MVT_CONV_BIG=0 keeps the 64-channel row tiles (read per call: A/B runs, tests)
-  if (ksize == 3 && stride == 1 && !in_stats && !(io_flags & MVT_IO_SHORT_WG) && a.in_bf16 && st_ok && Cout % BG_BN == 0 && ((uintptr_t)in & 15) == 0 && Cin % 8 == 0 &&
+  // Its statistics slots are its own 8-row tiles, while a.slots and mvt_conv2d_stat_slots -- by which the caller sized
+  // out_partial -- follow the row tile that MVT_ROWS_NW8 selects: where the two differ (16 rows: slots written past the image's
+  // part of the buffer; 4 rows: slots never written), a launch that takes statistics stays on the row tiles.
+  const bool big_slots_ok = !out_partial || mvt_detail_conv_rows_tile_rows(ksize, stride, Ho) == TR;
+  if (ksize == 3 && stride == 1 && !in_stats && big_slots_ok && !(io_flags & MVT_IO_SHORT_WG) && a.in_bf16 && st_ok && Cout % BG_BN == 0 && ((uintptr_t)in & 15) == 0 && Cin % 8 == 0 &&
       ldw % 8 == 0 && ((uintptr_t)w & 15) == 0 && (long long)Cout * ldw * 2 < (1LL << 31) && (long long)H * W * Cin * 2 < (1LL << 31)) {
     const char* e = getenv("MVT_CONV_BIG");
     if (!e || atoi(e) != 0) {

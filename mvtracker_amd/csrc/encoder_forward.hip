@@ -14,6 +14,7 @@ inline long long align256(long long b) { return (b + 255) & ~255LL; }
 struct Plan {
   long long stem, z0, y, s[4], d, cat, c2, part, st, total;  // byte offsets
   long long st_ch;                                           // channels a statistics table / a partials slot is sized for
+  long long part_floats;                                     // floats of the partials buffer
 };
 
 // workspace: bf16 activations + statistics scratch.  stem / z0 / y: one 64-channel map at H/2 each (the largest activation);
@@ -39,11 +40,15 @@ inline Plan plan(long long n, int H, int W, int C) {
   P.d = take(n * hs * ws * 96 * 2);
   P.cat = take(n * hs * ws * 416 * 2);
   P.c2 = take(n * hs * ws * 2 * C * 2);
-  // statistics: per conv n * slots * Cout * 2 floats, slots <= tiles of the H/2 map
-  // (the widest conv is conv2 with 2C channels -- more than the stages' 2 x 128 of a folded launch once latent_dim > 128)
+  // statistics: per conv n * slots * Cout * 2 floats.  Sized as the 8 x 32 tiles of the H/2 map times the widest launch: conv2
+  // with 2C channels, or the 2 x 128 of a folded launch.  Every launch fits that product, not each factor: with MVT_ROWS_NW8=2
+  // the 64-channel layer 1 has twice the slots (four-row tiles), 2 x 64 <= 256 -- and every later map has at most half the rows,
+  // so its four-row tiles are no more than the H/2 map's eight-row ones.  encoder_run checks every launch against part_floats
+  // before the first one (partials_fit).
   const long long slots_max = ((h2 + 7) / 8) * ((w2 + 31) / 32);
   P.st_ch = 2 * C > 256 ? 2 * C : 256;
-  P.part = take(n * slots_max * P.st_ch * 2 * 4);
+  P.part_floats = n * slots_max * P.st_ch * 2;
+  P.part = take(P.part_floats * 4);
   P.st = take(8 * n * P.st_ch * 2 * 4);            // up to 8 live (mean, rstd) tables
   P.total = o;
   return P;
@@ -106,6 +111,33 @@ static int encoder_run(const mvt_encoder_weights* w, const float* x4, const void
   const int h2 = H / 2, w2 = W / 2;
   int g = n;
   ENC_TRY(group_size(n, h2, w2, w->short_workgroups, &g));
+  static const bool no_fold = getenv("MVT_FOLD_DOWNSAMPLE") && atoi(getenv("MVT_FOLD_DOWNSAMPLE")) == 0;  // (A/B runs)
+
+  // The partial sums of every launch below fit the partials buffer (plan()): n * slots * Cout * 2 floats, twice that where a strided
+  // block's conv1 and downsample[0] share one launch.  Checked here, for the whole sequence, so that a refusal leaves nothing queued.
+  auto partials_fit = [&]() -> bool {
+    auto fits = [&](int slots, int cout, int halves) { return slots > 0 && (long long)halves * n * slots * cout * 2 <= P.part_floats; };
+    auto conv_fits = [&](int hh, int ww, int cin, int cout, int k, int stride, int halves) {
+      return fits(mvt_conv2d_stat_slots(hh, ww, cin, k, k, stride, k / 2, 0), cout, halves);
+    };
+    if (!(x4 ? conv_fits(H, W, 4, 64, 7, 2, 1) : fits(mvt_detail_conv_rows_slots(h2, w2, mvt_detail_conv_rows_tile_rows(7, 2, h2)), 64, 1))) return false;
+    const int couts[4] = {64, 96, 128, 128};
+    int hh = h2, ww = w2, cin = 64;
+    for (int l = 0; l < 4; ++l) {
+      const int cout = couts[l], stride = l ? 2 : 1;
+      if (l && cout % 32 == 0 && !no_fold) {  // (res_block's fold)
+        if (!conv_fits(hh, ww, cin, cout, 3, 2, 2)) return false;
+      } else if (!conv_fits(hh, ww, cin, cout, 3, stride, 1) || (l && !conv_fits(hh, ww, cin, cout, 1, stride, 1))) {
+        return false;
+      }
+      hh = (hh - 1) / stride + 1;
+      ww = (ww - 1) / stride + 1;
+      if (!conv_fits(hh, ww, cout, cout, 3, 1, 1)) return false;  // .0.conv2, .1.conv1, .1.conv2
+      cin = cout;
+    }
+    return conv_fits(H / 4, W / 4, 416, 2 * C, 3, 1, 1);
+  };
+  MVT_REQUIRE(partials_fit());
 
   // The launches below act on images [ga, ga + gn) of the call.  Every buffer keeps the whole call's layout -- image i owns slice
   // i of each activation buffer, of the partial sums of a launch and of a (mean, rstd) table -- so a group is the same launch
@@ -157,13 +189,12 @@ static int encoder_run(const mvt_encoder_weights* w, const float* x4, const void
     const int ho = (hh + 2 - 3) / stride + 1, wo = (ww + 2 - 3) / stride + 1;
     const long long in_img = (long long)hh * ww * cin * 2, out_img = (long long)ho * wo * cout * 2;
     float *s1 = nullptr, *s2 = nullptr, *sd = nullptr;
-    static const bool no_fold = getenv("MVT_FOLD_DOWNSAMPLE") && atoi(getenv("MVT_FOLD_DOWNSAMPLE")) == 0;  // (A/B runs)
     const bool fold = cd >= 0 && stride == 2 && !x_stats && cout % 32 == 0 && !no_fold;  // conv1 + downsample[0] read the same x: one launch
     if (fold) {
       const int slots = mvt_conv2d_stat_slots(hh, ww, cin, 3, 3, 2, 1, 0);
       MVT_REQUIRE(slots > 0);
       float* part_3 = part + (long long)ga * slots * cout * 2;
-      float* part_d = part_3 + (long long)n * slots * cout * 2;  // (the partials buffer is sized for the stem: room for both)
+      float* part_d = part_3 + (long long)n * slots * cout * 2;  // (both halves fit: partials_fit)
       ENC_TRY(mvt_conv3x3s2_down_bf16(img(xin, in_img), w->conv[c1].w, w->conv[c1].b, w->conv[cd].w, w->conv[cd].b, img(base + P.y, out_img),
                                       img(base + P.d, out_img), gn, hh, ww, cin, cout, cout, part_3, part_d, stream));
       s1 = new_st();

@@ -20,8 +20,13 @@ F. window correlation, radius 1..7, and the XCD workgroup permutation with every
 G. on the inputs of B..F the mocks of tests/hip_mock.py and tests/hip_mock_ring.py give the kernels' results on CPU copies (bit
    for bit for indices, keys of linear tiles, features, offsets and power-of-two scales; within the bar elsewhere), and the probes:
    each fault of corr_exact_ref planted into the restatement changes the expected result of its section on that section's inputs.
+
+The scans run 2 queries per wave with tile boxes and 8 without; MVT_KNN_Q, read once per process, overrides that.
+`knn_queries_per_wave` / `knn_kernels` restate the choice; tests/test_gpu_tuning_switches.py runs B in a child process per value.
 """
 import functools
+import os
+import re
 import types
 
 import numpy as np
@@ -271,6 +276,27 @@ def run_knn(lib, dev, c, entry):
 
 
 ENTRIES = ("scan", "search", "scan_levels", "search_levels")
+KNN_Q_COMPILED = (1, 2, 4, 8)
+
+
+def knn_queries_per_wave(boxes, q_env=None):
+    """knn_corr.hip: queries per wave of the scan kernels; q_env = MVT_KNN_Q as atoi reads it (0: unset; default: this process's).
+    A value outside KNN_Q_COMPILED has no kernel: the entries refuse."""
+    if q_env is None:
+        m = re.match(r"\s*[+-]?\d+", os.environ.get("MVT_KNN_Q", ""))
+        q_env = int(m.group()) if m else 0
+    return q_env if q_env else (2 if boxes else 8)
+
+
+def knn_kernels(c, q_env=None):
+    """{(kernel, Q, with tile boxes)} that the entries of case c launch (run_knn: the search entries always get boxes, a levels
+    scan has them when every level does)."""
+    kern = {"scan": "knn_scan_kernel", "search": "knn_scan_kernel", "scan_levels": "knn_scan_levels_kernel", "search_levels": "knn_search_levels_kernel"}
+    out = set()
+    for e in entries_of(c):
+        boxes = bool(c.boxed) or e.startswith("search")
+        out.add((kern[e], knn_queries_per_wave(boxes, q_env), boxes))
+    return out
 
 
 def entries_of(c):

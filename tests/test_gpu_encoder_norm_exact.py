@@ -42,10 +42,14 @@ D. mvt_resize_nearest, mvt_resize_bilinear_ac, mvt_concat_resize_bilinear_ac, th
    fp32 and in bf16, and equals the fp64 formula.
 E. Probes (CPU): planted faults in a Python restatement of the kernels' rules must break the assertions above on the cases' inputs.
 
-Not switched: MVT_ROWS_NW8, MVT_APPLY_GENERIC, MVT_CONCAT_GENERIC (read once per process).
+MVT_ROWS_NW8, MVT_APPLY_GENERIC and MVT_CONCAT_GENERIC are read once per process: tests/test_gpu_tuning_switches.py runs cases
+of this file in a child process per value.  `rows_tile` / `tile_rows` / `stat_slots` / `apply_kernel` / `concat_kernel` take the
+switch values as arguments and default to the process's environment, so the slot-count assertion of `run_conv` follows the switch.
 """
 import collections
 import functools
+import os
+import re
 import zlib
 
 import pytest
@@ -204,8 +208,25 @@ def rows_staged_fits(tm, ks, s, nw, tn):
     return nw * 32 * (tn * 32 + 8) <= pr * rs * 40
 
 
-def conv_variant(c):
-    """The kernel mvt_conv2d_bf16 launches for case c (gemm.hip mvt_conv2d_bf16, conv_rows.hip mvt_detail_conv_rows)."""
+def env_int(name):
+    """A once-per-process tuning variable as the library reads it: atoi of the value, 0 when unset."""
+    m = re.match(r"\s*[+-]?\d+", os.environ.get(name, ""))
+    return int(m.group()) if m else 0
+
+
+def rows_tile(k, s, Ho=None, nw8=None):
+    """conv_rows.hip: (TM, NW) of the row-tile kernel for (kernel size, stride) -- NW * TM output rows per workgroup.
+    nw8 = MVT_ROWS_NW8 (default: this process's): 1 = eight waves / 16 rows where Ho % 16 == 0, 2 = TM 1 / four rows.
+    Without Ho (the callers that ask for a case's kernel family, not for a launch) =1 answers for an Ho that is no multiple of 16."""
+    nw8 = env_int("MVT_ROWS_NW8") if nw8 is None else nw8
+    if k == 3 and s == 1:
+        return (2, 8) if (nw8 == 1 and Ho is not None and Ho % 16 == 0) else ((1, 4) if nw8 == 2 else (2, 4))
+    return (1, 4) if (k == 3 and s == 2) else (2, 4)
+
+
+def conv_variant(c, Ho=None, nw8=None):
+    """The kernel mvt_conv2d_bf16 launches for case c (gemm.hip mvt_conv2d_bf16, conv_rows.hip mvt_detail_conv_rows); the row
+    tile, and with it the staged epilogue, follows MVT_ROWS_NW8 (rows_tile)."""
     stem = c.Cin == 4
     inb, outb = c.io[0] == "b", c.io[1] == "b"
     ldo = c.Cout + c.ldo_extra
@@ -215,16 +236,17 @@ def conv_variant(c):
     if stem:
         return ("stem", 1 if c.Cout <= 32 else 2, st_ok)
     n96 = c.Cout % 64 != 0 and c.Cout % 96 == 0
-    if c.k == 3 and c.s == 1 and not c.norm and inb and st_ok and c.Cout % 256 == 0 and c.big:
+    tm, nw = rows_tile(c.k, c.s, Ho, nw8)
+    # (every call of this file takes statistics: the big tile, whose slots are its own 8-row tiles, only where the row tile has 8 too)
+    if c.k == 3 and c.s == 1 and not c.norm and inb and st_ok and c.Cout % 256 == 0 and c.big and tm * nw == 8:
         return ("big",)
     tn = 3 if n96 else 2
-    tm, nw = (1, 4) if (c.k == 3 and c.s == 2) else (2, 4)
     return ("rows", c.k, c.s, tn, st_ok and rows_staged_fits(tm, c.k, c.s, nw, tn))
 
 
-def epilogue_form(c):
+def epilogue_form(c, Ho=None, nw8=None):
     """The form of epilogue_rows (conv_rows.hip) case c runs: staged transposed / staged by pixel / quad / pair / scalar."""
-    v = conv_variant(c)
+    v = conv_variant(c, Ho, nw8)
     ldo = c.Cout + c.ldo_extra
     if v[0] in ("halo", "im2col"):
         return "gemm"
@@ -239,19 +261,35 @@ def epilogue_form(c):
     return "pair" if (c.Cout | ldo) % 2 == 0 else "scalar"
 
 
-def tile_rows(c):
+def tile_rows(c, Ho=None, nw8=None):
+    """Output rows of one statistics slot (conv_rows.hip mvt_detail_conv_rows_tile_rows): the stem and the big tile keep 8."""
+    if conv_variant(c, Ho, nw8)[0] == "rows":
+        tm, nw = rows_tile(c.k, c.s, Ho, nw8)
+        return tm * nw
     return 4 if (c.k == 3 and c.s == 2) else 8
 
 
-def stat_slots(c, H, W):
+def stat_slots(c, H, W, nw8=None):
     """mvt_conv2d_stat_slots."""
     Ho, Wo = conv_out(H, W, c.k, c.s)
-    v = conv_variant(c)
+    v = conv_variant(c, Ho, nw8)
     if v[0] == "halo":
         return cdiv(Ho, 8) * cdiv(Wo, 16) * 4
     if v[0] == "im2col":
         return Ho * Wo // 32 if (Ho * Wo) % 256 == 0 else 0
-    return cdiv(Ho, tile_rows(c)) * cdiv(Wo, 32)
+    return cdiv(Ho, tile_rows(c, Ho, nw8)) * cdiv(Wo, 32)
+
+
+def apply_kernel(io, C, generic=None):
+    """mvt_instnorm_apply on 16-byte aligned tensors: the 16-byte bf16 kernel or the generic one (generic = MVT_APPLY_GENERIC is set)."""
+    generic = ("MVT_APPLY_GENERIC" in os.environ) if generic is None else generic
+    return ("apply", "bf16-16B") if (io == "b" and C % 8 == 0 and C <= 2048 and not generic) else ("apply", "generic", io)
+
+
+def concat_kernel(io, ctot, generic=None):
+    """mvt_concat_resize_bilinear_ac: the row kernel of bf16 tensors or the generic one (generic = MVT_CONCAT_GENERIC is set)."""
+    generic = ("MVT_CONCAT_GENERIC" in os.environ) if generic is None else generic
+    return ("concat", "rows-bf16") if (io == "b" and not generic and ctot // 8 <= 256) else ("concat", "generic", io)
 
 
 # output sizes against the 8 x 32 tile: smaller than one tile, exactly one, one row and one column over, ragged in both directions

@@ -50,7 +50,8 @@ Probes (CPU): each fault of `encoder_wiring_ref.FAULTS`, planted in the referenc
 in by a factor of 2 at least, on the GPU tests' own weights and images.  Out of reach, by construction: a bias in front of an
 InstanceNorm cancels exactly (only conv3's bias is visible), and a wrong eps (it showed only 3 - 10 x the noise in a prototype).
 
-Not switched (read once per process): MVT_FOLD_DOWNSAMPLE, MVT_ROWS_NW8, MVT_CONV_BIG, MVT_APPLY_GENERIC, MVT_CONCAT_GENERIC.
+The switches a process reads once (MVT_FOLD_DOWNSAMPLE, MVT_ROWS_NW8, MVT_APPLY_GENERIC, MVT_CONCAT_GENERIC) are set by
+tests/test_gpu_tuning_switches.py, which runs cases of this file in a child process per value.  Not switched: MVT_CONV_BIG.
 """
 import collections
 import functools

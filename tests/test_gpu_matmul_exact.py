@@ -12,7 +12,9 @@ looks at the device.
 A. The host dispatch restated (pick_tile, the halo tiles, the branch of mvt_conv2d_bf16, the row-tile variants of conv_rows.hip, the
    launch forms of mvt_block_fused_bf16 / mvt_ln_proj_bf16): `test_cases_reach_every_variant` asserts that the parametrised shapes
    reach every variant the library compiles for these entry points, so a shape that falls back to another variant fails on the CPU.
-   (Not reached: the MVT_ROWS_NW8 / MVT_BLOCK_NMB tuning overrides, which a process reads once from its environment.)
+   (The MVT_ROWS_NW8 / MVT_BLOCK_NMB / MVT_BLOCK_NOSPLIT tuning overrides, which a process reads once from its environment, are
+   reached by tests/test_gpu_tuning_switches.py: it runs cases of this file in a child process per value.  The restatements
+   below take the switch values as arguments and default to the process's environment.)
 B. mvt_gemm, mvt_gemm_bf16 (bf16, bf16x3), mvt_ln_gemm_bf16: every tile at its edges, K on both sides of the 32- and 64-wide
    k-tiles and of the 4-element lda padding, act none / relu, with and without an integer residual, padded and NaN-poisoned ldc /
    ldr / lda.  torch.equal against the fp64 CPU matmul.  (mvt_ln_gemm_bf16 in bf16x3 mode keeps the 1e-6 residue of rstd in the lo
@@ -30,6 +32,8 @@ E. The probes are themselves tested: a dropped k, a dropped last k-tile, two swa
 """
 import collections
 import functools
+import os
+import re
 import zlib
 
 import pytest
@@ -82,6 +86,25 @@ def halo_tile(Cout):
     return 64 if Cout <= 64 else 128
 
 
+def env_int(name):
+    """A once-per-process tuning variable as the library reads it: atoi of the value, 0 when unset."""
+    m = re.match(r"\s*[+-]?\d+", os.environ.get(name, ""))
+    return int(m.group()) if m else 0
+
+
+def env_set(name):
+    return name in os.environ
+
+
+def rows_tile(k, s, Ho, nw8=None):
+    """conv_rows.hip: (TM, NW) of the row-tile kernel for (kernel size, stride) -- NW * TM output rows per workgroup.
+    nw8 = MVT_ROWS_NW8 (default: this process's): 1 = eight waves / 16 rows where Ho % 16 == 0, 2 = TM 1 / four rows."""
+    nw8 = env_int("MVT_ROWS_NW8") if nw8 is None else nw8
+    if k == 3 and s == 1:
+        return (2, 8) if (nw8 == 1 and Ho % 16 == 0) else ((1, 4) if nw8 == 2 else (2, 4))
+    return (1, 4) if (k == 3 and s == 2) else (2, 4)
+
+
 def rows_staged_fits(tm, ks, s, nw, tn):
     """conv_rows.hip LAUNCH2 `fits`: the per-wave staging tiles of the bf16 epilogue fit the patch LDS (Geo<TM, KS, S, NW>)."""
     rows = nw * tm
@@ -100,8 +123,8 @@ def conv_out(H, W, k, s):
     return (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
 
 
-def conv_variant(c, n, H, W):
-    """The kernel that mvt_conv2d / mvt_conv2d_bf16 launch for case c on n images of H x W."""
+def conv_variant(c, n, H, W, nw8=None):
+    """The kernel that mvt_conv2d / mvt_conv2d_bf16 launch for case c on n images of H x W (nw8: see rows_tile)."""
     Ho, Wo = conv_out(H, W, c.k, c.s)
     M, p = n * Ho * Wo, c.k // 2
     stem = c.Cin == 4
@@ -118,7 +141,7 @@ def conv_variant(c, n, H, W):
         if c.k == 3 and c.s == 1 and not c.short and inb and st_ok and c.Cout % 256 == 0 and c.big:
             return ("big",)
         tn = 3 if n96 else 2
-        tm, nw = (1, 4) if (c.k == 3 and c.s == 2) else (2, 4)
+        tm, nw = rows_tile(c.k, c.s, Ho, nw8)
         return ("rows", c.k, c.s, tn, inb, st_ok and rows_staged_fits(tm, c.k, c.s, nw, tn))
     if c.k == 3 and c.s == 1 and c.Cin % 32 == 0:
         return ("halo", c.prec, halo_tile(c.Cout))
@@ -129,11 +152,15 @@ def down_variant(Cout):
     return ("down", 3 if (Cout % 64 != 0 and Cout % 96 == 0) else 2)
 
 
-def block_forms(M, ws):
-    """mvt_block_fused_bf16: the kernel instantiations <NMB, MODE> one call launches."""
-    if M >= 4096:
+def block_forms(M, ws, nmb=None, nosplit=None):
+    """mvt_block_fused_bf16: the kernel instantiations <NMB, MODE> one call launches.  nmb = the value MVT_BLOCK_NMB forces
+    ("rule": the variable is unset), nosplit = MVT_BLOCK_NOSPLIT is set; default: this process's environment."""
+    if nmb is None:
+        nmb = env_int("MVT_BLOCK_NMB") if env_set("MVT_BLOCK_NMB") else "rule"
+    nosplit = env_set("MVT_BLOCK_NOSPLIT") if nosplit is None else nosplit
+    if (nmb if nmb != "rule" else (2 if M >= 4096 else 1)) == 2:
         return [("block", 2, 0)]
-    if ws and M <= 2048 and M % 32 == 0:
+    if ws and not nosplit and M <= 2048 and M % 32 == 0:
         return [("block", 1, 1), ("block", 1, 2)]
     return [("block", 1, 0)]
 

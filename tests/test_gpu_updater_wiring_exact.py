@@ -25,8 +25,9 @@ to 1e-6 with every active softmax putting <= 1e-8 off its planted key before any
 `wiring` is a plain torch restatement of updater_run's buffers and row ranges; `test_probes` plants 14 wiring faults in it and each
 must break the decode on the cases' own inputs.
 
-Not observable by this construction: LayerNorm eps 1e-5 against 1e-6 (both give +-1 in bf16), and the tuning variables read once
-per process (MVT_TIME_NMB1, MVT_FRAME_NMB1, MVT_BLOCK_NMB).  Per-head targets exist only in the virtual<-point stage (two wanted
+Not observable by this construction: LayerNorm eps 1e-5 against 1e-6 (both give +-1 in bf16).  The tuning variables read once per
+process (MVT_TIME_NMB1, MVT_FRAME_NMB1, MVT_BLOCK_NMB) are set by tests/test_gpu_tuning_switches.py, which runs cases of this file
+in a child process per value; `forms` takes the two it depends on as arguments and defaults to the environment.  Per-head targets exist only in the virtual<-point stage (two wanted
 codes, heads alternate): its 128 targets cover every point index up to n = 128 and otherwise both sides of every 32-key block
 (which contains every key-split and tile edge); rotated target sets reach every index up to n = 384.
 
@@ -35,6 +36,8 @@ GPU tests (`-m gpu`) drive the product's entries; the tests without the marker a
 import collections
 import functools
 import math
+import os
+import re
 
 import pytest
 import torch
@@ -490,15 +493,26 @@ def check_decodes(delta, want, what=""):
 # ------------------------------------------------------------------ the form selection of updater_run / mvt_attn_block_fused_bf16, restated
 
 
-def forms(n, S, mask, G=1):
+def env_is_zero(name):
+    """`getenv(name) && atoi(getenv(name)) == 0`: how the library reads MVT_TIME_NMB1 / MVT_FRAME_NMB1."""
+    v = os.environ.get(name)
+    m = None if v is None else re.match(r"\s*[+-]?\d+", v)
+    return v is not None and (int(m.group()) if m else 0) == 0
+
+
+def forms(n, S, mask, G=1, time_small=None, frame_small=None):
+    """time_small / frame_small: the 32-row time tiles / 32-token frame tiles are allowed (False = MVT_TIME_NMB1=0 /
+    MVT_FRAME_NMB1=0; default: this process's environment)."""
+    time_small = not env_is_zero("MVT_TIME_NMB1") if time_small is None else time_small
+    frame_small = not env_is_zero("MVT_FRAME_NMB1") if frame_small is None else frame_small
     Mp, Mv = n * S, G * NV * S
     M = Mp + Mv
     grouped = G > 1
     fuse_time, fuse_p2v, fuse_vs = bool(mask & 1) and S <= 32, bool(mask & 2) and not grouped, bool(mask & 4) and not grouped
-    small = Mp >= 4096 and cdiv(n, 32) * S <= 256
+    small = frame_small and Mp >= 4096 and cdiv(n, 32) * S <= 256
     fold = bool(mask & 32) and fuse_p2v and fuse_vs and Mp >= 4096 and not small and 8 * cdiv(n, 64) >= cdiv(3 * INNER, 32)
     parts = bool(mask & 16) and not grouped and n >= 512 and cdiv(n, 32) % 4 == 0
-    f = {"time": "sep" if not fuse_time else ("tile32" if cdiv(M, (32 // S) * S) <= 256 else "tile64"),
+    f = {"time": "sep" if not fuse_time else ("tile32" if time_small and cdiv(M, (32 // S) * S) <= 256 else "tile64"),
          "v2p": "partials" if parts else ("segmented" if grouped else "plain"),
          "vself": "deferred" if fold else ("frame_split" if fuse_vs else ("segmented" if grouped else "sep")),
          "p2v": "ctx" if fold else (("frame32" if small else "frame64") if fuse_p2v and Mp >= 4096 else ("segmented" if grouped else "sep"))}
@@ -509,6 +523,10 @@ def forms(n, S, mask, G=1):
 
 N_S12 = (5, 37, 341, 342, 448, 449, 511, 512, 513, 672, 673, 704, 740)  # (704 = 11 full 64-token tiles of the context form)
 N_MLP = (5, 37, 342, 513, 673, 704, 740)
+# the MLPs of the two blocks whose kernel MVT_FRAME_NMB1 switches, at the other ends of the range of n that it moves ([342, 672]) and
+# at whole 64-token tiles inside it (test_gpu_tuning_switches.py runs them under MVT_FRAME_NMB1=0)
+N_MLP_FRAME = (341, 448, 512, 672)
+MLPS_FRAME = [f"mlp_{b}@{L}" for L in (0, 1) for b in ("p2v", "vself")]
 MASKS = (0, 1, 2, 4, 16, 23, 39, 55)
 GROUPS = ((1, 37, 300, 5), (342, 400))
 
@@ -828,7 +846,8 @@ class Run:
 
 
 @gpu
-@pytest.mark.parametrize("name,n", [(c, n) for c in CHAINS for n in N_S12] + [(c, n) for c in MLPS for n in N_MLP])
+@pytest.mark.parametrize("name,n", [(c, n) for c in CHAINS for n in N_S12] + [(c, n) for c in MLPS for n in N_MLP]
+                         + [(c, n) for c in MLPS_FRAME for n in N_MLP_FRAME])
 def test_composite_decodes(hip, name, n):
     """Every fuse mask, the fused-input path on and off and the _tokens entry decode to the planted integers; delta's padding
     columns and guard row stay NaN, the workspace is NaN before every call.
