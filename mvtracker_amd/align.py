@@ -337,10 +337,7 @@ def list_problem(source, target, target_normals, max_distance, max_iterations, i
     if target_normals is None:
         target_normals = cloud.estimate_normals(target, normal_radius, normal_max_nn)
     nrm = _list_cloud(target_normals, "target_normals")
-    nt = (N + 63) // 64
-    box = torch.empty(1, nt, 8, device=dev)
-    gbox = torch.empty(1, (nt + 63) // 64, 8, device=dev)
-    build_search(tgt, 1, N, (0, 0), box, gbox)
+    box, gbox = hip.cloud_boxes(tgt, 1, N, (0, 0))
     D = _eye_rows(1, dev)[0] if init is None else _rows12(init.to(device=dev, dtype=torch.float64))
     return IcpRun(src, M, (0, 0), 1, [dict(xyz=tgt, nrm=nrm, box=box, gbox=gbox, P=N, grid=(0, 0))], max_distance, 1, D, int(max_iterations),
                   keep_queries=keep_queries)

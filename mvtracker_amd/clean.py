@@ -80,11 +80,7 @@ def search_clouds(xyz, n_clouds, n_points, grid, cleaning):
     state (n_clouds, 4) fp64 = (M, mu, sigma, thr), keep (n_clouds, n_points) uint8."""
     c = _check(cleaning)
     dev = xyz.device
-    nt = (n_points + 63) // 64
-    box = torch.empty(n_clouds, nt, 8, device=dev)
-    gbox = torch.empty(n_clouds, (nt + 63) // 64, 8, device=dev)
-    hip.tile_aabb(xyz, n_points, n_clouds, box, grid)
-    hip.tile_group_aabb(box, n_points, n_clouds, gbox)
+    box, gbox = hip.cloud_boxes(xyz, n_clouds, n_points, grid)
     stat = c.mode == hip.CLEAN_STATISTICAL
     values = torch.empty(n_clouds, n_points, device=dev, dtype=torch.float32 if stat else torch.int32)
     hip.clean_search(xyz, n_clouds, n_points, grid, c.mode, c.nb_neighbors, c.radius, c.min_points, box, gbox,

@@ -51,12 +51,8 @@ def normals_of_clouds(xyz, n_clouds, n_points, grid, radius, max_nn, nrm=None, b
     Returns nrm (n_clouds, n_points, 4), with ``details`` also (nbr_idx, nbr_cnt, cov)."""
     radius, max_nn = check_normal_search(radius, max_nn)
     dev = xyz.device
-    nt = (n_points + 63) // 64
     if box is None:
-        box = torch.empty(n_clouds, nt, 8, device=dev)
-        gbox = torch.empty(n_clouds, (nt + 63) // 64, 8, device=dev)
-        hip.tile_aabb(xyz, n_points, n_clouds, box, grid)
-        hip.tile_group_aabb(box, n_points, n_clouds, gbox)
+        box, gbox = hip.cloud_boxes(xyz, n_clouds, n_points, grid)
     if nrm is None:
         nrm = torch.empty(n_clouds, n_points, 4, device=dev)
     idx = cnt = cov = None

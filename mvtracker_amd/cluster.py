@@ -103,11 +103,7 @@ def cluster_clouds(xyz, n_clouds, n_points, grid, eps, min_samples, region_T_wor
     dev = xyz.device
     if bounds is not None:
         hip.cluster_crop(xyz, n_clouds, n_points, region_T_world, bounds)
-    nt = (n_points + 63) // 64
-    box = torch.empty(n_clouds, nt, 8, device=dev)
-    gbox = torch.empty(n_clouds, (nt + 63) // 64, 8, device=dev)
-    hip.tile_aabb(xyz, n_points, n_clouds, box, grid)
-    hip.tile_group_aabb(box, n_points, n_clouds, gbox)
+    box, gbox = hip.cloud_boxes(xyz, n_clouds, n_points, grid)
     r2 = radius_sq(eps)
     core = torch.empty(n_clouds, n_points, device=dev, dtype=torch.uint8)
     parent = torch.empty(n_clouds, n_points, device=dev, dtype=torch.int32)

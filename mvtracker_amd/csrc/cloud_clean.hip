@@ -11,7 +11,7 @@
 //                  rescanned for the new one.  Only the MULTISET of the K smallest d2 matters for the mean distance (equal d2 give
 //                  equal terms), so no indices are kept and a tie at the K-th place needs no rule.
 //                  radius: a counter per query, stopped at min_points + 1.
-//                Walk: pass 0 visits the query tile and the ring around it (3x3 patches, or tiles t-2..t+2 of a point list), which
+//                Walk (walk_cloud, cloud_search.h): pass 0 visits the query tile and the ring around it (3x3 patches, or tiles t-2..t+2 of a point list), which
 //                gives every query a bound; pass 1 visits the rest through the group boxes and tile boxes of mvt_tile_group_aabb /
 //                mvt_tile_aabb.  A box is skipped only when its distance exceeds the current bound: box to box (the query tile's
 //                own box, against the largest bound of the wave) for groups and tiles, then point to box per query; all with the
@@ -25,7 +25,7 @@
 namespace {
 
 constexpr int CS_WG = 128;  // threads per workgroup of the search (2 waves): K * 512 bytes of LDS, 32 KiB at K = 64
-constexpr int CM_WG = 256;
+constexpr int CM_WG = 256;  // (block_sum_f64 adds up four waves)
 
 __global__ __launch_bounds__(256) void clean_points_kernel(const float* __restrict__ depths, const float* __restrict__ conf,
                                                            const float* __restrict__ kinv, const float* __restrict__ einv, int V, int T, int t0,
@@ -54,6 +54,45 @@ __global__ __launch_bounds__(256) void clean_points_kernel(const float* __restri
   }
 }
 
+// What a query keeps during the walk.  MODE 0 (statistical): the K smallest d2 in its LDS column, the largest of them (+inf until K
+// are found) as the bound.  MODE 1 (radius): a counter stopped at cap, r2 as the bound until then.
+template <int MODE>
+struct clean_visitor : walk_defaults {
+  float* list;  // entry k of this lane's query: list[k * 64]
+  int K, cap;
+  float r2;
+  bool valid;
+  float thr;
+  int maxpos, cnt;
+  __device__ __forceinline__ clean_visitor(float* list_, int K_, float r2_, int cap_, bool valid_)
+      : list(list_), K(K_), cap(cap_), r2(r2_), valid(valid_), thr(inf_f()), maxpos(0), cnt(0) {}
+  __device__ __forceinline__ float bound() const { return MODE == 0 ? (valid ? thr : -inf_f()) : ((valid && cnt < cap) ? r2 : -inf_f()); }
+  __device__ __forceinline__ bool candidate(int, const f32x4& p) const { return finite3(p); }  // NaN points take no part
+  __device__ __forceinline__ void visit(int, int, float d2) {
+    if (MODE == 0) {
+      if (d2 < thr) {
+        list[maxpos * 64] = d2;
+        float m = -1.f;
+        int mp = 0;
+        for (int k = 0; k < K; ++k) {
+          const float v = list[k * 64];
+          if (v > m) {
+            m = v;
+            mp = k;
+          }
+        }
+        thr = m;
+        maxpos = mp;
+      }
+    } else {
+      cnt += d2 < r2 ? 1 : 0;
+    }
+  }
+  __device__ __forceinline__ void end_tile() {
+    if (MODE == 1) cnt = cnt < cap ? cnt : cap;
+  }
+};
+
 // MODE 0: statistical (a_out), MODE 1: radius (c_out).  One wave per (cloud, tile); lane = query.
 template <int MODE>
 __global__ __launch_bounds__(CS_WG) void clean_search_kernel(const float* __restrict__ xyz, long long P, int ntiles, int grid_w, int K, float r2,
@@ -64,15 +103,12 @@ __global__ __launch_bounds__(CS_WG) void clean_search_kernel(const float* __rest
   const int tile = blockIdx.x * (CS_WG / 64) + wave;
   if (tile >= ntiles) return;  // (wave-uniform; the kernel has no workgroup barrier)
   const long long cloud = blockIdx.y;
-  const float* __restrict__ cand = xyz + cloud * P * 4;
-  const int ng = (ntiles + 63) >> 6;
-  const float* __restrict__ fbox = box + cloud * ntiles * 8;
-  const float* __restrict__ fgbox = gbox + cloud * ng * 8;
+  const cloud_view cv = cloud_of(xyz, box, gbox, cloud, P, ntiles, grid_w);
   float* list = lds + wave * K * 64 + lane;  // entry k of this lane's query: list[k * 64]
 
-  const int qi = clean_tile_point(tile, lane, grid_w);
+  const int qi = cloud_tile_point(tile, lane, grid_w);
   f32x4 q = (f32x4){nan_f(), nan_f(), nan_f(), 0.f};
-  if (qi < P) q = *reinterpret_cast<const f32x4*>(cand + (long long)qi * 4);
+  if (qi < P) q = *reinterpret_cast<const f32x4*>(cv.xyz + (long long)qi * 4);
   const bool valid = finite3(q);
   if (!__ballot(valid)) {  // nothing to search for
     if (qi < P) {
@@ -81,80 +117,12 @@ __global__ __launch_bounds__(CS_WG) void clean_search_kernel(const float* __rest
     }
     return;
   }
-  float thr = inf_f();  // MODE 0: the largest of the K kept d2 (+inf until K are found)
-  int maxpos = 0, cnt = 0;
   if (MODE == 0)
     for (int k = 0; k < K; ++k) list[k * 64] = inf_f();
-  const f32x4 qlo = *reinterpret_cast<const f32x4*>(fbox + (long long)tile * 8), qhi = *reinterpret_cast<const f32x4*>(fbox + (long long)tile * 8 + 4);
+  const f32x4 qlo = *reinterpret_cast<const f32x4*>(cv.box + (long long)tile * 8), qhi = *reinterpret_cast<const f32x4*>(cv.box + (long long)tile * 8 + 4);
 
-  for (int pass = 0; pass < 2; ++pass) {
-    for (int gb = 0; gb < ng; gb += 64) {
-      // this lane's bound, and the wave's largest (-inf: the lane / the wave has nothing left to find)
-      float mine = MODE == 0 ? (valid ? thr : -inf_f()) : ((valid && cnt < cap) ? r2 : -inf_f());
-      float tmax = wave_max(mine);
-      bool gnear = gb + lane < ng;
-      if (pass == 1 && gnear) {
-        const float* gp = fgbox + (long long)(gb + lane) * 8;
-        const float lb = box_box_d2(qlo, qhi, *reinterpret_cast<const f32x4*>(gp), *reinterpret_cast<const f32x4*>(gp + 4));
-        gnear = !(lb > tmax);  // (a NaN bound never culls)
-      }
-      unsigned long long gmask = __ballot(gnear);
-      while (gmask) {
-        const int tb = (gb + __builtin_ctzll(gmask)) * 64;
-        gmask &= gmask - 1;
-        const int t = tb + lane;
-        bool tnear = t < ntiles && in_ring(t, tile, grid_w) == (pass == 0);
-        if (pass == 1 && tnear) {
-          const float* bp = fbox + (long long)t * 8;
-          const float lb = box_box_d2(qlo, qhi, *reinterpret_cast<const f32x4*>(bp), *reinterpret_cast<const f32x4*>(bp + 4));
-          tnear = !(lb > tmax);
-        }
-        unsigned long long tmask = __ballot(tnear);
-        while (tmask) {
-          const int tt = tb + __builtin_ctzll(tmask);
-          tmask &= tmask - 1;
-          // per query: can the tile hold a point below this lane's bound?
-          const float* bp = fbox + (long long)tt * 8;
-          const float lbq = point_box_d2(q, *reinterpret_cast<const f32x4*>(bp), *reinterpret_cast<const f32x4*>(bp + 4));
-          if (!__ballot(mine > -inf_f() && !(lbq > mine))) continue;
-          const int ci = clean_tile_point(tt, lane, grid_w);
-          f32x4 p = (f32x4){nan_f(), nan_f(), nan_f(), 0.f};
-          if (ci < P) p = *reinterpret_cast<const f32x4*>(cand + (long long)ci * 4);
-          unsigned long long cm = __ballot(finite3(p));  // NaN points take no part
-          while (cm) {
-            const int j = __builtin_ctzll(cm);
-            cm &= cm - 1;
-            const float cx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p[0]), j));
-            const float cy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p[1]), j));
-            const float cz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p[2]), j));
-            const float dx = cx - q[0], dy = cy - q[1], dz = cz - q[2];
-            const float d2 = gap_d2(dx, dy, dz);  // (NaN for a NaN query: every compare fails)
-            if (MODE == 0) {
-              if (d2 < thr) {
-                list[maxpos * 64] = d2;
-                float m = -1.f;
-                int mp = 0;
-                for (int k = 0; k < K; ++k) {
-                  const float v = list[k * 64];
-                  if (v > m) {
-                    m = v;
-                    mp = k;
-                  }
-                }
-                thr = m;
-                maxpos = mp;
-              }
-            } else {
-              cnt += d2 < r2 ? 1 : 0;
-            }
-          }
-          if (MODE == 1) cnt = cnt < cap ? cnt : cap;
-          mine = MODE == 0 ? (valid ? thr : -inf_f()) : ((valid && cnt < cap) ? r2 : -inf_f());
-        }
-        tmax = wave_max(mine);  // (bounds only shrink: the group mask taken with the older value stays valid)
-      }
-    }
-  }
+  clean_visitor<MODE> vis(list, K, r2, cap, valid);
+  for (int pass = 0; pass < 2; ++pass) walk_cloud(cv, q, qlo, qhi, tile, pass == 0 ? VISIT_RING : VISIT_REST, vis);
 
   if (MODE == 0) {
     // mean of the distances in ascending order of d2, fp64; entries still +inf were never found (fewer than K points in the cloud)
@@ -178,17 +146,8 @@ __global__ __launch_bounds__(CS_WG) void clean_search_kernel(const float* __rest
     }
     if (qi < P) a_out[cloud * P + qi] = (valid && kk > 0) ? (float)(sum / (double)kk) : nan_f();
   } else {
-    if (qi < P) c_out[cloud * P + qi] = valid ? cnt : -1;
+    if (qi < P) c_out[cloud * P + qi] = valid ? vis.cnt : -1;
   }
-}
-
-__device__ __forceinline__ double block_sum_f64(double v, double* s_red) {  // fixed tree, the four waves in order; every thread gets the sum
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();  // (s_red may still be read from the previous call)
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
 }
 
 // One workgroup per cloud.  state[cloud] = {M, mu, sigma, thr} (doubles); keep[cloud][P].
@@ -258,8 +217,7 @@ extern "C" int mvt_clean_points(const float* depths, const float* conf, const fl
     sx = sphere[0], sy = sphere[1], sz = sphere[2], sr2 = sphere[3] * sphere[3];
   }
   const long long total = (long long)V * nt * Hp * Wp;
-  const long long b = mvt_cdiv(total, 256);
-  hipLaunchKernelGGL(clean_points_kernel, dim3((unsigned)(b > 8192 ? 8192 : b)), dim3(256), 0, mvt_stream(stream), depths, conf, kinv, einv, V, T, t0,
+  hipLaunchKernelGGL(clean_points_kernel, dim3(strided_blocks(total)), dim3(256), 0, mvt_stream(stream), depths, conf, kinv, einv, V, T, t0,
                      nt, H, W, Hp, Wp, conf_thresh, sphere ? 1 : 0, sx, sy, sz, sr2, xyz);
   return mvt_launch_status();
 }
@@ -267,8 +225,7 @@ extern "C" int mvt_clean_points(const float* depths, const float* conf, const fl
 extern "C" int mvt_clean_search(const float* xyz, int C, long long P, int grid_w, int grid_h, int mode, int K, float radius, int min_points,
                                 const float* tile_box, const float* group_box, float* a_out, int* c_out, void* stream) {
   MVT_REQUIRE(aligned(xyz, 16) && aligned(tile_box, 16) && aligned(group_box, 16));
-  MVT_REQUIRE(C > 0 && C <= 65535 && P > 0 && P < (1ll << 31) - 64);
-  MVT_REQUIRE((grid_w == 0 && grid_h == 0) || (grid_w > 0 && grid_h > 0 && grid_w % 8 == 0 && grid_h % 8 == 0 && P == (long long)grid_w * grid_h));
+  MVT_REQUIRE(cloud_shape_ok(C, P, grid_w, grid_h));
   const int ntiles = (int)((P + 63) / 64);
   const dim3 grid((unsigned)mvt_cdiv(ntiles, CS_WG / 64), (unsigned)C);
   if (mode == MVT_CLEAN_STATISTICAL) {

@@ -93,6 +93,68 @@ __global__ __launch_bounds__(256) void cluster_init_kernel(int* __restrict__ par
   }
 }
 
+// What a query does during the walk, with the inclusive test d2 <= r2; r2 is the bound of a lane while it is active.
+template <int MODE>
+struct cluster_visitor : walk_defaults {
+  static constexpr bool skip_empty = true;
+  const unsigned char* ccore;
+  int* cpar;
+  float r2;
+  int cap, bound_steps, grid_w;
+  int qi, qmax;  // the lane's query; LINK: the largest query index of this tile
+  bool act;      // has the lane anything left to find?
+  int cnt;       // COUNT: neighbours so far, stopped at cap
+  int cur;       // LINK: the lowest index this lane knows in its own tree
+  int best;      // BORDER: the lowest root among the core neighbours (bound_steps: none)
+  bool bad;
+  int pv;  // of the lane's candidate of the tile at hand: LINK: a parent (possibly stale: still in its tree); BORDER: its root
+  __device__ __forceinline__ cluster_visitor(const unsigned char* ccore_, int* cpar_, float r2_, int cap_, int bound_, int grid_w_, int qi_, int qmax_,
+                                             bool act_)
+      : ccore(ccore_), cpar(cpar_), r2(r2_), cap(cap_), bound_steps(bound_), grid_w(grid_w_), qi(qi_), qmax(qmax_), act(act_), cnt(0), cur(qi_),
+        best(bound_), bad(false), pv(0) {}
+  __device__ __forceinline__ float bound() const { return act ? r2 : -inf_f(); }
+  __device__ __forceinline__ bool tile_ok(int t) const {  // (LINK: only candidates below the query unite)
+    return MODE == WALK_LINK ? cloud_tile_point(t, 0, grid_w) < qmax : true;
+  }
+  __device__ __forceinline__ bool candidate(int i, const f32x4& p) {
+    bool cok = finite3(p);  // NaN points take no part
+    pv = 0;
+    if (MODE != WALK_COUNT) {
+      cok = cok && ccore[i] != 0;
+      if (cok) pv = MODE == WALK_LINK ? uf_load(cpar + i) : cpar[i];
+    }
+    return cok;
+  }
+  __device__ __forceinline__ void visit(int j, int ci, float d2) {
+    const bool hit = act && d2 <= r2;  // (NaN for a NaN query: the compare fails)
+    if (MODE == WALK_COUNT) {
+      cnt += hit ? 1 : 0;
+    } else {
+      const int pj = __builtin_amdgcn_readlane(pv, j);
+      if (MODE == WALK_BORDER) {
+        best = (hit && pj < best) ? pj : best;
+      } else {
+        const int cj = __builtin_amdgcn_readlane(ci, j);
+        if (hit && cj < qi && pj != cur) {  // (pj == cur: the candidate already hangs under this lane's root)
+          const int r = uf_unite(cpar, cur, pj, bound_steps, bad);
+          if (bad) {
+            act = false;
+          } else {
+            cur = r;
+            if (r < pj) atomicMin(cpar + cj, r);  // shorten the candidate's path: r is in its tree and below its parent
+          }
+        }
+      }
+    }
+  }
+  __device__ __forceinline__ void end_tile() {
+    if (MODE == WALK_COUNT) {
+      cnt = cnt < cap ? cnt : cap;
+      act = act && cnt < cap;  // a query that has reached min_samples has nothing left to find
+    }
+  }
+};
+
 // One wave per (cloud, tile); lane = query.  out: core (COUNT) / nothing (LINK) / root (BORDER).
 template <int MODE>
 __global__ __launch_bounds__(CL_WG) void cluster_walk_kernel(const float* __restrict__ xyz, long long P, int ntiles, int grid_w, float r2, int cap,
@@ -103,119 +165,31 @@ __global__ __launch_bounds__(CL_WG) void cluster_walk_kernel(const float* __rest
   const int tile = blockIdx.x * (CL_WG / 64) + wave;
   if (tile >= ntiles) return;  // (wave-uniform; the kernel has no workgroup barrier)
   const long long cloud = blockIdx.y;
-  const float* __restrict__ cand = xyz + cloud * P * 4;
-  const int ng = (ntiles + 63) >> 6;
-  const float* __restrict__ fbox = box + cloud * ntiles * 8;
-  const float* __restrict__ fgbox = gbox + cloud * ng * 8;
+  const cloud_view cv = cloud_of(xyz, box, gbox, cloud, P, ntiles, grid_w);
   unsigned char* ccore = core + cloud * P;
   int* cpar = MODE == WALK_COUNT ? nullptr : parent + cloud * P;
   const int bound = (int)P;
 
-  const int qi = clean_tile_point(tile, lane, grid_w);
+  const int qi = cloud_tile_point(tile, lane, grid_w);
   f32x4 q = (f32x4){nan_f(), nan_f(), nan_f(), 0.f};
-  if (qi < P) q = *reinterpret_cast<const f32x4*>(cand + (long long)qi * 4);
+  if (qi < P) q = *reinterpret_cast<const f32x4*>(cv.xyz + (long long)qi * 4);
   const bool valid = finite3(q);
   const bool qcore = MODE != WALK_COUNT && valid && ccore[qi] != 0;
-  bool act = MODE == WALK_COUNT ? valid : (MODE == WALK_LINK ? qcore : (valid && !qcore));
-  int cnt = 0;        // COUNT: neighbours so far, stopped at cap
-  int cur = qi;       // LINK: the lowest index this lane knows in its own tree
-  int best = bound;   // BORDER: the lowest root among the core neighbours (bound: none)
-  bool bad = false;
-  const int qmax = clean_tile_point(tile, 63, grid_w);  // LINK: the largest query index of this tile
+  const bool act = MODE == WALK_COUNT ? valid : (MODE == WALK_LINK ? qcore : (valid && !qcore));
+  cluster_visitor<MODE> vis(ccore, cpar, r2, cap, bound, grid_w, qi, cloud_tile_point(tile, 63, grid_w), act);
 
   if (__ballot(act)) {
-    const f32x4 qlo = *reinterpret_cast<const f32x4*>(fbox + (long long)tile * 8), qhi = *reinterpret_cast<const f32x4*>(fbox + (long long)tile * 8 + 4);
-    for (int pass = 0; pass < 2; ++pass) {
-      for (int gb = 0; gb < ng; gb += 64) {
-        // this lane's bound, and the wave's largest (-inf: the lane / the wave has nothing left to find)
-        float mine = act ? r2 : -inf_f();
-        float tmax = wave_max(mine);
-        bool gnear = gb + lane < ng;
-        if (gnear) {
-          const float* gp = fgbox + (long long)(gb + lane) * 8;
-          const f32x4 glo = *reinterpret_cast<const f32x4*>(gp);
-          gnear = glo[3] > 0.f;  // a group without a finite point: none of its tiles is looked at
-          if (pass == 1 && gnear) gnear = !(box_box_d2(qlo, qhi, glo, *reinterpret_cast<const f32x4*>(gp + 4)) > tmax);
-        }
-        unsigned long long gmask = __ballot(gnear);
-        while (gmask) {
-          const int tb = (gb + __builtin_ctzll(gmask)) * 64;
-          gmask &= gmask - 1;
-          const int t = tb + lane;
-          bool tnear = t < ntiles && in_ring(t, tile, grid_w) == (pass == 0);
-          if (MODE == WALK_LINK && tnear) tnear = clean_tile_point(t, 0, grid_w) < qmax;  // (only candidates below the query unite)
-          if (tnear) {
-            const float* bp = fbox + (long long)t * 8;
-            const f32x4 blo = *reinterpret_cast<const f32x4*>(bp);
-            tnear = blo[3] > 0.f;  // a tile without a finite point is never loaded (its box is lo = +inf, hi = -inf)
-            if (pass == 1 && tnear) tnear = !(box_box_d2(qlo, qhi, blo, *reinterpret_cast<const f32x4*>(bp + 4)) > tmax);
-          }
-          unsigned long long tmask = __ballot(tnear);
-          while (tmask) {
-            const int tt = tb + __builtin_ctzll(tmask);
-            tmask &= tmask - 1;
-            // per query: can the tile hold a point within this lane's bound?
-            const float* bp = fbox + (long long)tt * 8;
-            const float lbq = point_box_d2(q, *reinterpret_cast<const f32x4*>(bp), *reinterpret_cast<const f32x4*>(bp + 4));
-            if (!__ballot(mine > -inf_f() && !(lbq > mine))) continue;
-            const int ci = clean_tile_point(tt, lane, grid_w);
-            f32x4 p = (f32x4){nan_f(), nan_f(), nan_f(), 0.f};
-            if (ci < P) p = *reinterpret_cast<const f32x4*>(cand + (long long)ci * 4);
-            bool cok = finite3(p);  // NaN points take no part
-            int pv = 0;             // LINK: a parent of the candidate (possibly stale: still in its tree); BORDER: its root
-            if (MODE != WALK_COUNT) {
-              cok = cok && ccore[ci] != 0;
-              if (cok) pv = MODE == WALK_LINK ? uf_load(cpar + ci) : cpar[ci];
-            }
-            unsigned long long cm = __ballot(cok);
-            while (cm) {
-              const int j = __builtin_ctzll(cm);
-              cm &= cm - 1;
-              const float cx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p[0]), j));
-              const float cy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p[1]), j));
-              const float cz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p[2]), j));
-              const float dx = cx - q[0], dy = cy - q[1], dz = cz - q[2];
-              const float d2 = gap_d2(dx, dy, dz);  // (NaN for a NaN query: the compare fails)
-              const bool hit = act && d2 <= r2;
-              if (MODE == WALK_COUNT) {
-                cnt += hit ? 1 : 0;
-              } else {
-                const int pj = __builtin_amdgcn_readlane(pv, j);
-                if (MODE == WALK_BORDER) {
-                  best = (hit && pj < best) ? pj : best;
-                } else {
-                  const int cj = __builtin_amdgcn_readlane(ci, j);
-                  if (hit && cj < qi && pj != cur) {  // (pj == cur: the candidate already hangs under this lane's root)
-                    const int r = uf_unite(cpar, cur, pj, bound, bad);
-                    if (bad) {
-                      act = false;
-                    } else {
-                      cur = r;
-                      if (r < pj) atomicMin(cpar + cj, r);  // shorten the candidate's path: r is in its tree and below its parent
-                    }
-                  }
-                }
-              }
-            }
-            if (MODE == WALK_COUNT) {
-              cnt = cnt < cap ? cnt : cap;
-              act = act && cnt < cap;  // a query that has reached min_samples has nothing left to find
-            }
-            mine = act ? r2 : -inf_f();
-          }
-          tmax = wave_max(mine);  // (bounds only shrink: the group mask taken with the older value stays valid)
-        }
-      }
-    }
+    const f32x4 qlo = *reinterpret_cast<const f32x4*>(cv.box + (long long)tile * 8), qhi = *reinterpret_cast<const f32x4*>(cv.box + (long long)tile * 8 + 4);
+    for (int pass = 0; pass < 2; ++pass) walk_cloud(cv, q, qlo, qhi, tile, pass == 0 ? VISIT_RING : VISIT_REST, vis);
   }
 
   if (MODE == WALK_COUNT) {
-    if (qi < P) ccore[qi] = (valid && cnt >= cap) ? 1 : 0;
+    if (qi < P) ccore[qi] = (valid && vis.cnt >= cap) ? 1 : 0;
   } else if (MODE == WALK_LINK) {
-    if (qcore && !bad && cur < qi) atomicMin(cpar + qi, cur);  // shorten the query's own path
-    if (bad) atomicOr(state + cloud * MVT_CLUSTER_STATE_WORDS + MVT_CLUSTER_STATUS, (unsigned long long)MVT_CLUSTER_BOUND);
+    if (qcore && !vis.bad && vis.cur < qi) atomicMin(cpar + qi, vis.cur);  // shorten the query's own path
+    if (vis.bad) atomicOr(state + cloud * MVT_CLUSTER_STATE_WORDS + MVT_CLUSTER_STATUS, (unsigned long long)MVT_CLUSTER_BOUND);
   } else {
-    if (qi < P) root[cloud * P + qi] = qcore ? cpar[qi] : ((valid && best < bound) ? best : -1);
+    if (qi < P) root[cloud * P + qi] = qcore ? cpar[qi] : ((valid && vis.best < bound) ? vis.best : -1);
   }
 }
 
@@ -338,16 +312,6 @@ __global__ __launch_bounds__(CF_WG) void cluster_finish_kernel(const float* __re
   }
 }
 
-inline bool cluster_shape_ok(int C, long long P, int grid_w, int grid_h) {
-  return C > 0 && C <= 65535 && P > 0 && P < (1ll << 31) - 64 &&
-         ((grid_w == 0 && grid_h == 0) || (grid_w > 0 && grid_h > 0 && grid_w % 8 == 0 && grid_h % 8 == 0 && P == (long long)grid_w * grid_h));
-}
-
-inline unsigned strided_blocks(long long total) {
-  const long long b = mvt_cdiv(total, 256);
-  return (unsigned)(b > 8192 ? 8192 : b);
-}
-
 }  // namespace
 
 extern "C" int mvt_cluster_crop(float* xyz, int C, long long P, const float* region_T_world, const float* bounds, void* stream) {
@@ -362,7 +326,7 @@ extern "C" int mvt_cluster_crop(float* xyz, int C, long long P, const float* reg
 
 extern "C" int mvt_cluster_count(const float* xyz, int C, long long P, int grid_w, int grid_h, float r2, int min_samples, const float* tile_box,
                                  const float* group_box, unsigned char* core, void* stream) {
-  MVT_REQUIRE(aligned(xyz, 16) && aligned(tile_box, 16) && aligned(group_box, 16) && core != nullptr && cluster_shape_ok(C, P, grid_w, grid_h));
+  MVT_REQUIRE(aligned(xyz, 16) && aligned(tile_box, 16) && aligned(group_box, 16) && core != nullptr && cloud_shape_ok(C, P, grid_w, grid_h));
   MVT_REQUIRE(r2 > 0.f && r2 < INFINITY && min_samples >= 1 && min_samples < (1 << 30));
   const int ntiles = (int)((P + 63) / 64);
   hipLaunchKernelGGL(cluster_walk_kernel<WALK_COUNT>, dim3((unsigned)mvt_cdiv(ntiles, CL_WG / 64), (unsigned)C), dim3(CL_WG), 0, mvt_stream(stream),
@@ -372,7 +336,7 @@ extern "C" int mvt_cluster_count(const float* xyz, int C, long long P, int grid_
 
 extern "C" int mvt_cluster_link(const float* xyz, int C, long long P, int grid_w, int grid_h, float r2, const float* tile_box,
                                 const float* group_box, const unsigned char* core, int* parent, long long* state, void* stream) {
-  MVT_REQUIRE(aligned(xyz, 16) && aligned(tile_box, 16) && aligned(group_box, 16) && core != nullptr && cluster_shape_ok(C, P, grid_w, grid_h));
+  MVT_REQUIRE(aligned(xyz, 16) && aligned(tile_box, 16) && aligned(group_box, 16) && core != nullptr && cloud_shape_ok(C, P, grid_w, grid_h));
   MVT_REQUIRE(r2 > 0.f && r2 < INFINITY && aligned(parent, 4) && aligned(state, 8));
   const int ntiles = (int)((P + 63) / 64);
   const long long total = (long long)C * P;
@@ -388,7 +352,7 @@ extern "C" int mvt_cluster_link(const float* xyz, int C, long long P, int grid_w
 
 extern "C" int mvt_cluster_border(const float* xyz, int C, long long P, int grid_w, int grid_h, float r2, const float* tile_box,
                                   const float* group_box, const unsigned char* core, const int* parent, int* root, void* stream) {
-  MVT_REQUIRE(aligned(xyz, 16) && aligned(tile_box, 16) && aligned(group_box, 16) && core != nullptr && cluster_shape_ok(C, P, grid_w, grid_h));
+  MVT_REQUIRE(aligned(xyz, 16) && aligned(tile_box, 16) && aligned(group_box, 16) && core != nullptr && cloud_shape_ok(C, P, grid_w, grid_h));
   MVT_REQUIRE(r2 > 0.f && r2 < INFINITY && aligned(parent, 4) && aligned(root, 4));
   const int ntiles = (int)((P + 63) / 64);
   hipLaunchKernelGGL(cluster_walk_kernel<WALK_BORDER>, dim3((unsigned)mvt_cdiv(ntiles, CL_WG / 64), (unsigned)C), dim3(CL_WG), 0, mvt_stream(stream),

@@ -2,7 +2,7 @@
 // voxel_down_sample and estimate_normals(KDTreeSearchParamHybrid(radius, max_nn))).  Two independent parts:
 //
 // normals      - PCA normals of every point of a cloud over its max_nn nearest points within the radius.  The walk is
-//                clean_search_kernel's (cloud_clean.hip): a wave owns one tile of 64 points, ONE QUERY PER LANE, candidates are
+//                walk_cloud (cloud_search.h), as in cloud_clean.hip: a wave owns one tile of 64 points, ONE QUERY PER LANE, candidates are
 //                broadcast lane by lane; pass 0 visits the ring, pass 1 the rest through the group and tile boxes, and a box is
 //                skipped only when its lower bound EXCEEDS the lane's bound (strictly: an equal-d2 point with a lower index in a
 //                tile visited later still wins).  What differs is the list: a query keeps the max_nn smallest (d2, index) PAIRS in
@@ -19,6 +19,7 @@
 //                scatter as mvt_query_pool), each writing its cell's mean, count and first index; then the labels.
 // No fused multiply-add is formed from a product and a sum written separately in this file: the fp64 results are those of the
 // same operations in numpy.
+#include "block_scan.h"
 #include "cloud_search.h"
 
 #pragma clang fp contract(off)
@@ -29,6 +30,7 @@ typedef unsigned long long u64;
 
 constexpr int NE_SWEEPS = 8;  // cyclic Jacobi sweeps of a 3x3 (fp64 converges in 4 to 5)
 constexpr int VX_WG = 256;
+static_assert(VX_WG == SCAN_WG, "block_counts_scan is written for this workgroup size");
 constexpr u64 VX_EMPTY = ~0ull;  // (a key has 63 bits)
 
 __device__ __forceinline__ double nan_d() { return __longlong_as_double(0x7ff8000000000000ll); }
@@ -79,6 +81,51 @@ __device__ __forceinline__ bool smallest_eigenvector(const double (&c6)[6], doub
   return true;
 }
 
+// What a query keeps during the walk: the K smallest (d2, index) pairs in its LDS columns, with r2 as the bound until the list is
+// full and the largest d2 afterwards.  Candidates arrive in ascending index order within a tile.
+struct normals_visitor : walk_defaults {
+  float* ld2;  // entry k of this lane's query: ld2[k * 64], lix[k * 64]
+  int* lix;
+  int K;
+  float r2;
+  bool valid;
+  int cnt, wpos, widx;  // entries kept; the place and the key (wd2, widx) of the largest once cnt == K
+  float wd2;
+  __device__ __forceinline__ normals_visitor(float* ld2_, int* lix_, int K_, float r2_, bool valid_)
+      : ld2(ld2_), lix(lix_), K(K_), r2(r2_), valid(valid_), cnt(0), wpos(0), widx(-1), wd2(-1.f) {}
+  // r^2 until the list is full, then its largest d2 (-inf: no query in this lane)
+  __device__ __forceinline__ float bound() const { return valid ? (cnt < K ? r2 : wd2) : -inf_f(); }
+  __device__ __forceinline__ bool candidate(int, const f32x4& p) const { return finite3(p); }  // NaN points take no part
+  __device__ __forceinline__ void visit(int j, int ci, float d2) {
+    const int cj = __builtin_amdgcn_readlane(ci, j);
+    bool rescan = false;
+    if (cnt < K) {
+      if (d2 < r2) {
+        ld2[cnt * 64] = d2;
+        lix[cnt * 64] = cj;
+        rescan = ++cnt == K;
+      }
+    } else if (d2 < wd2 || (d2 == wd2 && cj < widx)) {
+      ld2[wpos * 64] = d2;
+      lix[wpos * 64] = cj;
+      rescan = true;
+    }
+    if (rescan) {  // the largest key of the full list
+      wd2 = -1.f;
+      widx = -1;
+      for (int k = 0; k < K; ++k) {
+        const float v = ld2[k * 64];
+        const int ix = lix[k * 64];
+        if (v > wd2 || (v == wd2 && ix > widx)) {
+          wd2 = v;
+          widx = ix;
+          wpos = k;
+        }
+      }
+    }
+  }
+};
+
 // One wave per (cloud, tile); lane = query.  LDS: [K][64] d2, then [K][64] indices.
 __global__ __launch_bounds__(64) void normals_kernel(const float* __restrict__ xyz, long long P, int ntiles, int grid_w, int K, float r2,
                                                      const float* __restrict__ box, const float* __restrict__ gbox,
@@ -88,95 +135,21 @@ __global__ __launch_bounds__(64) void normals_kernel(const float* __restrict__ x
   const int lane = threadIdx.x;
   const int tile = blockIdx.x;  // (< ntiles: the grid has exactly ntiles workgroups per cloud)
   const long long cloud = blockIdx.y;
-  const float* __restrict__ cand = xyz + cloud * P * 4;
-  const int ng = (ntiles + 63) >> 6;
-  const float* __restrict__ fbox = box + cloud * ntiles * 8;
-  const float* __restrict__ fgbox = gbox + cloud * ng * 8;
+  const cloud_view cv = cloud_of(xyz, box, gbox, cloud, P, ntiles, grid_w);
+  const float* __restrict__ cand = cv.xyz;
   float* ld2 = lds + lane;                                    // entry k of this lane's query: ld2[k * 64], lix[k * 64]
   int* lix = reinterpret_cast<int*>(lds + (size_t)K * 64) + lane;
 
-  const int qi = clean_tile_point(tile, lane, grid_w);
+  const int qi = cloud_tile_point(tile, lane, grid_w);
   f32x4 q = (f32x4){nan_f(), nan_f(), nan_f(), 0.f};
   if (qi < P) q = *reinterpret_cast<const f32x4*>(cand + (long long)qi * 4);
   const bool valid = finite3(q);
-  int cnt = 0, wpos = 0, widx = -1;  // entries kept; the place and the key (wd2, widx) of the largest once cnt == K
-  float wd2 = -1.f;
-  const f32x4 qlo = *reinterpret_cast<const f32x4*>(fbox + (long long)tile * 8), qhi = *reinterpret_cast<const f32x4*>(fbox + (long long)tile * 8 + 4);
+  const f32x4 qlo = *reinterpret_cast<const f32x4*>(cv.box + (long long)tile * 8), qhi = *reinterpret_cast<const f32x4*>(cv.box + (long long)tile * 8 + 4);
 
+  normals_visitor vis(ld2, lix, K, r2, valid);
   const int npass = __ballot(valid) ? 2 : 0;  // (a tile of NaNs has nothing to search for)
-  for (int pass = 0; pass < npass; ++pass) {
-    for (int gb = 0; gb < ng; gb += 64) {
-      // this lane's bound: r^2 until the list is full, then its largest d2 (-inf: no query in this lane)
-      float mine = valid ? (cnt < K ? r2 : wd2) : -inf_f();
-      float tmax = wave_max(mine);
-      bool gnear = gb + lane < ng;
-      if (pass == 1 && gnear) {
-        const float* gp = fgbox + (long long)(gb + lane) * 8;
-        const float lb = box_box_d2(qlo, qhi, *reinterpret_cast<const f32x4*>(gp), *reinterpret_cast<const f32x4*>(gp + 4));
-        gnear = !(lb > tmax);  // (strict; a NaN bound never culls)
-      }
-      unsigned long long gmask = __ballot(gnear);
-      while (gmask) {
-        const int tb = (gb + __builtin_ctzll(gmask)) * 64;
-        gmask &= gmask - 1;
-        const int t = tb + lane;
-        bool tnear = t < ntiles && in_ring(t, tile, grid_w) == (pass == 0);
-        if (pass == 1 && tnear) {
-          const float* bp = fbox + (long long)t * 8;
-          const float lb = box_box_d2(qlo, qhi, *reinterpret_cast<const f32x4*>(bp), *reinterpret_cast<const f32x4*>(bp + 4));
-          tnear = !(lb > tmax);
-        }
-        unsigned long long tmask = __ballot(tnear);
-        while (tmask) {
-          const int tt = tb + __builtin_ctzll(tmask);
-          tmask &= tmask - 1;
-          const float* bp = fbox + (long long)tt * 8;
-          const float lbq = point_box_d2(q, *reinterpret_cast<const f32x4*>(bp), *reinterpret_cast<const f32x4*>(bp + 4));
-          if (!__ballot(mine > -inf_f() && !(lbq > mine))) continue;
-          const int ci = clean_tile_point(tt, lane, grid_w);
-          f32x4 p = (f32x4){nan_f(), nan_f(), nan_f(), 0.f};
-          if (ci < P) p = *reinterpret_cast<const f32x4*>(cand + (long long)ci * 4);
-          unsigned long long cm = __ballot(finite3(p));  // NaN points take no part
-          while (cm) {
-            const int j = __builtin_ctzll(cm);
-            cm &= cm - 1;
-            const float cx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p[0]), j));
-            const float cy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p[1]), j));
-            const float cz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p[2]), j));
-            const int cj = __builtin_amdgcn_readlane(ci, j);
-            const float d2 = gap_d2(cx - q[0], cy - q[1], cz - q[2]);  // (NaN for a NaN query: every compare fails)
-            bool rescan = false;
-            if (cnt < K) {
-              if (d2 < r2) {
-                ld2[cnt * 64] = d2;
-                lix[cnt * 64] = cj;
-                rescan = ++cnt == K;
-              }
-            } else if (d2 < wd2 || (d2 == wd2 && cj < widx)) {
-              ld2[wpos * 64] = d2;
-              lix[wpos * 64] = cj;
-              rescan = true;
-            }
-            if (rescan) {  // the largest key of the full list
-              wd2 = -1.f;
-              widx = -1;
-              for (int k = 0; k < K; ++k) {
-                const float v = ld2[k * 64];
-                const int ix = lix[k * 64];
-                if (v > wd2 || (v == wd2 && ix > widx)) {
-                  wd2 = v;
-                  widx = ix;
-                  wpos = k;
-                }
-              }
-            }
-          }
-          mine = valid ? (cnt < K ? r2 : wd2) : -inf_f();
-        }
-        tmax = wave_max(mine);  // (bounds only shrink: the group mask taken with the older value stays valid)
-      }
-    }
-  }
+  for (int pass = 0; pass < npass; ++pass) walk_cloud(cv, q, qlo, qhi, tile, pass == 0 ? VISIT_RING : VISIT_REST, vis);
+  const int cnt = vis.cnt;
 
   // The list in ascending (d2, index) order: neighbour indices out, S1 and S2 of the exact differences in fp64.
   double s1[3] = {0.0, 0.0, 0.0}, s2[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -403,28 +376,8 @@ __global__ __launch_bounds__(VX_WG) void voxel_count_kernel(const float* __restr
   if (threadIdx.x == 0) block_counts[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
 }
 
-// One workgroup: block_counts[nb] -> exclusive prefix in place, the total to *n_out.  Thread t owns [t * chunk, (t + 1) * chunk).
 __global__ __launch_bounds__(VX_WG) void voxel_scan_kernel(int* __restrict__ block_counts, int nb, int chunk, int* __restrict__ n_out) {
-  __shared__ long long s_sum[VX_WG];
-  const long long b0 = (long long)threadIdx.x * chunk;
-  long long sum = 0;
-  for (int j = 0; j < chunk; ++j)
-    if (b0 + j < nb) sum += block_counts[b0 + j];
-  s_sum[threadIdx.x] = sum;
-  __syncthreads();
-  long long off = 0, total = 0;
-  for (int w = 0; w < VX_WG; ++w) {
-    const long long v = s_sum[w];
-    off += w < (int)threadIdx.x ? v : 0;
-    total += v;
-  }
-  for (int j = 0; j < chunk; ++j)
-    if (b0 + j < nb) {
-      const int c = block_counts[b0 + j];
-      block_counts[b0 + j] = (int)off;
-      off += c;
-    }
-  if (threadIdx.x == 0) *n_out = (int)total;
+  block_counts_scan(block_counts, nb, chunk, n_out);
 }
 
 __global__ __launch_bounds__(VX_WG) void voxel_scatter_kernel(const float* __restrict__ xyz, long long P, const long long* __restrict__ state, VoxelTable t,
@@ -479,8 +432,7 @@ extern "C" int mvt_normals_estimate(const float* xyz, int C, long long P, int gr
   MVT_REQUIRE(aligned(xyz, 16) && aligned(tile_box, 16) && aligned(group_box, 16) && aligned(nrm, 16));
   MVT_REQUIRE((viewpoint == nullptr || aligned(viewpoint, 4)) && (nbr_idx == nullptr || aligned(nbr_idx, 4)) &&
               (nbr_cnt == nullptr || aligned(nbr_cnt, 4)) && (cov == nullptr || aligned(cov, 8)));
-  MVT_REQUIRE(C > 0 && C <= 65535 && P > 0 && P < (1ll << 31) - 64);
-  MVT_REQUIRE((grid_w == 0 && grid_h == 0) || (grid_w > 0 && grid_h > 0 && grid_w % 8 == 0 && grid_h % 8 == 0 && P == (long long)grid_w * grid_h));
+  MVT_REQUIRE(cloud_shape_ok(C, P, grid_w, grid_h));
   MVT_REQUIRE(max_nn >= 3 && max_nn <= MVT_NORMALS_MAX_NN && radius > 0.f);  // (radius = +inf: plain kNN; NaN fails the compare)
   const int ntiles = (int)((P + 63) / 64);
   hipLaunchKernelGGL(normals_kernel, dim3((unsigned)ntiles, (unsigned)C), dim3(64), (size_t)max_nn * 512, mvt_stream(stream), xyz, P, ntiles, grid_w,
@@ -500,8 +452,7 @@ extern "C" int mvt_voxel_bounds(const float* xyz, long long P, double voxel, dou
 extern "C" int mvt_voxel_insert(const float* xyz, long long P, long long* state, long long* table, long long capacity, void* stream) {
   MVT_REQUIRE(voxel_args(xyz, P, state) && aligned(table, 8) && voxel_capacity(capacity, P));
   const VoxelTable t = voxel_table(table, capacity);
-  const long long cb = mvt_cdiv(capacity, VX_WG);
-  hipLaunchKernelGGL(voxel_clear_kernel, dim3((unsigned)(cb > 8192 ? 8192 : cb)), dim3(VX_WG), 0, mvt_stream(stream), t);
+  hipLaunchKernelGGL(voxel_clear_kernel, dim3(strided_blocks(capacity)), dim3(VX_WG), 0, mvt_stream(stream), t);
   hipLaunchKernelGGL(voxel_insert_kernel, dim3((unsigned)mvt_cdiv(P, VX_WG)), dim3(VX_WG), 0, mvt_stream(stream), xyz, P, state, t);
   return mvt_launch_status();
 }

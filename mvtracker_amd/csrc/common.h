@@ -140,3 +140,22 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
   }
   return v;
 }
+
+__device__ __forceinline__ double wave_sum_f64(double v) {  // the fixed tree: lane l + lane (l ^ 32), then ^ 16, ... ^ 1: the same bits in every run
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// Sum over a workgroup of 256 threads: the fixed tree per wave, then the four waves in order; every thread gets the sum.  s_red: 4 doubles.
+__device__ __forceinline__ double block_sum_f64(double v, double* s_red) {
+  v = wave_sum_f64(v);
+  __syncthreads();  // (s_red may still be read from the previous call)
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+}
+
+// A word of a kernel's 64-bit state row, seen as a double.
+__device__ __forceinline__ double& st_f64(long long* state, int w) { return reinterpret_cast<double*>(state)[w]; }
+__device__ __forceinline__ double st_f64(const long long* state, int w) { return reinterpret_cast<const double*>(state)[w]; }

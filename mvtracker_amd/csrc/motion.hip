@@ -34,12 +34,6 @@ __device__ __forceinline__ float window_max(const float* q, long long stride, in
   return m;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // Four adjacent pixels of one channel plane as fp32.  VEC: the group is whole and its address aligned (the entry checks both);
 // otherwise element by element, pixels at or past `n` reading as 0.
 template <bool U8, bool VEC>

@@ -2,13 +2,14 @@
 // frame (unprojection + confidence / cylinder test + order-preserving compaction) and k-means over it (greedy k-means++ seeding,
 // Lloyd iterations).  Everything that is summed across lanes or workgroups is an INTEGER (fixed point), so results do not depend
 // on the order of addition: two runs give the same bits.  No kernel waits on another workgroup; every loop is bounded by an argument.
-#include "common.h"
+#include "block_scan.h"
 
 namespace {
 
 typedef unsigned long long u64;
 
 constexpr int QS_WG = 256;          // threads per workgroup of every kernel here
+static_assert(QS_WG == SCAN_WG, "wg_excl_scan_u64 and block_counts_scan are written for this workgroup size");
 constexpr int QS_TILE = 4 * QS_WG;  // points per tile of the k-means kernels (4 per lane)
 constexpr int QS_MAX_K = MVT_KMEANS_MAX_K;
 constexpr int QS_MAX_CAND = MVT_KMEANS_MAX_CAND;
@@ -20,41 +21,10 @@ enum { ST_LO = MVT_KM_LO, ST_HI = MVT_KM_HI, ST_SCALE = MVT_KM_SCALE, ST_SCALE2 
        ST_CONV = MVT_KM_CONVERGED, ST_EMPTY = MVT_KM_EMPTY, ST_INERTIA = MVT_KM_INERTIA, ST_INERTIA_ACC = MVT_KM_INERTIA_ACC,
        ST_SHIFT = MVT_KM_SHIFT, ST_POT = MVT_KM_POT, ST_CAND = MVT_KM_CAND };
 
-__device__ __forceinline__ double& st_f64(long long* state, int w) { return reinterpret_cast<double*>(state)[w]; }
-__device__ __forceinline__ double st_f64(const long long* state, int w) { return reinterpret_cast<const double*>(state)[w]; }
-
 __device__ __forceinline__ u64 wave_sum_u64(u64 v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += shfl_xor_u64(v, o);
   return v;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {  // fixed tree: the same bits for the same inputs
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// Exclusive prefix sum of v over the 256 threads of the workgroup (thread order); total = the sum of all.  lds: 4 words.
-__device__ __forceinline__ u64 wg_excl_scan_u64(u64 v, u64* lds, u64& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  u64 inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    unsigned lo = __shfl_up((unsigned)inc, o, 64), hi = __shfl_up((unsigned)(inc >> 32), o, 64);
-    if (lane >= o) inc += ((u64)hi << 32) | lo;
-  }
-  if (lane == 63) lds[wave] = inc;
-  __syncthreads();
-  u64 woff = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < QS_WG / 64; ++w) {
-    if (w < wave) woff += lds[w];
-    total += lds[w];
-  }
-  __syncthreads();  // lds may be reused at once
-  return woff + inc - v;
 }
 
 // ------------------------------------------------------------------------------------------------------------- candidate pool
@@ -93,23 +63,8 @@ __global__ __launch_bounds__(QS_WG) void pool_count_kernel(PoolArgs a, int n, in
   if (threadIdx.x == 0) block_counts[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
 }
 
-// One workgroup: block_counts[nb] -> exclusive prefix in place, the total to *count.  Thread t owns the contiguous chunk
-// [t * chunk, (t + 1) * chunk).
 __global__ __launch_bounds__(QS_WG) void pool_scan_kernel(int* __restrict__ block_counts, int nb, int chunk, int* __restrict__ count) {
-  __shared__ u64 s_scan[QS_WG / 64];
-  const int b0 = threadIdx.x * chunk;
-  u64 sum = 0;
-  for (int j = 0; j < chunk; ++j)
-    if (b0 + j < nb) sum += (u64)block_counts[b0 + j];
-  u64 total;
-  u64 off = wg_excl_scan_u64(sum, s_scan, total);
-  for (int j = 0; j < chunk; ++j)
-    if (b0 + j < nb) {
-      const int c = block_counts[b0 + j];
-      block_counts[b0 + j] = (int)off;
-      off += (u64)c;
-    }
-  if (threadIdx.x == 0) *count = (int)total;
+  block_counts_scan(block_counts, nb, chunk, count);
 }
 
 __global__ __launch_bounds__(QS_WG) void pool_scatter_kernel(PoolArgs a, int n, const int* __restrict__ block_base, float* __restrict__ pool) {

@@ -141,17 +141,7 @@ __device__ __forceinline__ int reflect101(int i, int n) {  // one reflection, th
   return min(max(i, 0), n - 1);
 }
 
-__device__ __forceinline__ double shfl_xor_f64(double v, int o) { return __longlong_as_double((long long)shfl_xor_u64((u64)__double_as_longlong(v), o)); }
-
-// fixed tree, the four waves in order; the sum is valid in thread 0
-__device__ __forceinline__ double sc_block_sum(double v, double* s_red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += shfl_xor_f64(v, o);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-}
+// the integer twin of block_sum_f64 (common.h)
 __device__ __forceinline__ u64 sc_block_sum(u64 v, u64* s_red) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += shfl_xor_u64(v, o);
@@ -233,8 +223,8 @@ __global__ __launch_bounds__(RP_WG) void score_tiles_kernel(const void* __restri
   n_cov = sc_block_sum(n_cov, s_red), sse = sc_block_sum(sse, s_red), sae = sc_block_sum(sae, s_red);
   sse_c = sc_block_sum(sse_c, s_red), sae_c = sc_block_sum(sae_c, s_red);
   n_depth = sc_block_sum(n_depth, s_red), n_close = sc_block_sum(n_close, s_red);
-  ssim = sc_block_sum(ssim, s_redd), ssim_c = sc_block_sum(ssim_c, s_redd);
-  dsum = sc_block_sum(dsum, s_redd), dsum_c = sc_block_sum(dsum_c, s_redd);
+  ssim = block_sum_f64(ssim, s_redd), ssim_c = block_sum_f64(ssim_c, s_redd);
+  dsum = block_sum_f64(dsum, s_redd), dsum_c = block_sum_f64(dsum_c, s_redd);
   if (threadIdx.x == 0) {
     const long long blk = ((long long)pair * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     u64* o = partial + blk * SC_WORDS;

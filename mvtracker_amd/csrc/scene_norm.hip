@@ -21,14 +21,6 @@ enum { WS_PREFIX = 256, WS_RANK = 257, WS_CNT_LE = 258, WS_MIN_GT = 259 };
 __device__ __forceinline__ u32 fkey(u32 b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 __device__ __forceinline__ u32 funkey(u32 k) { return (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k; }
 
-__device__ __forceinline__ double& st_f64(long long* state, int w) { return reinterpret_cast<double*>(state)[w]; }
-
-__device__ __forceinline__ double wave_sum_f64(double v) {  // fixed tree: the same bits for the same inputs
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // (every thread of a 256-thread workgroup) a fresh select for rank k: empty histogram, empty prefix
 __device__ __forceinline__ void sel_reset(u32* __restrict__ ws, u32 k) {
   ws[threadIdx.x] = 0;

@@ -443,6 +443,17 @@ def tile_group_aabb(box, Pn, T, group_box):
     _call("mvt_tile_group_aabb", _ptr(box), Pn, T, _ptr(group_box), _stream())
 
 
+def cloud_boxes(xyz, n_clouds, n_points, grid):
+    """The boxes that every cloud search walks, of clouds xyz (n_clouds, n_points, 4): ``tile_aabb`` then ``tile_group_aabb``.
+    Returns (box (n_clouds, tiles, 8), gbox (n_clouds, ceil(tiles / 64), 8))."""
+    nt = (n_points + 63) // 64
+    box = torch.empty(n_clouds, nt, 8, device=xyz.device)
+    gbox = torch.empty(n_clouds, (nt + 63) // 64, 8, device=xyz.device)
+    tile_aabb(xyz, n_points, n_clouds, box, grid)
+    tile_group_aabb(box, n_points, n_clouds, gbox)
+    return box, gbox
+
+
 def knn_search(xyz, Pn, coords, N, S, frame0, frame_step, T, K, idx_out, box, grid=(0, 0), gbox=None, seed_idx=None, seed_k=0,
                seed_dims=(0, 0, 0, 0)):
     """``knn_scan`` (one segment) + ``knn_merge`` in one launch: neighbour indices straight to idx_out (N,S,K) int32."""

@@ -14,6 +14,7 @@ and the wrong divisor.
    restatement decides the same at r (1 -+ 1e-5), at most 0.1 % undecided.
 3. Two runs give the same bits.  4. The predictor / streaming wiring, bit for bit.
 Every figure is printed before it is asserted."""
+import functools
 import os
 import sys
 
@@ -316,3 +317,86 @@ def test_wiring_predictor_and_stream(predictor, e2e_clip):
         outs.append(st.finish())
         assert torch.equal(torch.cat([o["traj_e"] for o in outs], 1), off["traj_e"])
         assert torch.equal(torch.cat([o["vis_e_as_prob"] for o in outs], 1), off["vis_e_as_prob"])
+
+
+# ------------------------------------------------------------------------------------------- 5. more than 64 groups of tiles
+# The searches' shared walk takes the groups of tiles 64 at a time, so a cloud needs more than 4096 tiles to reach the second round.
+# 65 * 64 * 64 lattice points, coordinates integers / 64 (every fp32 d2 is exact), stored as a point list of 4x4x4 blocks, one block
+# per tile (tight boxes), the BLOCKS in a seeded random order: 4160 tiles in 65 groups, neighbours on both sides of group 64.
+BIG_BLOCKS, BIG_SEED = (13, 20, 16), 11
+BIG_R2 = 6.5  # in lattice steps: no lattice distance (6 and 8 are); 81 offsets lie within it
+
+
+@functools.lru_cache(maxsize=None)
+def big_lattice():
+    """(xyz (P, 4) float32, slot (X, Y, Z): the list index of every lattice point)."""
+    bx, by, bz = BIG_BLOCKS
+    nb = bx * by * bz
+    tile_of_block = np.random.default_rng(BIG_SEED).permutation(nb).reshape(bx, by, bz)
+    i, j, k = np.meshgrid(np.arange(4 * bx), np.arange(4 * by), np.arange(4 * bz), indexing="ij")
+    slot = tile_of_block[i // 4, j // 4, k // 4] * 64 + (i % 4) * 16 + (j % 4) * 4 + k % 4
+    xyz = np.zeros((nb * 64, 4), np.float32)
+    xyz[slot.ravel(), 0], xyz[slot.ravel(), 1], xyz[slot.ravel(), 2] = i.ravel() / 64, j.ravel() / 64, k.ravel() / 64
+    return xyz, slot
+
+
+def lattice_offsets(r2):
+    m = int(np.sqrt(r2))
+    return [(a, b, c) for a in range(-m, m + 1) for b in range(-m, m + 1) for c in range(-m, m + 1) if a * a + b * b + c * c < r2]
+
+
+def shifted(a, o, fill):
+    """b[p] = a[p + o] where p + o lies in the lattice, else fill."""
+    b = np.full_like(a, fill)
+    src = tuple(slice(max(d, 0), a.shape[e] + min(d, 0)) for e, d in enumerate(o))
+    dst = tuple(slice(max(-d, 0), a.shape[e] + min(-d, 0)) for e, d in enumerate(o))
+    b[dst] = a[src]
+    return b
+
+
+def test_radius_counts_beyond_64_groups():
+    from mvtracker_amd import hip
+    xyz, slot = big_lattice()
+    P = xyz.shape[0]
+    offs = lattice_offsets(BIG_R2)
+    assert P == 65 * 64 * 64 and (P // 64 + 63) // 64 == 65 and len(offs) == 81
+    # the closed form: the lattice points within the radius, by shifted sums; and the pairs that only the second round of groups finds
+    want = np.zeros(slot.shape, np.int64)
+    across = np.zeros(slot.shape, bool)
+    for o in offs:
+        nb_slot = shifted(slot, o, -1)
+        want += nb_slot >= 0
+        across |= (slot // 64 < 4096) & (nb_slot // 64 >= 4096)
+    ref = np.empty(P, np.int64)
+    ref[slot.ravel()] = want.ravel()
+    x = dev(xyz[None])
+    box, gbox = hip.cloud_boxes(x, 1, P, (0, 0))
+    cnt = torch.empty(1, P, dtype=torch.int32, device=DEV)
+    # min_points = the largest possible count: no counter stops early, every lane keeps its bound to the end
+    hip.clean_search(x, 1, P, (0, 0), hip.CLEAN_RADIUS, 0, float(np.sqrt(BIG_R2) / 64), len(offs), box, gbox, c_out=cnt)
+    torch.cuda.synchronize()
+    got = cnt[0].cpu().numpy()
+    nd = int((got != ref).sum())
+    print(f"{P} points, {P // 64} tiles: counts {ref.min()}..{ref.max()}, {int(across.sum())} points below group 64 with a neighbour in it, "
+          f"counts differ at {nd}")
+    assert across.any() and nd == 0
+
+
+def test_nearest_indices_beyond_64_groups():
+    """The same cloud through the normals' search, max_nn = 8: on a lattice the 8 smallest (d2, index) pairs are full of equal d2, so
+    the indices check the tie rule across the round of groups as well."""
+    from mvtracker_amd import cloud
+    xyz, slot = big_lattice()
+    P = xyz.shape[0]
+    offs = lattice_offsets(3.5)  # 27 offsets: every point, a corner included, has at least 8 of them inside the lattice
+    d2 = np.array([a * a + b * b + c * c for a, b, c in offs], np.int64)
+    nb = np.stack([shifted(slot, o, -1).ravel() for o in offs], 1)  # (P, 27) in lattice order
+    key = np.where(nb >= 0, d2[None] * (1 << 32) + nb, np.int64(1) << 62)
+    ref = np.empty((P, 8), np.int64)
+    ref[slot.ravel()] = np.sort(key, 1)[:, :8] & 0xFFFFFFFF
+    assert (np.sort(key, 1)[:, 7] < (np.int64(1) << 62)).all()
+    _, idx, cnt, _ = cloud.normals_of_clouds(dev(xyz[None]), 1, P, (0, 0), float(np.sqrt(3.5) / 64), 8, details=True)
+    torch.cuda.synchronize()
+    nd = int((idx[0].cpu().numpy() != ref).any(1).sum())
+    print(f"{P} points: neighbour lists differ at {nd}, counts {int(cnt.min())}..{int(cnt.max())}")
+    assert nd == 0 and int(cnt.min()) == 8 and int(cnt.max()) == 8
