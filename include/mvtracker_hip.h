@@ -466,38 +466,29 @@ int mvt_attention_bf16_segmented(const void* q, int ldq, long long q_gs, long lo
 /* x[(r*S+s)*ld + 0:C] = v[r % n][0:C] for r < reps*n, all s: the virtual tokens of `reps` independent query sets. */
 int mvt_broadcast_rows_repeat(const float* v, float* x, int ld, int n, int S, int C, int reps, void* stream);
 
-/* Track state of one sliding window (mvtracker.py:505-511, 645-655, 695): n tracks (sorted by query frame), the first p0 of
- * them carried over from the previous window (prev_coords [p0][S][3], prev_vis [p0][S] logits; window stride S/2).
- * qxyz [n][3], qt [n] int32 query frames, feat_init [n][C].  Writes coords [n][S][3], mask_vis [n][S][2] = (track mask,
- * initial visibility), ffeats [n][S][C].  Window slot s reads frame min(w + s, T - 1). */
+/* Track state of one sliding window (mvtracker.py:505-511, 645-655, 695).  Slot s of the window is clip frame
+ * frame0 + frame_step * s, clamped to the clip [0, T): frame_step = +1 is the forward pass (n tracks sorted by query frame),
+ * frame_step = -1 the time-reversed pass of backward tracking (tracks sorted by DESCENDING query frame; qt holds the query frames
+ * themselves in both).  qxyz [n][3], qt [n] int32 query frames, feat_init [n][C].  Writes coords [n][S][3], mask_vis [n][S][2] =
+ * (track mask, initial visibility), ffeats [n][S][C].  A carried track continues from the second half of its row of the previous
+ * window (prev_coords [.][S][3], prev_vis [.][S] logits; window stride S/2), a new one starts at its query point with logit 10.
+ * Without a map (carry_src NULL) the first p0 tracks are carried, each from its own row.  With one (several independent query sets
+ * in one window, each with its own carried prefix) p0 must be 0, and carry_src[tr] >= 0 is the row of prev_* track tr continues
+ * from, -1 a track that enters here; prev_* may then be NULL only if no entry is >= 0.  The track mask of slot s, at frame f, is
+ * frame_step * (f - qt) >= 0 (the query frame reached), except in the half window the previous window covered
+ * (frame_step * (f - frame0) < S/2) for a carried track. */
 int mvt_window_prepare(const float* qxyz, const int* qt, const float* feat_init, const float* prev_coords, const float* prev_vis,
-                       int n, int p0, int S, int C, int w, int T, float* coords, float* mask_vis, float* ffeats, void* stream);
-/* mvt_window_prepare with an explicit carry map (several independent query sets in one window, each with its own carried
- * prefix): carry_src[tr] >= 0 is the row of prev_coords / prev_vis track tr continues from, -1 a track that enters here. */
-int mvt_window_prepare_mapped(const float* qxyz, const int* qt, const float* feat_init, const float* prev_coords, const float* prev_vis,
-                              const int* carry_src, int n, int S, int C, int w, int T, float* coords, float* mask_vis, float* ffeats,
-                              void* stream);
-/* Results of the window into the clip outputs in the caller's query order (mvtracker.py:692-693, 710-711): for s < min(S, T - w)
- * traj[(w+s)][order[i]] = coords[i][s], vis_logit = vis[i][s], vis_prob = sigmoid(vis[i][s]).  traj [T][N][3], vis_* [T][N],
- * order [n] int64. */
-int mvt_window_store(const float* coords, const float* vis, const long long* order, int n, int S, int w, int T, int N, float* traj,
-                     float* vis_logit, float* vis_prob, void* stream);
-/* mvt_window_store into a chunk of the clip (streaming): traj [f1-f0][N][3], vis_* [f1-f0][N] hold frames [f0, f1) of a clip of T
- * frames (T: as far as it is known, f1 <= T), and the window's slots s with f0 <= w + s < f1 go to row w + s - f0 -- what
- * mvt_window_store writes to those frames of the whole-clip tensors; no slot inside: nothing is written.  Rows no window writes keep
- * what the caller put there (zeros, as in the whole-clip result). */
-int mvt_window_store_chunk(const float* coords, const float* vis, const long long* order, int n, int S, int w, int T, int f0, int f1,
-                           int N, float* traj, float* vis_logit, float* vis_prob, void* stream);
-/* The window state and result store of the time-reversed pass (backward tracking).  wr is the window start in REVERSED time:
- * slot s is frame max(T-1-wr - s, 0) of the clip; the n tracks are sorted by DESCENDING query frame and qt [n] holds the query
- * frames themselves.  mvt_window_prepare_reversed is mvt_window_prepare on the time-flipped clip (track mask frame <= qt, carried
- * half excluded, slots past the clip's start repeat frame 0).  mvt_window_store_reversed writes slot s < min(S, T - wr) to frame
- * T-1-wr - s ONLY where that frame is < qt[i]: frames from the query frame on are the forward pass's and are never touched. */
-int mvt_window_prepare_reversed(const float* qxyz, const int* qt, const float* feat_init, const float* prev_coords,
-                                const float* prev_vis, int n, int p0, int S, int C, int wr, int T, float* coords, float* mask_vis,
-                                float* ffeats, void* stream);
-int mvt_window_store_reversed(const float* coords, const float* vis, const long long* order, const int* qt, int n, int S, int wr, int T,
-                              int N, float* traj, float* vis_logit, float* vis_prob, void* stream);
+                       const int* carry_src, int n, int p0, int S, int C, int frame0, int frame_step, int T, float* coords,
+                       float* mask_vis, float* ffeats, void* stream);
+/* Results of the window into the clip outputs in the caller's query order (mvtracker.py:692-693, 710-711).  traj [f1-f0][N][3],
+ * vis_* [f1-f0][N] hold frames [f0, f1) of a clip of T frames (T: as far as it is known, f1 <= T); the whole clip is f0 = 0,
+ * f1 = T, a chunk of it is what streaming emits.  Slot s whose frame f = frame0 + frame_step * s lies in the clip is written to row
+ * f - f0 iff f0 <= f < f1 and (before == NULL or f < before[i]):  traj[f - f0][order[i]] = coords[i][s], vis_logit = vis[i][s],
+ * vis_prob = sigmoid(vis[i][s]).  order [n] int64, before [n] int32.  The reversed pass gives its query frames as `before`: frames
+ * from the query frame on are the forward pass's and are never touched.  No slot inside [f0, f1): nothing is written.  Rows no
+ * window writes keep what the caller put there (zeros, in the tracker's results). */
+int mvt_window_store(const float* coords, const float* vis, const long long* order, const int* before, int n, int S, int frame0,
+                     int frame_step, int T, int f0, int f1, int N, float* traj, float* vis_logit, float* vis_prob, void* stream);
 
 /* Per-track evaluation metrics (mvtracker/evaluation/metrics.py:10-58, 61-171, 327-330; query_mode "first"): one row of
  * 11 + 2K floats per track -- movement, visible frames, occlusion accuracy (all / gt-occluded / gt-visible), average Jaccard,

@@ -62,18 +62,28 @@ __global__ __launch_bounds__(256) void token_assemble_kernel(const float* __rest
 }
 
 // Per-window track state (mvtracker.py:510-511, 645-680): one launch instead of a dozen tensor ops.
-//   coords [n][S][3]: tracks carried over from the previous window (n < p0) continue from its second half, the last estimate
-//                     held (:648-651); new tracks start at their query point (:510)
-//   mask_vis [n][S][2]: (track_mask, vis_init): the mask is (frame >= query frame) minus what earlier windows already covered
-//                     (:505-507, :695), window slots past the clip repeat the last frame (:598-604); vis_init is the previous
-//                     window's LOGIT for carried tracks (:653-655), 10 for new ones (:511)
+//   coords [n][S][3]: tracks carried over from the previous window continue from its second half, the last estimate held
+//                     (:648-651); new tracks start at their query point (:510)
+//   mask_vis [n][S][2]: (track_mask, vis_init): the mask is (frame at or after the query frame, in the pass's direction) minus what
+//                     earlier windows already covered (:505-507, :695), window slots past the clip's end repeat the last frame
+//                     (:598-604); vis_init is the previous window's LOGIT for carried tracks (:653-655), 10 for new ones (:511)
 //   ffeats [n][S][C]: the track's initial feature repeated over the window (:645)
+// Slot s is clip frame frame0 + frame_step * s, frame_step = +1 (forward pass) or -1 (the time-reversed pass of backward tracking,
+// tracks sorted by descending query frame).  Written with w = frame0 forwards and wr = T - 1 - frame0 (the window start in
+// reversed time) backwards, the three direction-dependent lines are
+//   S_local = min(S, step > 0 ? T - frame0 : frame0 + 1)   forwards min(S, T - w),         reversed min(S, T - wr)
+//   f = frame0 + step * min(s, S_local - 1)                forwards w + min(s, S_local-1), reversed frame0 - min(s, S_local-1) >= 0
+//   on = step * (f - qt) >= 0                              forwards f >= qt,               reversed f <= qt
+//        && !(carried && step * (f - frame0) < S / 2)      forwards f < w + half,          reversed frame0 - f < half: f > frame0 - half
+// all in integers.  The carried row is carry_src[tr] (-1: a track that enters here) or, without a map, tr itself for tr < p0.
 __global__ void window_prepare_kernel(const float* __restrict__ qxyz, const int* __restrict__ qt, const float* __restrict__ feat_init,
                                       const float* __restrict__ prev_coords, const float* __restrict__ prev_vis,
-                                      const int* __restrict__ carry_src, int n, int p0, int S, int C, int w, int T,
+                                      const int* __restrict__ carry_src, int n, int p0, int S, int C, int frame0, int frame_step, int T,
                                       float* __restrict__ coords, float* __restrict__ mask_vis, float* __restrict__ ffeats) {
   const long long total = (long long)n * S * (C / 4);
   const int half = S / 2;
+  const int room = frame_step > 0 ? T - frame0 : frame0 + 1;  // frames from slot 0 to the clip's end, in the pass's direction
+  const int S_local = room < S ? room : S;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int cq = (int)(i % (C / 4));
     const long long row = i / (C / 4);  // tr * S + s
@@ -82,7 +92,6 @@ __global__ void window_prepare_kernel(const float* __restrict__ qxyz, const int*
     *reinterpret_cast<f32x4*>(ffeats + row * C + cq * 4) = *reinterpret_cast<const f32x4*>(feat_init + (long long)tr * C + cq * 4);
     if (cq == 0) {
       const int sp = s < half ? half + s : S - 1;  // slot of the previous window this one continues from
-      // (carry_src: the row of the previous window's outputs this track continues from, -1 for a new track)
       const int src = carry_src ? carry_src[tr] : (tr < p0 ? tr : -1);
       float vis = 10.0f;
       if (src >= 0) {
@@ -93,9 +102,8 @@ __global__ void window_prepare_kernel(const float* __restrict__ qxyz, const int*
 #pragma unroll
         for (int a = 0; a < 3; ++a) coords[row * 3 + a] = qxyz[(long long)tr * 3 + a];
       }
-      const int S_local = T - w < S ? T - w : S;
-      const int f = w + (s < S_local ? s : S_local - 1);
-      const bool on = f >= qt[tr] && !(src >= 0 && f < w + half);
+      const int f = frame0 + frame_step * (s < S_local ? s : S_local - 1);
+      const bool on = frame_step * (f - qt[tr]) >= 0 && !(src >= 0 && frame_step * (f - frame0) < half);
       mask_vis[row * 2] = on ? 1.0f : 0.0f;
       mask_vis[row * 2 + 1] = vis;
     }
@@ -103,96 +111,22 @@ __global__ void window_prepare_kernel(const float* __restrict__ qxyz, const int*
 }
 
 // Results of one window into the clip-level outputs, in the caller's (unsorted) query order (mvtracker.py:692-693, 710-711):
-// traj [T][N][3], vis_logit / vis_prob [T][N]; order[tr] = position of sorted track tr in the caller's query list.
+// traj [f1-f0][N][3], vis_logit / vis_prob [f1-f0][N] hold frames [f0, f1) of the clip; order[tr] = position of sorted track tr in
+// the caller's query list.  Slot s of the ns slots from s0 on (the host's trim to the slots whose frame lies in [f0, f1)) is frame
+// f = frame0 + frame_step * s and goes to row f - f0, unless `before` is given and f >= before[tr] (the reversed pass of backward
+// tracking writes only frames before each row's query frame: the frames from it on are the forward pass's, so this predicate is the
+// merge of the two passes).
 __global__ void window_store_kernel(const float* __restrict__ coords, const float* __restrict__ vis, const long long* __restrict__ order,
-                                    int n, int S, int w, int T, int N, float* __restrict__ traj, float* __restrict__ vis_logit,
-                                    float* __restrict__ vis_prob) {
-  const int S_local = T - w < S ? T - w : S;
-  const long long total = (long long)n * S_local;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int s = (int)(i % S_local);
-    const int tr = (int)(i / S_local);
-    const long long src = (long long)tr * S + s;
-    const long long dst = (long long)(w + s) * N + order[tr];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) traj[dst * 3 + a] = coords[src * 3 + a];
-    const float lg = vis[src];
-    vis_logit[dst] = lg;
-    vis_prob[dst] = 1.0f / (1.0f + expf(-lg));
-  }
-}
-
-// window_store_kernel for streaming: the output is a chunk of the clip, frames [f0, f1), and only the window's slots inside it are
-// written -- chunk [f - f0][N][.] = what window_store_kernel writes to frame f of the whole-clip tensors.
-__global__ void window_store_chunk_kernel(const float* __restrict__ coords, const float* __restrict__ vis,
-                                          const long long* __restrict__ order, int n, int S, int w, int s0, int ns, int f0, int N,
-                                          float* __restrict__ traj, float* __restrict__ vis_logit, float* __restrict__ vis_prob) {
+                                    const int* __restrict__ before, int n, int S, int s0, int ns, int frame0, int frame_step, int f0,
+                                    int N, float* __restrict__ traj, float* __restrict__ vis_logit, float* __restrict__ vis_prob) {
   const long long total = (long long)n * ns;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int s = s0 + (int)(i % ns);
     const int tr = (int)(i / ns);
+    const int f = frame0 + frame_step * s;
+    if (before && f >= before[tr]) continue;
     const long long src = (long long)tr * S + s;
-    const long long dst = (long long)(w + s - f0) * N + order[tr];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) traj[dst * 3 + a] = coords[src * 3 + a];
-    const float lg = vis[src];
-    vis_logit[dst] = lg;
-    vis_prob[dst] = 1.0f / (1.0f + expf(-lg));
-  }
-}
-
-// The two kernels above for the time-reversed pass of backward tracking: the window starts at wr in REVERSED time (frame T-1-wr of
-// the clip) and slot s reads frame max(T-1-wr - s, 0), the tracks are sorted by descending query frame and qt holds the query frames
-// themselves.  This is window_prepare_kernel on the flipped clip written in the clip's own frame numbers: the mask is
-// (frame <= query frame) minus what earlier reversed windows covered, slots past the clip's start repeat frame 0.
-__global__ void window_prepare_reversed_kernel(const float* __restrict__ qxyz, const int* __restrict__ qt,
-                                               const float* __restrict__ feat_init, const float* __restrict__ prev_coords,
-                                               const float* __restrict__ prev_vis, int n, int p0, int S, int C, int wr, int T,
-                                               float* __restrict__ coords, float* __restrict__ mask_vis, float* __restrict__ ffeats) {
-  const long long total = (long long)n * S * (C / 4);
-  const int half = S / 2;
-  const int f0 = T - 1 - wr;  // the clip frame of slot 0
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int cq = (int)(i % (C / 4));
-    const long long row = i / (C / 4);  // tr * S + s
-    const int s = (int)(row % S);
-    const int tr = (int)(row / S);
-    *reinterpret_cast<f32x4*>(ffeats + row * C + cq * 4) = *reinterpret_cast<const f32x4*>(feat_init + (long long)tr * C + cq * 4);
-    if (cq == 0) {
-      const int sp = s < half ? half + s : S - 1;
-      const bool carried = tr < p0;
-      float vis = 10.0f;
-      if (carried) {
-        vis = prev_vis[(long long)tr * S + sp];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) coords[row * 3 + a] = prev_coords[((long long)tr * S + sp) * 3 + a];
-      } else {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) coords[row * 3 + a] = qxyz[(long long)tr * 3 + a];
-      }
-      const int S_local = T - wr < S ? T - wr : S;
-      const int f = f0 - (s < S_local ? s : S_local - 1);
-      const bool on = f <= qt[tr] && !(carried && f > f0 - half);
-      mask_vis[row * 2] = on ? 1.0f : 0.0f;
-      mask_vis[row * 2 + 1] = vis;
-    }
-  }
-}
-
-// Results of one reversed window: slot s is frame T-1-wr - s, and a row is written ONLY where that frame lies before the track's
-// query frame -- the frames from the query frame on belong to the forward pass, so the merge of the two passes is this predicate.
-__global__ void window_store_reversed_kernel(const float* __restrict__ coords, const float* __restrict__ vis,
-                                             const long long* __restrict__ order, const int* __restrict__ qt, int n, int S, int wr, int T,
-                                             int N, float* __restrict__ traj, float* __restrict__ vis_logit, float* __restrict__ vis_prob) {
-  const int S_local = T - wr < S ? T - wr : S;
-  const long long total = (long long)n * S_local;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int s = (int)(i % S_local);
-    const int tr = (int)(i / S_local);
-    const int f = T - 1 - wr - s;
-    if (f >= qt[tr]) continue;
-    const long long src = (long long)tr * S + s;
-    const long long dst = (long long)f * N + order[tr];
+    const long long dst = (long long)(f - f0) * N + order[tr];
 #pragma unroll
     for (int a = 0; a < 3; ++a) traj[dst * 3 + a] = coords[src * 3 + a];
     const float lg = vis[src];
@@ -326,62 +260,31 @@ extern "C" int mvt_token_assemble(const float* coords, const float* fcorr, int F
 }
 
 extern "C" int mvt_window_prepare(const float* qxyz, const int* qt, const float* feat_init, const float* prev_coords,
-                                  const float* prev_vis, int n, int p0, int S, int C, int w, int T, float* coords, float* mask_vis,
-                                  float* ffeats, void* stream) {
+                                  const float* prev_vis, const int* carry_src, int n, int p0, int S, int C, int frame0, int frame_step,
+                                  int T, float* coords, float* mask_vis, float* ffeats, void* stream) {
   MVT_REQUIRE(qxyz && qt && feat_init && coords && mask_vis && ffeats && n > 0 && p0 >= 0 && p0 <= n && S >= 2 && C > 0 && C % 4 == 0);
-  MVT_REQUIRE(w >= 0 && w < T && (p0 == 0 || (prev_coords && prev_vis)));
+  MVT_REQUIRE(frame0 >= 0 && frame0 < T && (frame_step == 1 || frame_step == -1));
+  // a map replaces the carried prefix.  (With one, prev_coords / prev_vis may be NULL only if no track is carried: a device map
+  // cannot be checked here, the kernel would fault)
+  MVT_REQUIRE(carry_src ? p0 == 0 : (p0 == 0 || (prev_coords && prev_vis)));
   hipLaunchKernelGGL(window_prepare_kernel, dim3(grid_for((long long)n * S * (C / 4))), dim3(256), 0, mvt_stream(stream), qxyz, qt,
-                     feat_init, prev_coords, prev_vis, nullptr, n, p0, S, C, w, T, coords, mask_vis, ffeats);
+                     feat_init, prev_coords, prev_vis, carry_src, n, p0, S, C, frame0, frame_step, T, coords, mask_vis, ffeats);
   return mvt_launch_status();
 }
 
-extern "C" int mvt_window_prepare_mapped(const float* qxyz, const int* qt, const float* feat_init, const float* prev_coords,
-                                         const float* prev_vis, const int* carry_src, int n, int S, int C, int w, int T, float* coords,
-                                         float* mask_vis, float* ffeats, void* stream) {
-  MVT_REQUIRE(qxyz && qt && feat_init && carry_src && coords && mask_vis && ffeats && n > 0 && S >= 2 && C > 0 && C % 4 == 0);
-  MVT_REQUIRE(w >= 0 && w < T);
-  // (prev_coords / prev_vis may be NULL only if no track is carried: a device map cannot be checked here, the kernel would fault)
-  hipLaunchKernelGGL(window_prepare_kernel, dim3(grid_for((long long)n * S * (C / 4))), dim3(256), 0, mvt_stream(stream), qxyz, qt,
-                     feat_init, prev_coords, prev_vis, carry_src, n, 0, S, C, w, T, coords, mask_vis, ffeats);
-  return mvt_launch_status();
-}
-
-extern "C" int mvt_window_store(const float* coords, const float* vis, const long long* order, int n, int S, int w, int T, int N,
-                                float* traj, float* vis_logit, float* vis_prob, void* stream) {
-  MVT_REQUIRE(coords && vis && order && traj && vis_logit && vis_prob && n > 0 && n <= N && S > 0 && w >= 0 && w < T);
-  hipLaunchKernelGGL(window_store_kernel, dim3(grid_for((long long)n * S)), dim3(256), 0, mvt_stream(stream), coords, vis, order, n, S, w, T,
-                     N, traj, vis_logit, vis_prob);
-  return mvt_launch_status();
-}
-
-extern "C" int mvt_window_store_chunk(const float* coords, const float* vis, const long long* order, int n, int S, int w, int T, int f0,
-                                      int f1, int N, float* traj, float* vis_logit, float* vis_prob, void* stream) {
-  MVT_REQUIRE(coords && vis && order && traj && vis_logit && vis_prob && n > 0 && n <= N && S > 0 && w >= 0 && w < T);
-  MVT_REQUIRE(f0 >= 0 && f1 > f0 && f1 <= T);
-  // the window's slots inside the chunk: s0 .. s1 - 1 (none: nothing to write); f1 <= T keeps them within the clip
-  const int s0 = f0 > w ? f0 - w : 0;
-  const int s1 = f1 - w < S ? f1 - w : S;
+extern "C" int mvt_window_store(const float* coords, const float* vis, const long long* order, const int* before, int n, int S,
+                                int frame0, int frame_step, int T, int f0, int f1, int N, float* traj, float* vis_logit, float* vis_prob,
+                                void* stream) {
+  MVT_REQUIRE(coords && vis && order && traj && vis_logit && vis_prob && n > 0 && n <= N && S > 0);
+  MVT_REQUIRE(frame0 >= 0 && frame0 < T && (frame_step == 1 || frame_step == -1) && f0 >= 0 && f1 > f0 && f1 <= T);
+  // the window's slots inside [f0, f1): s0 .. s1 - 1 (none: nothing to write); f1 <= T and f0 >= 0 keep them within the clip
+  const int lo = frame_step > 0 ? f0 - frame0 : frame0 - f1 + 1;
+  const int hi = frame_step > 0 ? f1 - frame0 : frame0 - f0 + 1;
+  const int s0 = lo > 0 ? lo : 0;
+  const int s1 = hi < S ? hi : S;
   if (s1 <= s0) return MVT_OK;
-  hipLaunchKernelGGL(window_store_chunk_kernel, dim3(grid_for((long long)n * (s1 - s0))), dim3(256), 0, mvt_stream(stream), coords, vis,
-                     order, n, S, w, s0, s1 - s0, f0, N, traj, vis_logit, vis_prob);
-  return mvt_launch_status();
-}
-
-extern "C" int mvt_window_prepare_reversed(const float* qxyz, const int* qt, const float* feat_init, const float* prev_coords,
-                                           const float* prev_vis, int n, int p0, int S, int C, int wr, int T, float* coords,
-                                           float* mask_vis, float* ffeats, void* stream) {
-  MVT_REQUIRE(qxyz && qt && feat_init && coords && mask_vis && ffeats && n > 0 && p0 >= 0 && p0 <= n && S >= 2 && C > 0 && C % 4 == 0);
-  MVT_REQUIRE(wr >= 0 && wr < T && (p0 == 0 || (prev_coords && prev_vis)));
-  hipLaunchKernelGGL(window_prepare_reversed_kernel, dim3(grid_for((long long)n * S * (C / 4))), dim3(256), 0, mvt_stream(stream), qxyz,
-                     qt, feat_init, prev_coords, prev_vis, n, p0, S, C, wr, T, coords, mask_vis, ffeats);
-  return mvt_launch_status();
-}
-
-extern "C" int mvt_window_store_reversed(const float* coords, const float* vis, const long long* order, const int* qt, int n, int S,
-                                         int wr, int T, int N, float* traj, float* vis_logit, float* vis_prob, void* stream) {
-  MVT_REQUIRE(coords && vis && order && qt && traj && vis_logit && vis_prob && n > 0 && n <= N && S > 0 && wr >= 0 && wr < T);
-  hipLaunchKernelGGL(window_store_reversed_kernel, dim3(grid_for((long long)n * S)), dim3(256), 0, mvt_stream(stream), coords, vis, order,
-                     qt, n, S, wr, T, N, traj, vis_logit, vis_prob);
+  hipLaunchKernelGGL(window_store_kernel, dim3(grid_for((long long)n * (s1 - s0))), dim3(256), 0, mvt_stream(stream), coords, vis, order,
+                     before, n, S, s0, s1 - s0, frame0, frame_step, f0, N, traj, vis_logit, vis_prob);
   return mvt_launch_status();
 }
 

@@ -29,7 +29,8 @@ def grouped_layout(qts: Sequence[Sequence[int]], S: int, T: int) -> dict:
       active      (G,) sorted rows [base[g], base[g] + active[g]) ever enter a window (the rest keep zero outputs)
       windows     in execution order: dict(w, groups (member group ids), p0 / p1 (per member: carried / active prefix),
                   off (row offsets of the members, len + 1), rows (sorted row of every window row), carry (row of the previous
-                  window of the same members this row continues from, -1 for a track that enters here), out (caller row of
+                  window of the same members this row continues from, -1 for a track that enters here: window_prepare's
+                  carry_src), out (caller row of
                   every window row: the un-sort map of window_store), new_tracks (bool: the window follows no earlier one))
     """
     G = len(qts)

@@ -67,7 +67,6 @@ SIGNATURES = {
     "mvt_corr_gather_dot": [I, P, P, I, P, P, I, P, P, I, I, I, I, I, I, I, I, I, P, I, I, P],
     "mvt_corr_gather_dot_opts": [I, P, P, I, P, P, I, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, I, I, P],
     "mvt_knn1_gather": [P, I, LL, I, P, I, I, I, I, I, I, I, P, P, P],
-    "mvt_window_store_chunk": [P, P, P, I, I, I, I, I, I, I, P, P, P, P],
     "mvt_window_corr": [P, P, P, P, I, I, I, I, I, I, I, I, I, P],
     "mvt_window_corr_levels": [I, P, I, P, P, P, P, P, I, I, I, I, I, I, P],
     "mvt_pos_embed": [P, I, I, I, I, P, P, P],
@@ -81,15 +80,12 @@ SIGNATURES = {
     "mvt_attention_segmented": [P, I, LL, LL, P, P, I, LL, LL, P, I, I, I, I, I, P, P, P, P, P],
     "mvt_attention_bf16_segmented": [P, I, LL, LL, P, P, I, LL, LL, P, I, I, I, I, I, I, P, P, P, P, P, LL, P],
     "mvt_broadcast_rows_repeat": [P, P, I, I, I, I, I, P],
-    "mvt_window_prepare_mapped": [P, P, P, P, P, P, I, I, I, I, I, P, P, P, P],
     "mvt_updateformer_grouped_workspace_bytes": [I, I, I],
     "mvt_updateformer_forward_grouped": [P, P, I, I, I, P, P, I, P, P, P, P, LL, P],
     "mvt_updateformer_forward_tokens_grouped": [P, P, I, I, P, P, I, P, P, P, P, LL, P],
     "mvt_attn_block_fused_bf16": [P, I, P, P, P, P, P, P, P, I, P, I, LL, I, P, P],
-    "mvt_window_prepare": [P, P, P, P, P, I, I, I, I, I, I, P, P, P, P],
-    "mvt_window_store": [P, P, P, I, I, I, I, I, P, P, P, P],
-    "mvt_window_prepare_reversed": [P, P, P, P, P, I, I, I, I, I, I, P, P, P, P],
-    "mvt_window_store_reversed": [P, P, P, P, I, I, I, I, I, P, P, P, P],
+    "mvt_window_prepare": [P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P],
+    "mvt_window_store": [P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P],
     "mvt_track_metrics": [P, P, P, P, P, I, I, I, P, I, F, P, I, P],
     "mvt_encoder_workspace_bytes": [I, I, I, I],
     "mvt_encoder_forward": [P, P, I, I, I, P, I, I, P, LL, P],
@@ -611,43 +607,25 @@ def broadcast_rows_repeat(v, x, ld, n, S, Cc, reps):
     _call("mvt_broadcast_rows_repeat", _ptr(v), _ptr(x), ld, n, S, Cc, reps, _stream())
 
 
-def window_prepare_mapped(qxyz, qt, feat_init, prev_coords, prev_vis, carry_src, n, S, Cc, w, T, coords, mask_vis, ffeats):
-    assert qt.dtype == torch.int32 and carry_src.dtype == torch.int32 and carry_src.numel() >= n
-    _call("mvt_window_prepare_mapped", _ptr(_f32c(qxyz)), _ptr(qt), _ptr(_f32c(feat_init)), _ptr(prev_coords), _ptr(prev_vis),
-          _ptr(carry_src), n, S, Cc, w, T, _ptr(coords), _ptr(mask_vis), _ptr(ffeats), _stream())
-
-
-def window_prepare(qxyz, qt, feat_init, prev_coords, prev_vis, n, p0, S, Cc, w, T, coords, mask_vis, ffeats):
+def window_prepare(qxyz, qt, feat_init, prev_coords, prev_vis, n, p0, S, Cc, frame0, T, coords, mask_vis, ffeats, frame_step=1, carry_src=None):
+    """Track state of the window whose slot s is clip frame frame0 + frame_step * s (-1: the time-reversed pass; ``qt`` holds the query
+    frames themselves either way).  The first ``p0`` rows continue from their own rows of ``prev_*``, or, with ``carry_src`` (int32,
+    then p0 = 0), row i from row carry_src[i] >= 0, -1 for a track that enters here."""
     assert qt.dtype == torch.int32
-    _call("mvt_window_prepare", _ptr(_f32c(qxyz)), _ptr(qt), _ptr(_f32c(feat_init)), _ptr(prev_coords), _ptr(prev_vis), n, p0, S, Cc, w, T,
-          _ptr(coords), _ptr(mask_vis), _ptr(ffeats), _stream())
+    assert carry_src is None or (carry_src.dtype == torch.int32 and carry_src.numel() >= n)
+    _call("mvt_window_prepare", _ptr(_f32c(qxyz)), _ptr(qt), _ptr(_f32c(feat_init)), _ptr(prev_coords), _ptr(prev_vis), _ptr(carry_src),
+          n, p0, S, Cc, frame0, frame_step, T, _ptr(coords), _ptr(mask_vis), _ptr(ffeats), _stream())
 
 
-def window_store(coords, vis, order, n, S, w, T, N, traj, vis_logit, vis_prob):
-    assert order.dtype == torch.int64
-    _call("mvt_window_store", _ptr(coords), _ptr(vis), _ptr(order), n, S, w, T, N, _ptr(traj), _ptr(vis_logit), _ptr(vis_prob), _stream())
-
-
-def window_store_chunk(coords, vis, order, n, S, w, T, f0, f1, N, traj, vis_logit, vis_prob):
-    """``window_store`` into a chunk of the clip: traj (f1-f0, N, 3) / vis_* (f1-f0, N) hold frames [f0, f1) of a clip of T frames (as
-    far as known, f1 <= T); the window's slots outside the chunk are dropped."""
+def window_store(coords, vis, order, n, S, frame0, T, N, traj, vis_logit, vis_prob, frame_step=1, before=None, frames=None):
+    """The window's slots into traj (f1-f0, N, 3) / vis_* (f1-f0, N), which hold frames ``frames`` = (f0, f1) of a clip of T frames (as
+    far as known, f1 <= T; None: the whole clip).  Slots outside the range are dropped, and with ``before`` (int32 per row: the
+    reversed pass's query frames) a row's slots at or past its bound."""
+    f0, f1 = (0, T) if frames is None else frames
     assert order.dtype == torch.int64 and traj.shape[0] == f1 - f0 and traj.shape[1] == N
-    _call("mvt_window_store_chunk", _ptr(coords), _ptr(vis), _ptr(order), n, S, w, T, f0, f1, N, _ptr(traj), _ptr(vis_logit), _ptr(vis_prob),
-          _stream())
-
-
-def window_prepare_reversed(qxyz, qt, feat_init, prev_coords, prev_vis, n, p0, S, Cc, wr, T, coords, mask_vis, ffeats):
-    """``window_prepare`` of the time-reversed pass: ``wr`` is the window start in reversed time, ``qt`` the query frames themselves."""
-    assert qt.dtype == torch.int32
-    _call("mvt_window_prepare_reversed", _ptr(_f32c(qxyz)), _ptr(qt), _ptr(_f32c(feat_init)), _ptr(prev_coords), _ptr(prev_vis), n, p0, S,
-          Cc, wr, T, _ptr(coords), _ptr(mask_vis), _ptr(ffeats), _stream())
-
-
-def window_store_reversed(coords, vis, order, qt, n, S, wr, T, N, traj, vis_logit, vis_prob):
-    """``window_store`` of the time-reversed pass: slot s goes to frame T-1-wr-s, only where that frame is before the row's query frame."""
-    assert order.dtype == torch.int64 and qt.dtype == torch.int32
-    _call("mvt_window_store_reversed", _ptr(coords), _ptr(vis), _ptr(order), _ptr(qt), n, S, wr, T, N, _ptr(traj), _ptr(vis_logit),
-          _ptr(vis_prob), _stream())
+    assert before is None or before.dtype == torch.int32
+    _call("mvt_window_store", _ptr(coords), _ptr(vis), _ptr(order), _ptr(before), n, S, frame0, frame_step, T, f0, f1, N, _ptr(traj),
+          _ptr(vis_logit), _ptr(vis_prob), _stream())
 
 
 def broadcast_rows(v, x, ld, n, S, Cc):

@@ -194,12 +194,11 @@ class StreamSession:
         from . import hip
         c = self.carry
         if c and b > a:
-            hip.window_store_chunk(c["coords"], c["vis"], self.order_d, c["p0"], self.model.S, c["w"], self.sched.received, a, b, out["traj"].shape[1],
-                                   out["traj"], out["vis_logit"], out["vis_prob"])
+            hip.window_store(c["coords"], c["vis"], self.order_d, c["p0"], self.model.S, c["w"], self.sched.received, out["traj"].shape[1],
+                             out["traj"], out["vis_logit"], out["vis_prob"], frames=(a, b))
 
     def _step(self, ops, frames, clip=None):
         import torch
-        from . import hip
         m = self.model
         a, b = frames
         N = self.queries.shape[0]
@@ -213,8 +212,8 @@ class StreamSession:
                 continue
             _, w, p1, hi = op
             self.store["ring"] = (self.sched.base, self.sched.R, w, hi)
-            m._run_windows(self.store, [(w, p1)], [w], 1, hip.window_prepare, (self.qxyz, self.qt_sd, self.feat), None, (), out, self.iters,
-                           None, enter_frames=self.qt_s, carry=self.carry, T=hi + 1)
+            m._run_windows(self.store, [(w, p1)], [w], 1, (self.qxyz, self.qt_sd, self.feat), self.order_d, out, self.iters, None,
+                           store_slots=False, enter_frames=self.qt_s, carry=self.carry, T=hi + 1)
             self._store_carried(out, a, b)
         return {"frames": (a, b), "traj_e": out["traj"][None], "vis_e": out["vis_prob"][None], "vis_logits": out["vis_logit"][None]}
 

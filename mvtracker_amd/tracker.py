@@ -1320,18 +1320,19 @@ class MVTracker(nn.Module):
 
         return store, pending, pending_back, start_side_encoder
 
-    def _run_windows(self, store, windows, frame0s, frame_step, prepare, rows, store_out, unsort, out, iters, trace,
+    def _run_windows(self, store, windows, frame0s, frame_step, rows, order, out, iters, trace, before=None, store_slots=True,
                      enter_frames=None, pre=None, pending=(), after_first_corr=None, carry=None, T=None):
         """One pass of the reference's window loop (mvtracker.py:537-695) over ``windows`` = [(start, active prefix), ...], slot s
-        of window i reading store frame clamp(frame0s[i] + s * frame_step, 0, T-1).  ``prepare`` / ``store_out``: the library's
-        window-state and result-store entry of the pass, ``rows`` = (query xyz, query frames, initial feature rows) in the pass's
-        sorted order on the device, ``unsort`` = what ``store_out`` takes to put window rows back into the caller's.  ``out``: the
-        call's result tensors.  Forward pass only: ``enter_frames`` (host query frames: the feature rows of the tracks that enter
-        a window are initialised there), ``pre`` (``_presearch``), ``pending`` ((first frame, event) of the feature blocks in
-        flight on the second stream, in frame order), ``after_first_corr`` (``_refine``, first window).  Returns the windows run.
+        of window i reading store frame clamp(frame0s[i] + s * frame_step, 0, T-1).  The pass supplies data only: ``rows`` = (query
+        xyz, query frames, initial feature rows) in the pass's sorted order on the device, ``order`` = the position of each sorted
+        row in the caller's query list (the un-sort of the result store), ``before`` = an optional per-row frame bound of the result
+        store (the reversed pass's query frames: it writes only the frames before them).  ``out``: the call's result tensors.
+        Forward pass only: ``enter_frames`` (host query frames: the feature rows of the tracks that enter a window are initialised
+        there), ``pre`` (``_presearch``), ``pending`` ((first frame, event) of the feature blocks in flight on the second stream, in
+        frame order), ``after_first_corr`` (``_refine``, first window).  Returns the windows run.
         Streaming (``mvtracker_amd.streaming``) runs the loop a few windows at a time: ``carry`` is a dict that holds what one window
         hands to the next (p0, coords, vis, prev_idx, w) between calls, ``T`` the clip length as far as it is known (``out`` then only
-        needs the NaN flag), and with ``store_out`` None the session stores the carried window's slots itself."""
+        needs the NaN flag), and with ``store_slots`` False the session stores the carried window's slots itself."""
         S, C = self.S, self.latent_dim
         qxyz, qt_d, feat = rows
         dev = qxyz.device
@@ -1362,7 +1363,7 @@ class MVTracker(nn.Module):
             wc = torch.empty(p1, S, 3, device=dev)
             wf = torch.empty(p1, S, C, device=dev)
             wm = torch.empty(p1, S, 2, device=dev)
-            prepare(qxyz, qt_d, feat, coords, vis, p1, p0, S, C, w, T, wc, wm, wf)
+            hip.window_prepare(qxyz, qt_d, feat, coords, vis, p1, p0, S, C, f0, T, wc, wm, wf, frame_step=frame_step)
             wtrace = None
             if trace is not None:
                 wtrace = {} if frame_step > 0 else dict(reversed_window=w)
@@ -1373,8 +1374,9 @@ class MVTracker(nn.Module):
             after_first_corr = None
             coords = preds[-1]
             # :692-693, un-sorted (:710-711); the reversed pass writes only frames before each row's query frame
-            if store_out is not None:
-                store_out(coords, vis, *unsort, p1, S, w, T, out["traj"].shape[1], out["traj"], out["vis_logit"], out["vis_prob"])
+            if store_slots:
+                hip.window_store(coords, vis, order, p1, S, f0, T, out["traj"].shape[1], out["traj"], out["vis_logit"], out["vis_prob"],
+                                 frame_step=frame_step, before=before)
             done.append((w, p1))
             p0 = p1
             if carry is not None:
@@ -1487,9 +1489,8 @@ class MVTracker(nn.Module):
             start_side_encoder = None
 
         # ---- forward pass
-        windows = self._run_windows(store, fwd, [w for w, _ in fwd], 1, hip.window_prepare, (qxyz, qt_sd, out["feat_init"]),
-                                    hip.window_store, (order_d,), out, iters, trace, enter_frames=qt_s, pre=pre, pending=pending,
-                                    after_first_corr=start_side_encoder)
+        windows = self._run_windows(store, fwd, [w for w, _ in fwd], 1, (qxyz, qt_sd, out["feat_init"]), order_d, out, iters, trace,
+                                    enter_frames=qt_s, pre=pre, pending=pending, after_first_corr=start_side_encoder)
         for _, ev in pending:  # frames no window consumed: still join the side stream before the inputs are released
             torch.cuda.current_stream(dev).wait_event(ev)  # hand-over H7: the caller's inputs (read by the second stream) are released
 
@@ -1508,8 +1509,8 @@ class MVTracker(nn.Module):
             self._feat_init(store, back["sorted_qt"], qxyz_b, 0, back["active"], feat_b)
             if len(fix_rows):
                 out["feat_init"].index_copy_(0, small_d[4], feat_b.index_select(0, small_d[5]))
-            windows_b = self._run_windows(store, back["windows"], back["frame0"], -1, hip.window_prepare_reversed, (qxyz_b, qt_bd, feat_b),
-                                          hip.window_store_reversed, (order_bd, qt_bd), out, iters, trace)
+            windows_b = self._run_windows(store, back["windows"], back["frame0"], -1, (qxyz_b, qt_bd, feat_b), order_bd, out, iters, trace,
+                                          before=qt_bd)
 
         self.last_windows = windows
         self.last_windows_backward = windows_b
@@ -1584,8 +1585,8 @@ class MVTracker(nn.Module):
             wc = torch.empty(n, S, 3, device=dev)
             wf = torch.empty(n, S, C, device=dev)
             wm = torch.empty(n, S, 2, device=dev)
-            hip.window_prepare_mapped(qxyz[rows_d].contiguous(), qt_sd[rows_d].contiguous(), feat_init[rows_d].contiguous(), coords, vis,
-                                      carry_d.to(torch.int32), n, S, C, wd["w"], T, wc, wm, wf)
+            hip.window_prepare(qxyz[rows_d].contiguous(), qt_sd[rows_d].contiguous(), feat_init[rows_d].contiguous(), coords, vis, n, 0, S, C,
+                               wd["w"], T, wc, wm, wf, carry_src=carry_d.to(torch.int32))
             wtrace = None
             if trace is not None:
                 wtrace = dict(w=wd["w"], groups=list(wd["groups"]), group_offsets=wd["off"].tolist(), carried=wd["p0"].tolist())

@@ -516,7 +516,21 @@ def window_corr(fmap, targets, coords, out, BS, N, Cc, h, w, level, radius, ldo,
         o[row] = v.t().reshape(-1) / math.sqrt(Cc)
 
 
-def window_prepare(qxyz, qt, feat_init, prev_coords, prev_vis, n, p0, S, Cc, w, T, coords, mask_vis, ffeats):
+def window_prepare(qxyz, qt, feat_init, prev_coords, prev_vis, n, p0, S, Cc, frame0, T, coords, mask_vis, ffeats, frame_step=1, carry_src=None):
+    if frame_step < 0:  # the reversed pass: the forward form on flipped time
+        assert frame_step == -1
+        return window_prepare(qxyz, T - 1 - qt, feat_init, prev_coords, prev_vis, n, p0, S, Cc, T - 1 - frame0, T, coords, mask_vis, ffeats,
+                              carry_src=carry_src)
+    if carry_src is not None:  # a carry map: every row a window of its own, carried from the row the map names or new
+        assert p0 == 0
+        q2, t1, f2 = qxyz.reshape(-1, 3), qt.reshape(-1), feat_init.reshape(-1, Cc)
+        c3, m3, f3 = coords.reshape(-1, S, 3), mask_vis.reshape(-1, S, 2), ffeats.reshape(-1, S, Cc)
+        for i, src in enumerate(carry_src.reshape(-1)[:n].tolist()):
+            pc = prev_coords.reshape(-1, S, 3)[src:src + 1].contiguous() if src >= 0 else None
+            pv = prev_vis.reshape(-1, S)[src:src + 1].contiguous() if src >= 0 else None
+            window_prepare(q2[i:i + 1], t1[i:i + 1], f2[i:i + 1], pc, pv, 1, int(src >= 0), S, Cc, frame0, T, c3[i:i + 1], m3[i:i + 1], f3[i:i + 1])
+        return
+    w = frame0
     half = S // 2
     ffeats.reshape(n, S, Cc).copy_(feat_init.reshape(-1, Cc)[:n, None, :].expand(n, S, Cc))
     c = coords.reshape(n, S, 3)
@@ -535,7 +549,29 @@ def window_prepare(qxyz, qt, feat_init, prev_coords, prev_vis, n, p0, S, Cc, w, 
     mv[..., 1] = vis
 
 
-def window_store(coords, vis, order, n, S, w, T, N, traj, vis_logit, vis_prob):
+def window_store(coords, vis, order, n, S, frame0, T, N, traj, vis_logit, vis_prob, frame_step=1, before=None, frames=None):
+    if frames is not None:  # a chunk of the clip: the whole-clip store into a padded temporary, then cut
+        f0, f1 = frames
+        assert 0 <= f0 < f1 <= T and 0 <= frame0 < T
+        tmp = [torch.zeros(T, N, 3), torch.zeros(T, N), torch.zeros(T, N)]
+        for t, c in zip(tmp, (traj, vis_logit, vis_prob)):
+            t[f0:f1] = c.reshape(t[f0:f1].shape)
+        window_store(coords, vis, order, n, S, frame0, T, N, *tmp, frame_step=frame_step, before=before)
+        for t, c in zip(tmp, (traj, vis_logit, vis_prob)):
+            c.reshape(t[f0:f1].shape).copy_(t[f0:f1])
+        return
+    if frame_step < 0 or before is not None:  # slot by slot, row by row
+        assert frame_step in (1, -1)
+        c, v, o = coords.reshape(n, S, 3), vis.reshape(n, S), order.reshape(-1)
+        for i in range(n):
+            for s in range(S):
+                f = frame0 + frame_step * s
+                if 0 <= f < T and (before is None or f < int(before[i])):
+                    traj.reshape(T, N, 3)[f, o[i]] = c[i, s]
+                    vis_logit.reshape(T, N)[f, o[i]] = v[i, s]
+                    vis_prob.reshape(T, N)[f, o[i]] = torch.sigmoid(v[i, s])
+        return
+    w = frame0
     s_local = min(S, T - w)
     o = order.reshape(-1)[:n]
     traj.reshape(T, N, 3)[w:w + s_local, o] = coords.reshape(n, S, 3)[:, :s_local].permute(1, 0, 2)

@@ -73,17 +73,6 @@ def knn1_gather_ring(fvec, Pn, Cc, keys, n, nseg, frame, ring, feat_out, idx_out
     hip_mock.knn1_gather(_linear(fvec, ring, Pn * Cc), Pn, Cc, keys, n, nseg, f0, feat_out, idx_out)
 
 
-def window_store_chunk(coords, vis, order, n, S, w, T, f0, f1, N, traj, vis_logit, vis_prob):
-    """``window_store`` on the clip of T frames, of which the chunk holds frames [f0, f1)."""
-    assert 0 <= f0 < f1 <= T and w < T
-    tmp = [torch.zeros(T, N, 3), torch.zeros(T, N), torch.zeros(T, N)]
-    for t, c in zip(tmp, (traj, vis_logit, vis_prob)):
-        t[f0:f1] = c.reshape(t[f0:f1].shape)
-    hip_mock.window_store(coords, vis, order, n, S, w, T, N, *tmp)
-    for t, c in zip(tmp, (traj, vis_logit, vis_prob)):
-        c.reshape(t[f0:f1].shape).copy_(t[f0:f1])
-
-
 def conv2d(x, wt, bias, out, n, H, W, Cin, Cout, KH, KW, stride, pad, ldo, act=0):
     """hip_mock.conv2d image by image.  The library's convolutions do not depend on how many images a call holds; torch's CPU
     convolution blocks by batch size and may differ in the last bit between a frame encoded alone and inside a larger call, which
@@ -103,5 +92,5 @@ def install(monkeypatch):
     hip_mock.install(monkeypatch)
     me = sys.modules[__name__]
     for name in ("knn_scan_ring knn_search_ring knn_scan_levels_ring knn_search_levels_ring corr_gather_dot_ring corr_gather_dot_opts_ring "
-                 "knn1_gather_ring window_store_chunk conv2d").split():
+                 "knn1_gather_ring conv2d").split():
         monkeypatch.setattr(hip, name, getattr(me, name))

@@ -74,7 +74,7 @@ def test_exports_and_constants(tmp_path):
     assert RegionCluster is cluster.RegionCluster and RegionReport is cluster.RegionReport
     assert {"cluster", "RegionCluster", "RegionReport", "cluster_points", "select_region_points", "region_masks"} <= set(mvtracker_amd.__all__)
     assert all(n in hip.SIGNATURES for n in ("mvt_cluster_crop", "mvt_cluster_count", "mvt_cluster_link", "mvt_cluster_border", "mvt_cluster_finish"))
-    assert hip.abi_version() == 8
+    assert hip.abi_version() == 9
     r = RegionCluster()
     assert (r.box, r.eps, r.min_samples, r.conf_thresh) == (((-0.08, 0.08), (-0.07, 0.07), (-0.04, 0.18)), 0.03, 12, None)  # the reference's
     assert r.bounds == (-0.08, 0.08, -0.07, 0.07, -0.04, 0.18) and RegionCluster(box=None).bounds is None

@@ -160,8 +160,8 @@ def test_signed_frame_step_equals_flipped_store(model, clips):
 
 
 def test_reversed_window_kernels(model):
-    """mvt_window_prepare_reversed is mvt_window_prepare on flipped times; mvt_window_store_reversed writes frame T-1-wr-s only
-    where it lies before the row's query frame."""
+    """mvt_window_prepare with frame_step = -1 is frame_step = +1 on flipped times; mvt_window_store with frame_step = -1 and the
+    query frames as `before` writes frame T-1-wr-s only where it lies before the row's query frame."""
     T, S, C, n, p0, N = 18, 12, 128, 10, 6, 14
     gen = torch.Generator().manual_seed(2)
     qt = torch.sort(torch.randint(0, T, (n,), generator=gen), descending=True).values.int().to(DEV)
@@ -172,7 +172,7 @@ def test_reversed_window_kernels(model):
         for rev in (True, False):
             wc, wm, wf = torch.empty(n, S, 3, device=DEV), torch.empty(n, S, 2, device=DEV), torch.empty(n, S, C, device=DEV)
             if rev:
-                hip.window_prepare_reversed(qxyz, qt, feat, pc, pv, n, p0, S, C, wr, T, wc, wm, wf)
+                hip.window_prepare(qxyz, qt, feat, pc, pv, n, p0, S, C, T - 1 - wr, T, wc, wm, wf, frame_step=-1)
             else:
                 hip.window_prepare(qxyz, (T - 1 - qt).int(), feat, pc, pv, n, p0, S, C, wr, T, wc, wm, wf)
             outs.append((wc, wm, wf))
@@ -182,7 +182,7 @@ def test_reversed_window_kernels(model):
         coords, vis = torch.randn(n, S, 3, generator=gen).to(DEV), torch.randn(n, S, generator=gen).to(DEV)
         traj = torch.full((T, N, 3), 7.0, device=DEV)
         lg, pr = torch.full((T, N), 7.0, device=DEV), torch.full((T, N), 7.0, device=DEV)
-        hip.window_store_reversed(coords, vis, order, qt, n, S, wr, T, N, traj, lg, pr)
+        hip.window_store(coords, vis, order, n, S, T - 1 - wr, T, N, traj, lg, pr, frame_step=-1, before=qt)
         want_t, want_l = torch.full((T, N, 3), 7.0), torch.full((T, N), 7.0)
         for i in range(n):
             for s in range(min(S, T - wr)):

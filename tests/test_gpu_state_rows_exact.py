@@ -5,7 +5,7 @@ restatement, of the reference-side exactness claims and of the probes.  Every ou
 where a later launch accumulates into it) before the launch, gets a padded leading dimension where the entry has one and a guard
 row behind the last one, and whatever the kernel must not write has to stay poisoned.
 
-A. Window state machine (mvt_window_prepare / _prepare_mapped / _store / _store_chunk / _prepare_reversed / _store_reversed).
+A. Window state machine (mvt_window_prepare / mvt_window_store: frame_step +1 and -1, carry map, `before` bound, frame chunks).
    `reference_loop` is the reference's window loop (mvtracker.py:505-531, 537-540, 645-662, 692-698, 710-711) restated tensor for
    tensor for B = 1: the full (T, N) track mask zeroed with `[: w + S, :p1] = 0`, coords_init_ / vis_init_ updated in place, the
    short last window padded by repeating the last mask slot, `coords[:S_local]` stored, the un-sort by inv_sort_inds.  It knows
@@ -15,8 +15,10 @@ A. Window state machine (mvt_window_prepare / _prepare_mapped / _store / _store_
    between.  Sweep: S in {2, 4, 6, 12}, T in {2, 3, S/2+1, S-1, S, S+1, 3S/2, 3S/2+1, 2S+1, 3S-1}, C = 4, query frames random (at
    each N in {1, 5, 9, 13}) / all 0 / all T-S/2-1 (N cycling); a layout for which the reference runs no window is not generated.
    All comparisons are torch.equal, except vis_prob, which is within 1e-6 of the fp64 sigmoid of the logit (the bar of
-   test_reversed_window_kernels).  On every window the mocks of tests/hip_mock.py and tests/hip_mock_ring.py give the kernels'
-   outputs bit for bit on CPU copies of the same inputs (vis_prob, computed by two different exponentials: both within that 1e-6).
+   test_reversed_window_kernels).  On every window the mocks of tests/hip_mock.py give the kernels' outputs bit for bit on CPU
+   copies of the same inputs (vis_prob, computed by two different exponentials: both within that 1e-6).  The options combine: the
+   reversed sweep (flipped query frames, frame_step = -1, the query frames as `before`) also runs chunked and with a carry map, and
+   `before` also runs with frame_step = +1.
 B. Row kernels of tokens.hip: layernorm, delta_split, rowdot, broadcast_rows(_repeat), token_assemble, pos_embed; rows in
    {1, 5, 1000}.  LayerNorm / GroupNorm rows are m +- c with half the signs negative (and one entry m for odd C): sum, mean and the
    centred values are exact in any order, and the result is compared with fp64 F.layer_norm under the per-element bar
@@ -37,7 +39,6 @@ import torch
 import torch.nn.functional as F
 
 import hip_mock
-import hip_mock_ring
 from mvtracker_amd.backward import reversed_layout, window_prefixes
 
 gpu = pytest.mark.gpu
@@ -228,18 +229,18 @@ def run_windows(ops, lay, dev, reverse=False):
     r = dict(windows=list(windows), recs=[], order_d=order_t.to(dev), qt_d=torch.from_numpy(qt_s.astype(np.int32)).to(dev),
              qxyz_s=lay.qxyz[order_t].contiguous().to(dev), feat_s=lay.feat[order_t].contiguous().to(dev),
              traj=poison(T, N, 3, dev=dev, value=SENT), logit=poison(T, N, dev=dev, value=SENT), prob=poison(T, N, dev=dev, value=SENT))
+    # the reversed pass: slot 0 of the window that starts at w in reversed time is clip frame T-1-w, the slots run downwards, and
+    # only the frames before each row's query frame are stored
+    r["step"], r["before"] = (-1, r["qt_d"]) if reverse else (1, None)
     prev_c = prev_v = None
     p0 = 0
     for w, p1 in windows:
+        f0 = T - 1 - w if reverse else w
         wc, wm, wf = poison(p1, S, 3, dev=dev), poison(p1, S, 2, dev=dev), poison(p1, S, CW, dev=dev)
-        prep = ops.window_prepare_reversed if reverse else ops.window_prepare
-        prep(r["qxyz_s"], r["qt_d"], r["feat_s"], prev_c, prev_v, p1, p0, S, CW, w, T, wc, wm, wf)
+        ops.window_prepare(r["qxyz_s"], r["qt_d"], r["feat_s"], prev_c, prev_v, p1, p0, S, CW, f0, T, wc, wm, wf, frame_step=r["step"])
         out, lg = standin(w, wc, wm[..., 1], wm[..., 0], wf)
-        if reverse:
-            ops.window_store_reversed(out, lg, r["order_d"], r["qt_d"], p1, S, w, T, N, r["traj"], r["logit"], r["prob"])
-        else:
-            ops.window_store(out, lg, r["order_d"], p1, S, w, T, N, r["traj"], r["logit"], r["prob"])
-        r["recs"].append(dict(w=w, p0=p0, p1=p1, prev_c=prev_c, prev_v=prev_v, wc=wc, wm=wm, wf=wf, out=out, lg=lg))
+        ops.window_store(out, lg, r["order_d"], p1, S, f0, T, N, r["traj"], r["logit"], r["prob"], frame_step=r["step"], before=r["before"])
+        r["recs"].append(dict(w=w, f0=f0, p0=p0, p1=p1, prev_c=prev_c, prev_v=prev_v, wc=wc, wm=wm, wf=wf, out=out, lg=lg))
         prev_c, prev_v, p0 = out, lg, p1
     return r
 
@@ -270,8 +271,10 @@ def check_run(run, ref, lay, reverse=False):
 
 # ---- the kernels' rules in torch (the probes' carrier and the vectorised statement of the grid-stride cases)
 
-def rule_prepare(qxyz, qt, feat, prev_c, prev_v, n, p0, S, Cc, w, T, coords, mask_vis, ffeats, carry_src=None, bug=None, reverse=False):
+def rule_prepare(qxyz, qt, feat, prev_c, prev_v, n, p0, S, Cc, frame0, T, coords, mask_vis, ffeats, frame_step=1, carry_src=None, bug=None):
     dev = coords.device
+    reverse = frame_step < 0
+    w = T - 1 - frame0 if reverse else frame0  # the window start in the pass's own time
     half = S // 2
     s = torch.arange(S, device=dev)
     last = S - 2 if bug == "carry_from_S-2" else S - 1
@@ -292,7 +295,8 @@ def rule_prepare(qxyz, qt, feat, prev_c, prev_v, n, p0, S, Cc, w, T, coords, mas
     if reverse:
         f0 = T - 1 - w
         f = (f0 - sl)[None, :]
-        entered, first_half = f <= q, f > f0 - half
+        entered = f < q if bug == "rev:f<qt" else f <= q
+        first_half = f >= f0 - half if bug == "rev:f>=f0-half" else f > f0 - half
     else:
         f = (w + sl)[None, :]
         entered = f > q if bug == "f>qt" else f >= q
@@ -303,39 +307,47 @@ def rule_prepare(qxyz, qt, feat, prev_c, prev_v, n, p0, S, Cc, w, T, coords, mas
     ffeats.reshape(-1)[:n * S * Cc].copy_(feat[:n, None, :].expand(n, S, Cc).reshape(-1))
 
 
-def rule_store(coords, vis, order, n, S, w, T, N, traj, vis_logit, vis_prob, bug=None, qt=None):
-    """qt given: the reversed form (slot s is frame T-1-w-s, written only before the row's query frame)."""
+def rule_store(coords, vis, order, n, S, frame0, T, N, traj, vis_logit, vis_prob, frame_step=1, before=None, frames=None, bug=None):
+    """Slot s is frame frame0 + frame_step * s; written to row frame - f0 where the frame lies in `frames` = (f0, f1) (None: the whole
+    clip) and before the row's bound, if one is given."""
     dev = coords.device
-    s_local = min(S, T - w)
+    f0, f1 = (0, T) if frames is None else frames
+    s_local = min(S, T - frame0 if frame_step > 0 else frame0 + 1)
     if bug == "drop_last_short_slot" and s_local < S:
         s_local -= 1
     o = torch.arange(n, device=dev) if bug == "no_order" else order[:n]
     s = torch.arange(s_local, device=dev)
-    fr = ((w + s) if qt is None else (T - 1 - w - s))[None, :].expand(n, s_local)
-    keep = torch.ones(n, s_local, dtype=torch.bool, device=dev) if qt is None else fr < qt[:n].long()[:, None]
-    fi, ni = fr[keep], o[:, None].expand(n, s_local)[keep]
+    fr = (frame0 + frame_step * s)[None, :].expand(n, s_local)
+    keep = (fr >= f0) & (fr < f1)
+    if before is not None:
+        keep = keep & (fr < before[:n].long()[:, None])
+    fi, ni = fr[keep] - f0, o[:, None].expand(n, s_local)[keep]
     lg = vis.reshape(n, S)[:, :s_local][keep]
     traj.reshape(-1, N, 3)[fi, ni] = coords.reshape(n, S, 3)[:, :s_local][keep]
     vis_logit.reshape(-1, N)[fi, ni] = lg
-    vis_prob.reshape(-1, N)[fi, ni] = torch.sigmoid(lg)
+    # (the sigmoid of the whole window, then the selection: torch's CPU sigmoid is not the same bits for every vector length, and
+    #  the chunks of one window are compared side by side with its whole-clip store)
+    vis_prob.reshape(-1, N)[fi, ni] = torch.sigmoid(vis.reshape(n, S))[:, :s_local][keep]
 
 
 def rule_ops(bug=None):
-    return types.SimpleNamespace(
-        window_prepare=functools.partial(rule_prepare, bug=bug), window_store=functools.partial(rule_store, bug=bug),
-        window_prepare_reversed=functools.partial(rule_prepare, reverse=True),
-        window_store_reversed=lambda coords, vis, order, qt, n, S, wr, T, N, traj, lg, pr: rule_store(coords, vis, order, n, S, wr, T, N,
-                                                                                                    traj, lg, pr, qt=qt))
+    return types.SimpleNamespace(window_prepare=functools.partial(rule_prepare, bug=bug), window_store=functools.partial(rule_store, bug=bug))
 
 
-PROBES = ["f>qt", "f<=w+half", "f<w+half-1", "carry_from_S-2", "vis_other_slot", "no_order", "drop_last_short_slot"]
+REVERSED_PROBES = ["rev:f<qt", "rev:f>=f0-half"]  # the mirror images of "f>qt" and "f<=w+half": they break the reversed rule only
+PROBES = ["f>qt", "f<=w+half", "f<w+half-1", "carry_from_S-2", "vis_other_slot", "no_order", "drop_last_short_slot"] + REVERSED_PROBES
 
 
-def failing_layouts(ops):
+def failing_layouts(ops, reverse=False):
+    """Layouts whose sweep fails; reverse: the reversed sweep (each layout's reference against the reversed pass of its flip)."""
     bad = 0
     for lay, ref in zip(layouts(), references()):
         try:
-            check_run(run_windows(ops, lay, "cpu"), ref, lay)
+            if reverse:
+                rl = flip_layout(lay)
+                check_run(run_windows(ops, rl, "cpu", reverse=True), ref, rl, reverse=True)
+            else:
+                check_run(run_windows(ops, lay, "cpu"), ref, lay)
         except AssertionError:
             bad += 1
     return bad
@@ -365,53 +377,45 @@ def test_reference_reversed_against_rule():
     for lay in layouts():
         rl = flip_layout(lay)
         check_run(run_windows(rule_ops(), rl, "cpu", reverse=True), reference_loop(lay.qt, lay.qxyz, lay.feat, lay.S, lay.T), rl, reverse=True)
+    assert failing_layouts(hip_mock, reverse=True) == 0
 
 
 @pytest.mark.parametrize("bug", PROBES)
 def test_window_probes_break_the_sweep(bug):
-    bad = failing_layouts(rule_ops(bug))
-    print(f"{bug}: {bad} of {len(layouts())} layouts fail")
+    """Each planted fault fails the sweep of its direction, and leaves the other direction's alone."""
+    rev = bug in REVERSED_PROBES
+    bad = failing_layouts(rule_ops(bug), reverse=rev)
+    print(f"{bug}: {bad} of {len(layouts())} layouts fail the {'reversed' if rev else 'forward'} sweep")
     assert bad > 0
-
-
-def test_mock_ring_chunk_against_mock_store():
-    """hip_mock_ring.window_store_chunk over a partition of the clip lays out hip_mock.window_store's result (what the GPU test
-    asserts of the kernels, here of the mocks alone)."""
-    for lay in layouts()[::7]:
-        run = run_windows(hip_mock, lay, "cpu")
-        for rec in run["recs"]:
-            check_chunks(hip_mock.window_store, hip_mock_ring.window_store_chunk, None, rec, run, lay, "cpu")
-
-
-@functools.lru_cache(maxsize=None)
-def device_runs():
-    from mvtracker_amd import hip
-    ops = types.SimpleNamespace(window_prepare=lambda *a: hip.window_prepare(*a), window_store=lambda *a: hip.window_store(*a))
-    runs = [run_windows(ops, lay, DEV) for lay in layouts()]
-    torch.cuda.synchronize()
-    return runs
+    if rev:
+        assert failing_layouts(rule_ops(bug)) == 0
 
 
 def fresh_outputs(f, N, dev):
     return [poison(f, N, 3, dev=dev, value=SENT), poison(f, N, dev=dev, value=SENT), poison(f, N, dev=dev, value=SENT)]
 
 
-def check_chunks(store, store_chunk, mock_chunk, rec, run, lay, dev):
-    S, T, N, w, p1 = lay.S, lay.T, lay.N, rec["w"], rec["p1"]
+def check_chunks(store, mock_store, rec, run, lay, dev):
+    """Chunk stores over partitions of the clip, side by side, are the whole-clip store of the run's pass (and what `mock_store`
+    gives chunk by chunk); a chunk outside the window's frames stays at the sentinel."""
+    S, T, N, w, fr0, p1 = lay.S, lay.T, lay.N, rec["w"], rec["f0"], rec["p1"]
+    opts = dict(frame_step=run["step"], before=run["before"])
+    mopts = dict(frame_step=run["step"], before=cpu(run["before"]))
+    lo, hi = sorted((fr0, fr0 + run["step"] * (S - 1)))  # the window's frames, before the clip's ends cut them
     whole = fresh_outputs(T, N, dev)
-    store(rec["out"], rec["lg"], run["order_d"], p1, S, w, T, N, *whole)
+    store(rec["out"], rec["lg"], run["order_d"], p1, S, fr0, T, N, *whole, **opts)
     for L in sorted({1, S // 2, S // 2 + 1, T}):
         parts, mocks = [], []
         for f0 in range(0, T, L):
             f1 = min(f0 + L, T)
             ch = fresh_outputs(f1 - f0, N, dev)
-            store_chunk(rec["out"], rec["lg"], run["order_d"], p1, S, w, T, f0, f1, N, *ch)
-            if f1 <= w or f0 >= w + S:  # a chunk that does not meet the window: success, nothing written
+            store(rec["out"], rec["lg"], run["order_d"], p1, S, fr0, T, N, *ch, frames=(f0, f1), **opts)
+            if f1 <= lo or f0 > hi:  # a chunk that does not meet the window: success, nothing written
                 assert all(float((c - SENT).abs().max()) == 0.0 for c in ch), (lay[:4], w, f0, f1)
             parts.append(ch)
-            if mock_chunk is not None:
+            if mock_store is not None:
                 mk = fresh_outputs(f1 - f0, N, "cpu")
-                mock_chunk(cpu(rec["out"]), cpu(rec["lg"]), cpu(run["order_d"]), p1, S, w, T, f0, f1, N, *mk)
+                mock_store(cpu(rec["out"]), cpu(rec["lg"]), cpu(run["order_d"]), p1, S, fr0, T, N, *mk, frames=(f0, f1), **mopts)
                 mocks.append(mk)
         for k in range(3):
             side = torch.cat([p[k] for p in parts], 0)
@@ -424,6 +428,99 @@ def check_chunks(store, store_chunk, mock_chunk, rec, run, lay, dev):
                     wrote = mside != SENT
                     check_prob(side, torch.cat([p[1] for p in parts], 0), wrote)
                     check_prob(mside, torch.cat([m[1] for m in mocks], 0), wrote)
+
+
+def check_mapped(prepare, rec, run, lay, dev):
+    """The carry map: the prefix form written as a map, then the window's rows permuted with the previous window's rows scattered
+    over a larger, poisoned buffer, both against the prefix form's outputs in `rec`."""
+    S, T = lay.S, lay.T
+    fr0, p0, p1 = rec["f0"], rec["p0"], rec["p1"]
+    g = gen("mapped", lay[:4], rec["w"])
+    carry = torch.where(torch.arange(p1) < p0, torch.arange(p1), torch.full((p1,), -1)).int().to(dev)
+    wc, wm, wf = poison(p1, S, 3, dev=dev), poison(p1, S, 2, dev=dev), poison(p1, S, CW, dev=dev)
+    prepare(run["qxyz_s"], run["qt_d"], run["feat_s"], rec["prev_c"], rec["prev_v"], p1, 0, S, CW, fr0, T, wc, wm, wf, frame_step=run["step"],
+            carry_src=carry)
+    assert torch.equal(wc, rec["wc"]) and torch.equal(wm, rec["wm"]) and torch.equal(wf, rec["wf"]), (lay[:4], rec["w"])
+    perm = torch.randperm(p1, generator=g)
+    pos = torch.randperm(p0 + 2, generator=g)[:p0]
+    prev_c = prev_v = None
+    if p0:
+        prev_c, prev_v = poison(p0 + 2, S, 3, dev=dev), poison(p0 + 2, S, dev=dev)
+        prev_c[pos.to(dev)] = rec["prev_c"]
+        prev_v[pos.to(dev)] = rec["prev_v"]
+    carry = torch.tensor([int(pos[r]) if r < p0 else -1 for r in perm.tolist()], dtype=torch.int32).to(dev)
+    pd = perm.to(dev)
+    wc, wm, wf = poison(p1, S, 3, dev=dev), poison(p1, S, 2, dev=dev), poison(p1, S, CW, dev=dev)
+    prepare(run["qxyz_s"][pd].contiguous(), run["qt_d"][pd].contiguous(), run["feat_s"][pd].contiguous(), prev_c, prev_v, p1, 0, S, CW, fr0, T,
+            wc, wm, wf, frame_step=run["step"], carry_src=carry)
+    assert torch.equal(wc, rec["wc"][pd]) and torch.equal(wm, rec["wm"][pd]) and torch.equal(wf, rec["wf"][pd]), (lay[:4], rec["w"])
+
+
+def check_before_forward(store, rec, run, lay, dev):
+    """A per-row frame bound on the forward store: `rule_store`'s result, which is the unbounded store with every caller column
+    put back to the sentinel from its row's bound on."""
+    S, T, N, w, p1 = lay.S, lay.T, lay.N, rec["w"], rec["p1"]
+    before = torch.randint(0, T + 2, (p1,), generator=gen("before", lay[:4], w)).int().to(dev)
+    before[0] = w + S // 2  # a bound inside the window whatever the draw
+    got, want, free = fresh_outputs(T, N, dev), fresh_outputs(T, N, dev), fresh_outputs(T, N, dev)
+    store(rec["out"], rec["lg"], run["order_d"], p1, S, w, T, N, *got, before=before)
+    rule_store(rec["out"], rec["lg"], run["order_d"], p1, S, w, T, N, *want, before=before)
+    rule_store(rec["out"], rec["lg"], run["order_d"], p1, S, w, T, N, *free)
+    bound = torch.zeros(N, dtype=torch.long, device=dev)
+    bound[run["order_d"][:p1]] = before.long()
+    cut = torch.arange(T, device=dev)[:, None] >= bound[None, :]
+    free[0][cut], free[1][cut] = SENT, SENT
+    assert torch.equal(want[0], free[0]) and torch.equal(want[1], free[1]), (lay[:4], w)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), (lay[:4], w)
+    wrote = (want[1] != SENT).cpu()
+    assert bool(wrote.any()) == bool((before.long() > w).any())
+    check_prob(got[2], got[1], wrote)
+
+
+def cpu_runs(ops, reverse, every=7):
+    """(layout, run) of every `every`-th sweep layout on the CPU; reverse: the reversed pass of the flipped layout."""
+    for lay in layouts()[::every]:
+        lay = flip_layout(lay) if reverse else lay
+        yield lay, run_windows(ops, lay, "cpu", reverse=reverse)
+
+
+def test_mock_ring_chunk_against_mock_store():
+    """hip_mock.window_store with `frames` over a partition of the clip lays out its whole-clip result, and the kernel rule's chunk
+    by chunk (what the GPU tests assert of the kernels, here of the stand-ins alone), forwards and on the reversed sweep."""
+    for reverse in (False, True):
+        for lay, run in cpu_runs(hip_mock, reverse):
+            for rec in run["recs"]:
+                check_chunks(hip_mock.window_store, None, rec, run, lay, "cpu")
+                check_chunks(rule_ops().window_store, hip_mock.window_store, rec, run, lay, "cpu")
+
+
+def test_carry_map_against_rule_and_mock():
+    """The carry-map cases of test_window_prepare_mapped on the stand-ins alone, forwards and on the reversed sweep."""
+    for ops in (rule_ops(), hip_mock):
+        for reverse in (False, True):
+            for lay, run in cpu_runs(ops, reverse):
+                for rec in run["recs"]:
+                    check_mapped(ops.window_prepare, rec, run, lay, "cpu")
+
+
+def test_before_forward_against_rule_and_mock():
+    for ops in (rule_ops(), hip_mock):
+        for lay, run in cpu_runs(ops, False):
+            for rec in run["recs"]:
+                check_before_forward(ops.window_store, rec, run, lay, "cpu")
+
+
+def device_ops():
+    from mvtracker_amd import hip
+    return types.SimpleNamespace(window_prepare=lambda *a, **k: hip.window_prepare(*a, **k), window_store=lambda *a, **k: hip.window_store(*a, **k))
+
+
+@functools.lru_cache(maxsize=None)
+def device_runs(reverse=False):
+    """The sweep on the device; reverse: the reversed pass of every flipped layout (the reference is the unflipped layout's)."""
+    runs = [run_windows(device_ops(), flip_layout(lay) if reverse else lay, DEV, reverse=reverse) for lay in layouts()]
+    torch.cuda.synchronize()
+    return runs
 
 
 @gpu
@@ -455,45 +552,77 @@ def test_window_mock_conformity(hip):
 def test_window_store_chunk(hip):
     for lay, run in zip(layouts(), device_runs()):
         for rec in run["recs"]:
-            check_chunks(lambda *a: hip.window_store(*a), lambda *a: hip.window_store_chunk(*a), hip_mock_ring.window_store_chunk, rec, run,
-                         lay, DEV)
+            check_chunks(device_ops().window_store, hip_mock.window_store, rec, run, lay, DEV)
+
+
+@gpu
+def test_window_store_chunk_reversed(hip):
+    """Reversed chunks: on the reversed sweep, chunk stores over the same partitions equal the whole-clip reversed store."""
+    for lay, run in zip(layouts(), device_runs(reverse=True)):
+        for rec in run["recs"]:
+            check_chunks(device_ops().window_store, hip_mock.window_store, rec, run, flip_layout(lay), DEV)
 
 
 @gpu
 def test_window_prepare_mapped(hip):
     for lay, run in zip(layouts(), device_runs()):
-        S, T = lay.S, lay.T
         for rec in run["recs"]:
-            w, p0, p1 = rec["w"], rec["p0"], rec["p1"]
-            g = gen("mapped", lay[:4], w)
-            # the prefix form as a map
-            carry = torch.where(torch.arange(p1) < p0, torch.arange(p1), torch.full((p1,), -1)).int().to(DEV)
-            wc, wm, wf = poison(p1, S, 3, dev=DEV), poison(p1, S, 2, dev=DEV), poison(p1, S, CW, dev=DEV)
-            hip.window_prepare_mapped(run["qxyz_s"], run["qt_d"], run["feat_s"], rec["prev_c"], rec["prev_v"], carry, p1, S, CW, w, T, wc, wm, wf)
-            assert torch.equal(wc, rec["wc"]) and torch.equal(wm, rec["wm"]) and torch.equal(wf, rec["wf"]), (lay[:4], w)
-            # the window's rows permuted, the previous window's rows scattered over a larger, poisoned buffer
-            perm = torch.randperm(p1, generator=g)
-            pos = torch.randperm(p0 + 2, generator=g)[:p0]
-            prev_c = prev_v = None
-            if p0:
-                prev_c, prev_v = poison(p0 + 2, S, 3, dev=DEV), poison(p0 + 2, S, dev=DEV)
-                prev_c[pos.to(DEV)] = rec["prev_c"]
-                prev_v[pos.to(DEV)] = rec["prev_v"]
-            carry = torch.tensor([int(pos[r]) if r < p0 else -1 for r in perm.tolist()], dtype=torch.int32).to(DEV)
-            pd = perm.to(DEV)
-            wc, wm, wf = poison(p1, S, 3, dev=DEV), poison(p1, S, 2, dev=DEV), poison(p1, S, CW, dev=DEV)
-            hip.window_prepare_mapped(run["qxyz_s"][pd].contiguous(), run["qt_d"][pd].contiguous(), run["feat_s"][pd].contiguous(), prev_c, prev_v,
-                                      carry, p1, S, CW, w, T, wc, wm, wf)
-            assert torch.equal(wc, rec["wc"][pd]) and torch.equal(wm, rec["wm"][pd]) and torch.equal(wf, rec["wf"][pd]), (lay[:4], w)
+            check_mapped(device_ops().window_prepare, rec, run, lay, DEV)
+
+
+@gpu
+def test_window_prepare_mapped_reversed(hip):
+    """Reversed carry map: the cases of test_window_prepare_mapped on the reversed sweep."""
+    for lay, run in zip(layouts(), device_runs(reverse=True)):
+        for rec in run["recs"]:
+            check_mapped(device_ops().window_prepare, rec, run, flip_layout(lay), DEV)
+
+
+@gpu
+def test_window_store_before_forward(hip):
+    """`before` with frame_step = +1, against rule_store."""
+    for lay, run in zip(layouts(), device_runs()):
+        for rec in run["recs"]:
+            check_before_forward(device_ops().window_store, rec, run, lay, DEV)
 
 
 @gpu
 def test_window_sweep_reversed(hip):
-    ops = types.SimpleNamespace(window_prepare_reversed=lambda *a: hip.window_prepare_reversed(*a),
-                                window_store_reversed=lambda *a: hip.window_store_reversed(*a))
-    for lay, ref in zip(layouts(), references()):
-        rl = flip_layout(lay)
-        check_run(run_windows(ops, rl, DEV, reverse=True), ref, rl, reverse=True)
+    for lay, run, ref in zip(layouts(), device_runs(reverse=True), references()):
+        check_run(run, ref, flip_layout(lay), reverse=True)
+
+
+@gpu
+def test_window_entries_refuse_bad_arguments(hip):
+    """frame_step = 0, a carry map together with a carried prefix, and a chunk past the clip's end: return code 1, nothing launched,
+    nothing written.  The same calls with the argument put right are accepted."""
+    n, p0, S, T, w = 5, 2, 4, 9, 3
+    g = gen("refuse")
+    qxyz, feat, qt = G(ints(g, -9, 9, n, 3)), G(ints(g, -3, 3, n, CW)), torch.tensor([0, 1, 3, 4, 5], dtype=torch.int32, device=DEV)
+    prev_c, prev_v = G(ints(g, -99, 99, p0, S, 3)), G(ints(g, -18, 18, p0, S))
+    carry = torch.tensor([0, 1, -1, -1, -1], dtype=torch.int32, device=DEV)
+    coords, vis, order = G(ints(g, -99, 99, n, S, 3)), G(ints(g, -18, 18, n, S)), torch.randperm(n, generator=g).to(DEV)
+
+    def prepare(outs, p0=0, **kw):
+        hip.window_prepare(qxyz, qt, feat, prev_c, prev_v, n, p0, S, CW, w, T, *outs, **kw)
+
+    def store(outs, T_=T, **kw):
+        hip.window_store(coords, vis, order, n, S, w, T_, n, *outs, **kw)
+
+    good = [poison(n, S, 3, dev=DEV), poison(n, S, 2, dev=DEV), poison(n, S, CW, dev=DEV)]
+    prepare(good, carry_src=carry)
+    stored = fresh_outputs(2, n, DEV)
+    store(stored, frames=(w, w + 2))
+    torch.cuda.synchronize()
+    assert not any(bool(torch.isnan(b).any()) for b in good) and not any(bool((b == SENT).any()) for b in stored)
+    bad = [poison(n, S, 3, dev=DEV), poison(n, S, 2, dev=DEV), poison(n, S, CW, dev=DEV)]
+    kept = fresh_outputs(2, n, DEV)
+    for call in (lambda: prepare(bad, p0=p0, frame_step=0), lambda: prepare(bad, p0=p0, carry_src=carry),
+                 lambda: store(kept, frame_step=0, frames=(w, w + 2)), lambda: store(kept, T_=w + 1, frames=(w, w + 2))):
+        with pytest.raises(hip.HipError, match="arguments rejected"):
+            call()
+    torch.cuda.synchronize()
+    assert all(untouched(b) for b in bad) and all(bool((b == SENT).all()) for b in kept)
 
 
 @gpu

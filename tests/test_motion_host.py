@@ -54,7 +54,7 @@ def test_exports_and_constants(tmp_path):
     assert MotionMask is motion.MotionMask and MotionReport is motion.MotionReport and motion_masks is motion.motion_masks
     assert {"motion", "MotionMask", "MotionReport", "motion_masks"} <= set(mvtracker_amd.__all__)
     assert all(n in hip.SIGNATURES for n in ("mvt_motion_blocks", "mvt_motion_tiles", "mvt_motion_temporal", "mvt_motion_mask", "mvt_motion_report"))
-    assert hip.abi_version() == 8
+    assert hip.abi_version() == 9
     m = MotionMask()
     assert (m.window, m.patch_radius, m.diff_thresh) == (-1, 7, 10.0)  # the reference's
     with pytest.raises(Exception):
