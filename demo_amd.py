@@ -86,6 +86,15 @@ def build_parser():
                          "from a ring frame store whose size does not depend on the clip length")
     ap.add_argument("--block-frames", type=int, default=6, metavar="B", help="frames per pushed block with --streaming")
     ap.add_argument("--save-npz", help="result file (tracks_3d, visibilities, query_points, camera data)")
+    ap.add_argument("--save-overlay", metavar="DIR", default=None,
+                    help="draw the tracks into every view's frames on the device (mvtracker_amd.render_track_overlays, the reference's "
+                         "visualizer_mp4 drawing rules) and write view{v}_frame{t:04d}.png into DIR (one view{v}.npy per view without PIL)")
+    ap.add_argument("--overlay-trail", type=int, default=None, metavar="L", help="segments a track leaves behind: -1 all (default), 0 none")
+    ap.add_argument("--overlay-linewidth", type=int, default=None, metavar="W", help="line width 1..8 (default 2); markers have twice the radius")
+    ap.add_argument("--overlay-pad", type=int, default=None, metavar="P", help="white border of P pixels, 0..64 (default 0)")
+    ap.add_argument("--overlay-min-depth", type=float, default=None, metavar="D",
+                    help="draw a point only when its camera depth exceeds D (default: no test, as the reference)")
+    ap.add_argument("--overlay-max-tracks", type=int, default=None, metavar="M", help="draw only the first M tracks (the reference draws 36)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--clean-depths", choices=["statistical", "radius"], default=None,
                     help="remove outliers from every (view, frame) depth map before tracking (mvtracker_amd.clean_depths, the reference "
@@ -200,8 +209,45 @@ def query_motion_from_args(args):
         raise SystemExit(str(e)) from None
 
 
+def track_overlay_from_args(args):
+    """The TrackOverlay of --save-overlay and the --overlay-* flags, or None."""
+    names = ("trail", "linewidth", "pad", "min_depth", "max_tracks")
+    details = {k: getattr(args, "overlay_" + k) for k in names if getattr(args, "overlay_" + k) is not None}
+    if args.save_overlay is None:
+        if details:
+            raise SystemExit("--overlay-trail / -linewidth / -pad / -min-depth / -max-tracks need --save-overlay")
+        return None
+    from mvtracker_amd import TrackOverlay
+    try:
+        return TrackOverlay(**details)
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+
+
+def save_overlay(video, directory):
+    """video (V, T, 3, Hp, Wp) uint8 -> view{v}_frame{t:04d}.png in ``directory`` with PIL when it imports, else one view{v}.npy
+    (T, 3, Hp, Wp) per view; the list of files written."""
+    os.makedirs(directory, exist_ok=True)
+    frames = video.cpu().numpy()
+    files = []
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+    for v in range(frames.shape[0]):
+        if Image is None:
+            files.append(os.path.join(directory, f"view{v}.npy"))
+            np.save(files[-1], frames[v])
+            continue
+        for t in range(frames.shape[1]):
+            files.append(os.path.join(directory, f"view{v}_frame{t:04d}.png"))
+            Image.fromarray(np.ascontiguousarray(frames[v, t].transpose(1, 2, 0))).save(files[-1])
+    return files
+
+
 def main():
     args = build_parser().parse_args()
+    track_overlay = track_overlay_from_args(args)
     region, region_poses = query_region_from_args(args, args.temporal_stride)  # (flag errors before any work)
     motion, motion_keep = query_motion_from_args(args)
     if not torch.cuda.is_available():
@@ -316,6 +362,12 @@ def main():
         sample_io.save_result(args.save_npz, out["traj_e"], out["vis_e"], s, temporal_stride=args.temporal_stride,
                               spatial_downsample=args.spatial_downsample)
         print("saved", args.save_npz)
+    if track_overlay is not None:  # after the timed call, from what it returned: the streaming path has the same tracks
+        from mvtracker_amd import render_track_overlays
+        video, _ = render_track_overlays(s["rgbs"][0], out["traj_e"][0], out["vis_e"][0], s["query_points_3d"][0, :, 0], s["intrs"][0], s["extrs"][0],
+                                         track_overlay)
+        files = save_overlay(video, args.save_overlay)
+        print(f"track overlay: {tuple(video.shape)} drawn on the device, {len(files)} files in {args.save_overlay}")
 
 
 if __name__ == "__main__":

@@ -1059,6 +1059,46 @@ int mvt_motion_mask(const float* src, int V, int T, int H, int W, int win, int r
  * out as mvt_motion_mask wrote them: all_mode = its win == 0), each added in an order fixed by the number of terms. */
 int mvt_motion_report(const double* partial, const int* counts, int V, int T, int H, int W, int all_mode, double* report, void* stream);
 
+/* ---- track overlays (csrc/overlay.hip; mvtracker_amd/overlay.py drives these) ----
+ * The tracker's world-space tracks drawn into every view's frames (reference: mvtracker/utils/visualizer_mp4.py Visualizer.visualize,
+ * draw_tracks_on_video, _draw_pred_tracks; DESIGN section 8 "Track overlays" states the rule and its deviations).
+ * Projection of track point (x, y, z) by K (3x3) and E (3x4) of its (view, frame), fp32, every operation rounded on its own:
+ *   c_r = ((E[r,0] x + E[r,1] y) + E[r,2] z) + E[r,3];  h_r = (K[r,0] c_0 + K[r,1] c_1) + K[r,2] c_2;  px = h_0 / h_2, py = h_1 / h_2.
+ * Integer point: px, py clipped to [-1e4, 1e4], + pad in fp32, truncated toward zero.  It is invalid when px or py is NaN, or when
+ * use_min_depth and not c_2 > min_depth.
+ * Frame t of a view, later overwrites earlier: the frame (a float frame clamped to [0, 255] and truncated, NaN -> 0; 255 on the
+ * border of `pad` pixels); for s in the trail window, ascending, for track i ascending, the stroke from point (s, i) to point
+ * (s+1, i) unless s < query_frames[i], an endpoint is invalid or an endpoint is (0, 0); for i ascending the marker of point (t, i)
+ * unless query_frames[i] > t, it is invalid, or x == 0 or y == 0: a disc of radius R = 2 linewidth when visible, else a ring.
+ * Primitives, integer, not anti-aliased, clipped to the padded image: stroke of width w from a to b with d = b - a, L2 = |d|^2,
+ * q = (p - a).d covers p iff (q <= 0: 4 |p-a|^2 <= w^2; q >= L2: 4 |p-b|^2 <= w^2; else 4 ((p-a) x d)^2 <= w^2 L2); disc
+ * |p-c|^2 <= R^2; ring (2R-1)^2 <= 4 |p-c|^2 <= (2R+1)^2.
+ * Key planes (V, Hp, Wp) uint64, Hp = H + 2 pad, zero = empty, key = order << 24 | r << 16 | g << 8 | b kept by atomic maximum:
+ * the line plane persists over the frames of a clip (order (s+1) << 20 | i), the marker plane (order i + 1) is reset by
+ * mvt_overlay_compose.  Limits: N and every frame number < MVT_OVERLAY_MAX_INDEX, Hp and Wp <= MVT_OVERLAY_MAX_SIDE (all integer
+ * terms then fit 64 bits), V * Hp * Wp < 2^31.  The same bits in every run. */
+#define MVT_OVERLAY_MAX_LINEWIDTH 8
+#define MVT_OVERLAY_MAX_PAD 64
+#define MVT_OVERLAY_MAX_SIDE 8192
+#define MVT_OVERLAY_MAX_INDEX (1 << 20)
+/* tracks (T, N, 3), intrs (V, T, 3, 3), extrs (V, T, 3, 4).  Any of: xyz (V, T, N, 3) fp32 <- (px, py, c_2), the reference's
+ * world_space_to_pixel_xy_and_camera_z per view; points (T, V, N, 4) int32 <- (x, y, valid, 0); and, with lut (256, 3) uint8,
+ * colors[n] <- lut[min(255, max(0, y * 256 / Hp))] for every track n whose query frame max(query_frames[n], 0) is frame0 + t for
+ * a t of this launch, y the integer y in view color_view (pad when that point is invalid).  frame0: the clip's number of t = 0. */
+int mvt_overlay_project(const float* tracks, const float* intrs, const float* extrs, int V, int T, int N, float* xyz, int* points, int pad,
+                        int use_min_depth, float min_depth, const int* query_frames, int frame0, const unsigned char* lut, int color_view, int Hp,
+                        unsigned char* colors, void* stream);
+/* The scatter of frame t: the markers of cur (V, N, 4) into marker_keys and, with prev (the points of frame t-1; t >= 1) and
+ * line_keys, the segments t-1 -> t into line_keys (both or neither).  Tracks 0..M-1 of N are drawn; visibility (N) bytes of
+ * frame t or NULL (all visible); colors (N, 3) uint8; query_frames (N) int32. */
+int mvt_overlay_draw(const int* prev, const int* cur, const unsigned char* visibility, const int* query_frames, const unsigned char* colors, int V,
+                     int N, int M, int t, int linewidth, int Hp, int Wp, unsigned long long* line_keys, unsigned long long* marker_keys,
+                     void* stream);
+/* out[:, t_local] of (V, T, 3, Hp, Wp) uint8 <- marker key, else the line key when its segment s >= first_segment (line_keys NULL:
+ * no lines), else frames[:, t_local] of (V, T, 3, H, W) uint8 or fp32, else 255; marker_keys is zero again afterwards. */
+int mvt_overlay_compose(const void* frames, int is_u8, int V, int T, int t_local, int H, int W, int pad, const unsigned long long* line_keys,
+                        int first_segment, unsigned long long* marker_keys, unsigned char* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

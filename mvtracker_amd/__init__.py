@@ -1,6 +1,6 @@
 """MI355X-native multi-view point-tracking forward path (drop-in for mvtracker.models' predictor).
 
-    from mvtracker_amd import MVTracker, EvaluationPredictor, load_mvtracker, sample_queries, auto_scene_normalization, DepthCleaning, clean_depths, CameraAlignment, align_cameras, estimate_normals, voxel_downsample, ReprojectionCheck, reprojection_report, RegionCluster, region_masks, cluster_points, MotionMask, motion_masks
+    from mvtracker_amd import MVTracker, EvaluationPredictor, load_mvtracker, sample_queries, auto_scene_normalization, DepthCleaning, clean_depths, CameraAlignment, align_cameras, estimate_normals, voxel_downsample, ReprojectionCheck, reprojection_report, RegionCluster, region_masks, cluster_points, MotionMask, motion_masks, TrackOverlay, render_track_overlays
 
 ``synth`` (numpy only) can be imported without the HIP library; everything else loads
 libmvtracker_hip.so on import and raises if it is missing -- there is no CPU fallback.
@@ -10,7 +10,8 @@ __all__ = ["MVTracker", "EvaluationPredictor", "load_mvtracker", "hip", "synth",
            "clean_point_cloud", "align", "CameraAlignment", "PcaCameraAlignment", "CameraCorrection", "align_cameras", "align_point_clouds", "cloud",
            "estimate_normals", "voxel_downsample", "reproject", "ReprojectionCheck", "ReprojectionReport", "reprojection_report", "reproject_views",
            "render_point_cloud", "compare_reports", "cluster", "RegionCluster", "RegionReport", "cluster_points", "select_region_points",
-           "region_masks", "motion", "MotionMask", "MotionReport", "motion_masks"]
+           "region_masks", "motion", "MotionMask", "MotionReport", "motion_masks", "overlay", "TrackOverlay", "TrackOverlaySession", "project_tracks",
+           "render_track_overlays", "open_track_overlay", "stack_views"]
 
 
 def __getattr__(name):
@@ -47,7 +48,10 @@ def __getattr__(name):
     if name in ("MotionMask", "MotionReport", "motion_masks"):
         from . import motion
         return getattr(motion, name)
-    if name in ("hip", "synth", "sample_io", "adapter", "geometry", "parallel", "queries", "scene", "clean", "align", "cloud", "reproject", "cluster", "motion"):
+    if name in ("TrackOverlay", "TrackOverlaySession", "project_tracks", "render_track_overlays", "open_track_overlay", "stack_views"):
+        from . import overlay
+        return getattr(overlay, name)
+    if name in ("hip", "synth", "sample_io", "adapter", "geometry", "parallel", "queries", "scene", "clean", "align", "cloud", "reproject", "cluster", "motion", "overlay"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -133,6 +133,9 @@ SIGNATURES = {
     "mvt_motion_temporal": [P, I, I, I, I, I, I, P, P, P],
     "mvt_motion_mask": [P, I, I, I, I, I, I, F, P, P, P],
     "mvt_motion_report": [P, P, I, I, I, I, I, P, P],
+    "mvt_overlay_project": [P, P, P, I, I, I, P, P, I, I, F, P, I, P, I, I, P, P],
+    "mvt_overlay_draw": [P, P, P, P, P, I, I, I, I, I, I, I, P, P, P],
+    "mvt_overlay_compose": [P, I, I, I, I, I, I, I, P, I, P, P, P],
 }
 _RET = {"mvt_build_arch": C.c_char_p, "mvt_encoder_workspace_bytes": C.c_longlong, "mvt_updateformer_workspace_bytes": C.c_longlong,
         "mvt_updateformer_grouped_workspace_bytes": C.c_longlong}
@@ -1247,3 +1250,51 @@ def motion_report(partial, counts, V, T, H, W, all_mode, report):
     assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= V * (1 if all_mode else T) * motion_tiles(H, W)
     assert report.dtype == torch.float64 and report.is_contiguous() and report.numel() >= T - 1 + V * T
     _call("mvt_motion_report", _ptr(partial), _ptr(counts), V, T, H, W, int(bool(all_mode)), _ptr(report), _stream())
+
+
+# ------------------------------------------------------------------ track overlays (mvtracker_amd/overlay.py drives these)
+OVERLAY_MAX_LINEWIDTH, OVERLAY_MAX_PAD, OVERLAY_MAX_SIDE, OVERLAY_MAX_INDEX = 8, 64, 8192, 1 << 20  # MVT_OVERLAY_*
+
+
+def overlay_project(tracks, intrs, extrs, V, T, N, xyz=None, points=None, pad=0, min_depth=None, query_frames=None, frame0=0, lut=None,
+                    color_view=0, Hp=0, colors=None):
+    """tracks (T, N, 3), intrs (V, T, 3, 3), extrs (V, T, 3, 4) fp32 -> any of xyz (V, T, N, 3) fp32 <- (px, py, camera z); points
+    (T, V, N, 4) int32 <- (x, y, valid, 0); with ``lut`` (256, 3) uint8, colors (N, 3) uint8 rows of the tracks whose query frame is
+    one of frame0 .. frame0 + T - 1."""
+    for a, shape in ((tracks, (T, N, 3)), (intrs, (V, T, 3, 3)), (extrs, (V, T, 3, 4))):
+        assert tuple(_f32c(a).shape) == shape, (tuple(a.shape), shape)
+    assert xyz is None or (tuple(_f32c(xyz).shape) == (V, T, N, 3))
+    assert points is None or (points.dtype == torch.int32 and points.is_contiguous() and tuple(points.shape) == (T, V, N, 4))
+    if lut is not None:
+        assert lut.dtype == torch.uint8 and lut.is_contiguous() and tuple(lut.shape) == (256, 3)
+        assert colors.dtype == torch.uint8 and colors.is_contiguous() and tuple(colors.shape) == (N, 3)
+        assert query_frames.dtype == torch.int32 and query_frames.is_contiguous() and query_frames.numel() == N
+    _call("mvt_overlay_project", _ptr(tracks), _ptr(intrs), _ptr(extrs), V, T, N, _ptr(xyz), _ptr(points), pad, int(min_depth is not None),
+          0.0 if min_depth is None else float(min_depth), _ptr(query_frames) if lut is not None else None, frame0, _ptr(lut), color_view, Hp,
+          _ptr(colors) if lut is not None else None, _stream())
+
+
+def overlay_draw(prev, cur, visibility, query_frames, colors, V, N, M, t, linewidth, Hp, Wp, line_keys, marker_keys):
+    """The markers of frame t (cur (V, N, 4) int32) into marker_keys and, with prev (frame t-1) and line_keys, the segments t-1 -> t
+    into line_keys, both (V, Hp, Wp) int64 holding unsigned keys.  visibility (N) bool of frame t or None."""
+    for p in (prev, cur):
+        assert p is None or (p.dtype == torch.int32 and p.is_contiguous() and tuple(p.shape) == (V, N, 4))
+    assert visibility is None or (visibility.dtype in (torch.bool, torch.uint8) and visibility.is_contiguous() and visibility.numel() == N)
+    assert query_frames.dtype == torch.int32 and query_frames.is_contiguous() and query_frames.numel() == N
+    assert colors.dtype == torch.uint8 and colors.is_contiguous() and tuple(colors.shape) == (N, 3)
+    for k in (line_keys, marker_keys):
+        assert k is None or (k.dtype == torch.int64 and k.is_contiguous() and tuple(k.shape) == (V, Hp, Wp))
+    _call("mvt_overlay_draw", _ptr(prev), _ptr(cur), _ptr(visibility), _ptr(query_frames), _ptr(colors), V, N, M, t, linewidth, Hp, Wp,
+          _ptr(line_keys), _ptr(marker_keys), _stream())
+
+
+def overlay_compose(frames, V, T, t_local, H, W, pad, line_keys, first_segment, marker_keys, out):
+    """out[:, t_local] of (V, T, 3, H + 2 pad, W + 2 pad) uint8 <- markers over the lines of segments >= first_segment over
+    frames[:, t_local] of (V, T, 3, H, W) uint8 or fp32 over the white border; marker_keys is zero again afterwards."""
+    Hp, Wp = H + 2 * pad, W + 2 * pad
+    assert frames.dtype in (torch.uint8, torch.float32) and frames.is_contiguous() and tuple(frames.shape) == (V, T, 3, H, W)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (V, T, 3, Hp, Wp)
+    for k in (line_keys, marker_keys):
+        assert k is None or (k.dtype == torch.int64 and k.is_contiguous() and tuple(k.shape) == (V, Hp, Wp))
+    _call("mvt_overlay_compose", _ptr(frames), int(frames.dtype == torch.uint8), V, T, t_local, H, W, pad, _ptr(line_keys), first_segment,
+          _ptr(marker_keys), _ptr(out), _stream())

@@ -109,6 +109,7 @@ class EvaluationPredictor(torch.nn.Module):
         self.last_camera_correction = None  # the CameraCorrection of the last forward (None: the cameras went in as they were)
         # the ReprojectionReport of the cameras the last forward tracked with, and of the uncorrected ones when it also aligned them
         self.last_reprojection_report = self.last_reprojection_report_before = None
+        self.last_track_overlay = None  # (video (V,T,3,Hp,Wp) uint8, colors (N,3) uint8) of the last forward with track_overlay
         self.model.eval()
 
     # ---- helpers -------------------------------------------------------------------------
@@ -175,9 +176,17 @@ class EvaluationPredictor(torch.nn.Module):
             depth_cleaning=None,
             camera_alignment=None,
             reprojection_check=None,
+            track_overlay=None,
             **kwargs,
     ):
-        """``reprojection_check``: a ``ReprojectionCheck``: the cameras the tracker is about to use (after depth cleaning and camera
+        """``track_overlay``: a ``TrackOverlay``: after the tracking, the tracks are drawn into every view's frames on the device
+        (``mvtracker_amd.render_track_overlays``) and ``(video, colors)`` is kept as ``last_track_overlay``.  The overlay is drawn
+        on the raw input frames, at the caller's resolution and in the caller's world: ``traj_e`` as returned, the thresholded
+        ``vis_e``, the query frames of ``query_points_3d[..., 0]``, the raw ``intrs`` and the ``extrs`` the tracker used before any
+        normalisation (after ``camera_alignment`` if given).  Nothing the tracker reads is changed; ``save_debug_logs`` stays
+        accepted and ignored.  None: not one launch.  There is no stream form (``open_stream`` takes no overlay): a stream's tracks
+        arrive one window after their frames, so a caller who kept the frames draws them with ``mvtracker_amd.open_track_overlay``.
+        ``reprojection_check``: a ``ReprojectionCheck``: the cameras the tracker is about to use (after depth cleaning and camera
         alignment, before normalisation and resize) are judged by ``mvtracker_amd.reprojection_report`` and the report is kept as
         ``last_reprojection_report``; with ``camera_alignment`` the report of the uncorrected cameras is kept too, as
         ``last_reprojection_report_before``.  Nothing the tracker reads is changed.  None: not one launch.
@@ -204,6 +213,11 @@ class EvaluationPredictor(torch.nn.Module):
         hip.require_device(rgbs)
         dev = rgbs.device
         V, T = num_views, num_frames
+        self.last_track_overlay = None
+        if track_overlay is not None:  # checked before anything is launched; drawn after the tracking, on the raw frames
+            from . import overlay
+            overlay._check(track_overlay)
+            overlay_rgbs, overlay_query_frames = rgbs, query_points_3d[0, :, 0]
         # (uint8 frames stay uint8 unless they have to be resized: the encoder's first kernel converts them)
         if not (rgbs.dtype == torch.uint8 and self.interp_shape is None):
             rgbs = rgbs.to(torch.float32)
@@ -233,6 +247,8 @@ class EvaluationPredictor(torch.nn.Module):
                 self.last_reprojection_report_before = reproject.reprojection_report(rgbs, depths, intrs, extrs_uncorrected, reprojection_check,
                                                                                      depths_conf=depths_conf)
             self.last_reprojection_report = reproject.reprojection_report(rgbs, depths, intrs, extrs, reprojection_check, depths_conf=depths_conf)
+        if track_overlay is not None:  # the caller's cameras: before the normalisation and the resize
+            overlay_intrs, overlay_extrs = intrs, extrs
         # scene normalisation, from the raw inputs (a nearest resize with rescaled intrinsics keeps world points); the support
         # points below are built from the transformed depths and cameras, so they need nothing of their own
         xf = self._scene_transform(scene_transform, (depths, intrs, extrs, depths_conf))
@@ -380,6 +396,9 @@ class EvaluationPredictor(torch.nn.Module):
             self.last_nan = False
         if xf is not None:
             traj_e = xf.restore_tracks(traj_e)
+        if track_overlay is not None:
+            self.last_track_overlay = overlay.render_track_overlays(overlay_rgbs[0], traj_e[0], vis_e[0] > self.visibility_threshold, overlay_query_frames,
+                                                                    overlay_intrs[0], overlay_extrs[0], track_overlay)
         return {"traj_e": traj_e, "vis_e": vis_e > self.visibility_threshold, "vis_e_as_prob": vis_e}
 
     @staticmethod
