@@ -4,6 +4,7 @@ its remote pieces (torch.hub / HuggingFace downloads, Rerun logging, depth estim
 
     python demo_amd.py --sample-path data_sample.npz --checkpoint mvtracker_200000_june2025.pth --save-npz tracks.npz
     python demo_amd.py --synthetic --precision bf16            # seeded synthetic clip, seeded random weights (no files needed)
+    python demo_amd.py --synthetic --query-masks bands --per-mask-tracking --print-masks   # queries per segmented object, tracked apart
 
 Mirrors reference demo.py: sample layout :650, 922-929; temporal / spatial subsampling :905-944 (``--temporal_stride``,
 ``--spatial_downsample``); ``--random_query_points`` :967-993 (512 queries drawn from the depth of frame 0 inside a cylinder);
@@ -66,6 +67,21 @@ def build_parser():
     ap.add_argument("--query-motion-radius", type=int, default=None, metavar="R", help="a pixel moves when one within R pixels does (default 7)")
     ap.add_argument("--query-motion-thresh", type=float, default=None, metavar="D",
                     help="channel-mean frame difference from which a pixel moves, in the frames' own units (default 10, for 0..255 frames)")
+    ap.add_argument("--query-masks", default=None, metavar="KEY",
+                    help="queries on segmented objects (mvtracker_amd.mask_queries): KEY names the (V, T, H, W) label map (0 = background, "
+                         "1..255 a camera's instance ids) or the (I, V, T, H, W) stack of boolean instance masks in the sample NPZ; with "
+                         "--synthetic any KEY gives depth bands per view")
+    ap.add_argument("--mask-frames-before", type=int, default=None, metavar="N", help="frames before an object's anchor frame (default 3)")
+    ap.add_argument("--mask-frames-after", type=int, default=None, metavar="N", help="frames after it (default 1)")
+    ap.add_argument("--mask-anchor", default=None, metavar="first|INT", help="an object's first frame with a valid pixel (default) or one frame for all")
+    ap.add_argument("--mask-distance-threshold", type=float, default=None, metavar="D",
+                    help="two cameras' ids are one object when their mean centroid distance is below D (default 0.15, in the clip's units)")
+    ap.add_argument("--mask-no-match", action="store_true", help="the label ids are global already: label l is object l - 1 in every camera")
+    ap.add_argument("--mask-max-points", type=int, default=256, metavar="N", help="query points per object and frame")
+    ap.add_argument("--mask-method", choices=["random", "kmeans"], default=None, help="how a larger pool is cut to --mask-max-points (default random)")
+    ap.add_argument("--per-mask-tracking", action="store_true",
+                    help="track every object's queries as a query set of its own (EvaluationPredictor.forward(query_groups=...))")
+    ap.add_argument("--print-masks", action="store_true", help="print the mask query report (matching table, frames, pools, rows)")
     ap.add_argument("--print-motion", action="store_true",
                     help="print the clip's motion report (static share per view and frame, mean frame differences) and its static "
                          "prefix: the leading frames before anything moves (the reference demo's _detect_static_prefix_frames)")
@@ -209,6 +225,53 @@ def query_motion_from_args(args):
         raise SystemExit(str(e)) from None
 
 
+def query_masks_from_args(args):
+    """The MaskQueries of --query-masks and the --mask-* flags, or None."""
+    details = (args.mask_frames_before, args.mask_frames_after, args.mask_anchor, args.mask_distance_threshold, args.mask_method)
+    if args.query_masks is None:
+        if any(d is not None for d in details) or args.mask_no_match or args.per_mask_tracking or args.print_masks:
+            raise SystemExit("--mask-* flags, --per-mask-tracking and --print-masks need --query-masks")
+        return None
+    if args.sample_queries is not None or args.random_query_points:
+        raise SystemExit("--query-masks replaces --sample-queries / --random-query-points: give one of them")
+    if args.per_mask_tracking and (args.streaming or args.single_point or args.backward_tracking):
+        raise SystemExit("--per-mask-tracking runs in joint mode only (no --streaming, --single-point or --backward-tracking)")
+    from mvtracker_amd import MaskQueries
+    kw = {k: v for k, v in zip(("frames_before", "frames_after", "anchor", "distance_threshold", "method"), details) if v is not None}
+    if "anchor" in kw and kw["anchor"] != "first":
+        try:
+            kw["anchor"] = int(kw["anchor"])
+        except ValueError:
+            raise SystemExit(f"--mask-anchor must be 'first' or a frame number, got {kw['anchor']!r}") from None
+    try:
+        return MaskQueries(match=not args.mask_no_match, max_points_per_frame=args.mask_max_points, **kw)
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+
+
+def mask_labels(args, s):
+    """The label map of --query-masks: from the sample NPZ, or (--synthetic) three depth bands per view, numbered from the far band
+    in odd views so that the cameras' ids differ."""
+    if args.synthetic:
+        d = s["depths"][0, :, :, 0]
+        lab = torch.bucketize(d, torch.tensor([0.5, 2.5, 3.5, 4.5], device=d.device)).clamp(max=4) % 4
+        lab[1::2] = torch.where(lab[1::2] > 0, 4 - lab[1::2], lab[1::2])
+        return lab.to(torch.uint8)
+    with np.load(args.sample_path) as z:
+        if args.query_masks not in z:
+            raise SystemExit(f"--query-masks: no array {args.query_masks!r} in {args.sample_path}")
+        m = torch.from_numpy(z[args.query_masks])
+    st = args.temporal_stride
+    if m.dtype == torch.bool:
+        from mvtracker_amd import labels_from_instances
+        m = labels_from_instances(m[:, :, ::st] if m.dim() == 5 else m[None, :, ::st])
+    else:
+        m = (m[0] if m.dim() == 5 else m)[:, ::st]
+    if args.spatial_downsample > 1:
+        m = m[..., ::args.spatial_downsample, ::args.spatial_downsample]
+    return m.to(s["depths"].device)
+
+
 def track_overlay_from_args(args):
     """The TrackOverlay of --save-overlay and the --overlay-* flags, or None."""
     names = ("trail", "linewidth", "pad", "min_depth", "max_tracks")
@@ -250,6 +313,7 @@ def main():
     track_overlay = track_overlay_from_args(args)
     region, region_poses = query_region_from_args(args, args.temporal_stride)  # (flag errors before any work)
     motion, motion_keep = query_motion_from_args(args)
+    mask_options = query_masks_from_args(args)
     if not torch.cuda.is_available():
         raise SystemExit("demo_amd.py needs an MI355X: the tracker has no CPU path")
     from mvtracker_amd import sample_io, synth
@@ -325,6 +389,14 @@ def main():
             print(report.table())
         for report in motion_reports.values():
             print(f"query motion ({motion_keep} pixels):", report.summary())
+    elif mask_options is not None:
+        from mvtracker_amd import mask_queries
+        s["query_points_3d"], object_ids, report = mask_queries(mask_labels(args, s), s["depths"], s["intrs"], s["extrs"], mask_options,
+                                                                depths_conf=s.get("depths_conf") if mask_options.conf_thresh is not None else None)
+        print("mask queries:", report.summary())
+        if args.print_masks:
+            print(report.matching.table())
+            print(report.table())
     elif args.random_query_points or s["query_points_3d"].shape[1] == 0:
         s["query_points_3d"] = random_queries(s["depths"].float(), s["intrs"], s["extrs"])
     xf = None
@@ -336,7 +408,7 @@ def main():
     V, T = s["rgbs"].shape[1:3]
     print(f"clip: {V} views x {T} frames x {tuple(s['rgbs'].shape[-2:])}, {s['query_points_3d'].shape[1]} queries, precision {args.precision}")
     call = lambda: predictor(rgbs=s["rgbs"], depths=s["depths"], intrs=s["intrs"], extrs=s["extrs"], query_points_3d=s["query_points_3d"],
-                             scene_transform=xf, depth_cleaning=cleaning)
+                             scene_transform=xf, depth_cleaning=cleaning, query_groups=object_ids if args.per_mask_tracking else None)
     if args.streaming:
         if args.block_frames < 1:
             raise SystemExit("--block-frames must be at least 1")
@@ -364,6 +436,10 @@ def main():
         print("saved", args.save_npz)
     if track_overlay is not None:  # after the timed call, from what it returned: the streaming path has the same tracks
         from mvtracker_amd import render_track_overlays
+        if mask_options is not None:  # one colour per object
+            import dataclasses
+            from mvtracker_amd import object_colors
+            track_overlay = dataclasses.replace(track_overlay, colors=object_colors(object_ids))
         video, _ = render_track_overlays(s["rgbs"][0], out["traj_e"][0], out["vis_e"][0], s["query_points_3d"][0, :, 0], s["intrs"][0], s["extrs"][0],
                                          track_overlay)
         files = save_overlay(video, args.save_overlay)

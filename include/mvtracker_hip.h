@@ -1099,6 +1099,45 @@ int mvt_overlay_draw(const int* prev, const int* cur, const unsigned char* visib
 int mvt_overlay_compose(const void* frames, int is_u8, int V, int T, int t_local, int H, int W, int pad, const unsigned long long* line_keys,
                         int first_segment, unsigned long long* marker_keys, unsigned char* out, void* stream);
 
+/* ---- mask queries (csrc/mask_queries.hip; mvtracker_amd/masks.py drives these; DESIGN section 8 "Mask queries") ----
+ * labels (V, T, H, W), one byte per pixel: 0 = background, 1..255 a camera's local instance ids; the pointer is 16-byte aligned.
+ * depths / conf (V, T, 1, H, W) fp32 (conf may be NULL), kinv [V*T][9], einv [V*T][12] as mvt_query_pool takes them.
+ * A labelled pixel is VALID when its depth is finite, min_depth < depth <= max_depth (fp32 comparisons) and, with conf,
+ * conf > conf_thresh.  Its world point is mvt_query_pool's (the same unprojection at stride 1).
+ * Limits: V <= MVT_MASK_MAX_VIEWS, V * T <= 65535, H * W <= 2^24, V * H * W < 2^31; anything else: MVT_ERR_ARG before any launch.
+ * Everything summed is an integer: the same bits in every run. */
+#define MVT_MASK_LABELS 256
+#define MVT_MASK_MAX_LABEL 255
+#define MVT_MASK_MAX_VIEWS 64
+#define MVT_MASK_FRAC_BITS 20   /* fixed point of the coordinate sums: q = (int64) rint((double) x * 2^20) */
+#define MVT_MASK_RANGE_BITS 18  /* a valid point with a non-finite coordinate or |coordinate| >= 2^18 is left out and counted */
+#define MVT_MASK_STAT_WORDS 6   /* int64 words per (view, frame, label): */
+#define MVT_MASK_PIXELS 0       /*   labelled pixels */
+#define MVT_MASK_COUNT 1        /*   valid pixels whose point is in range: the terms of the sums */
+#define MVT_MASK_SUM 2          /*   .. 4: fixed-point sums of x, y, z */
+#define MVT_MASK_OUT_OF_RANGE 5 /*   valid pixels left out of the sums */
+/* stats (V, T, 256, MVT_MASK_STAT_WORDS) int64, 16-byte aligned, cleared here, then one pass over the clip.  Row 0 of every image
+ * stays zero. */
+int mvt_mask_stats(const unsigned char* labels, const float* depths, const float* conf, const float* kinv, const float* einv, int V, int T,
+                   int H, int W, float min_depth, float max_depth, float conf_thresh, long long* stats, void* stream);
+/* centroid (V, T, 256, 3) fp64 <- (double) sum / (double) count * 2^-20 where count >= min_pixels (>= 1), NaN elsewhere. */
+int mvt_mask_centroids(const long long* stats, int V, int T, int min_pixels, double* centroid, void* stream);
+/* The greedy "average distance" matching on the centroids.  global_id (V, 256) int32 <- the object of every (view, label), -1 where
+ * it has no centroid in any frame; distance (V, 256) fp64 <- the distance it joined its object at, NaN where it opened a new one;
+ * state int32[2] <- (objects, present ids); ids: workspace of V * 256 int32.  match == 0: label l is object l - 1 in every view,
+ * objects = the largest present label. */
+int mvt_mask_match(const double* centroid, int V, int T, int min_common_frames, double distance_threshold, int match, int* ids,
+                   int* global_id, double* distance, int* state, void* stream);
+/* out (V, T, H, W) int32 <- table[v][label], -1 for background; table (V, 256) int32; out is 16-byte aligned. */
+int mvt_mask_relabel(const unsigned char* labels, const int* table, int V, int T, int H, int W, int* out, void* stream);
+/* The pool of (object, frame t): the valid pixels of frame t whose table[v][label] == object, in raster order (view, row, column):
+ * pool (capacity, 3) fp32 <- their world points, pixel (capacity) int32 <- their raster index (v * H + y) * W + x, count <- how many
+ * there are (rows beyond capacity are counted, not written).  block_counts: workspace of ceil(V * H * W / 256) int32.  Count, scan,
+ * scatter as mvt_query_pool; the clip is read in place. */
+int mvt_mask_pool(const unsigned char* labels, const float* depths, const float* conf, const float* kinv, const float* einv, int V, int T,
+                  int t, int H, int W, float min_depth, float max_depth, float conf_thresh, const int* table, int object, int capacity,
+                  float* pool, int* pixel, int* count, int* block_counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

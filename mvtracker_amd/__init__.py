@@ -1,6 +1,6 @@
 """MI355X-native multi-view point-tracking forward path (drop-in for mvtracker.models' predictor).
 
-    from mvtracker_amd import MVTracker, EvaluationPredictor, load_mvtracker, sample_queries, auto_scene_normalization, DepthCleaning, clean_depths, CameraAlignment, align_cameras, estimate_normals, voxel_downsample, ReprojectionCheck, reprojection_report, RegionCluster, region_masks, cluster_points, MotionMask, motion_masks, TrackOverlay, render_track_overlays
+    from mvtracker_amd import MVTracker, EvaluationPredictor, load_mvtracker, sample_queries, auto_scene_normalization, DepthCleaning, clean_depths, CameraAlignment, align_cameras, estimate_normals, voxel_downsample, ReprojectionCheck, reprojection_report, RegionCluster, region_masks, cluster_points, MotionMask, motion_masks, TrackOverlay, render_track_overlays, MaskQueries, mask_queries
 
 ``synth`` (numpy only) can be imported without the HIP library; everything else loads
 libmvtracker_hip.so on import and raises if it is missing -- there is no CPU fallback.
@@ -11,7 +11,9 @@ __all__ = ["MVTracker", "EvaluationPredictor", "load_mvtracker", "hip", "synth",
            "estimate_normals", "voxel_downsample", "reproject", "ReprojectionCheck", "ReprojectionReport", "reprojection_report", "reproject_views",
            "render_point_cloud", "compare_reports", "cluster", "RegionCluster", "RegionReport", "cluster_points", "select_region_points",
            "region_masks", "motion", "MotionMask", "MotionReport", "motion_masks", "overlay", "TrackOverlay", "TrackOverlaySession", "project_tracks",
-           "render_track_overlays", "open_track_overlay", "stack_views"]
+           "render_track_overlays", "open_track_overlay", "stack_views", "masks", "MaskQueries", "MaskStatistics", "MaskMatching",
+           "MaskQueryReport", "labels_from_instances", "mask_statistics", "match_mask_ids", "global_masks", "lift_masks", "mask_queries",
+           "object_colors"]
 
 
 def __getattr__(name):
@@ -51,7 +53,11 @@ def __getattr__(name):
     if name in ("TrackOverlay", "TrackOverlaySession", "project_tracks", "render_track_overlays", "open_track_overlay", "stack_views"):
         from . import overlay
         return getattr(overlay, name)
-    if name in ("hip", "synth", "sample_io", "adapter", "geometry", "parallel", "queries", "scene", "clean", "align", "cloud", "reproject", "cluster", "motion", "overlay"):
+    if name in ("MaskQueries", "MaskStatistics", "MaskMatching", "MaskQueryReport", "labels_from_instances", "mask_statistics", "match_mask_ids",
+                "global_masks", "lift_masks", "mask_queries", "object_colors"):
+        from . import masks
+        return getattr(masks, name)
+    if name in ("hip", "synth", "sample_io", "adapter", "geometry", "parallel", "queries", "scene", "clean", "align", "cloud", "reproject", "cluster", "motion", "overlay", "masks"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -136,6 +136,11 @@ SIGNATURES = {
     "mvt_overlay_project": [P, P, P, I, I, I, P, P, I, I, F, P, I, P, I, I, P, P],
     "mvt_overlay_draw": [P, P, P, P, P, I, I, I, I, I, I, I, P, P, P],
     "mvt_overlay_compose": [P, I, I, I, I, I, I, I, P, I, P, P, P],
+    "mvt_mask_stats": [P, P, P, P, P, I, I, I, I, F, F, F, P, P],
+    "mvt_mask_centroids": [P, I, I, I, P, P],
+    "mvt_mask_match": [P, I, I, I, C.c_double, I, P, P, P, P, P],
+    "mvt_mask_relabel": [P, P, I, I, I, I, P, P],
+    "mvt_mask_pool": [P, P, P, P, P, I, I, I, I, I, F, F, F, P, I, I, P, P, P, P, P],
 }
 _RET = {"mvt_build_arch": C.c_char_p, "mvt_encoder_workspace_bytes": C.c_longlong, "mvt_updateformer_workspace_bytes": C.c_longlong,
         "mvt_updateformer_grouped_workspace_bytes": C.c_longlong}
@@ -1298,3 +1303,64 @@ def overlay_compose(frames, V, T, t_local, H, W, pad, line_keys, first_segment, 
         assert k is None or (k.dtype == torch.int64 and k.is_contiguous() and tuple(k.shape) == (V, Hp, Wp))
     _call("mvt_overlay_compose", _ptr(frames), int(frames.dtype == torch.uint8), V, T, t_local, H, W, pad, _ptr(line_keys), first_segment,
           _ptr(marker_keys), _ptr(out), _stream())
+
+
+# ------------------------------------------------------------------ mask queries (mvtracker_amd/masks.py drives these)
+MASK_LABELS, MASK_MAX_LABEL, MASK_MAX_VIEWS, MASK_FRAC_BITS, MASK_RANGE_BITS = 256, 255, 64, 20, 18  # MVT_MASK_*
+MASK_STAT_WORDS, MASK_PIXELS, MASK_COUNT, MASK_SUM, MASK_OUT_OF_RANGE = 6, 0, 1, 2, 5
+
+
+def _mask_clip_check(labels, depths, conf, kinv, einv, V, T, H, W):
+    assert labels.dtype == torch.uint8 and labels.is_contiguous() and tuple(labels.shape) == (V, T, H, W)
+    assert depths.dtype == torch.float32 and depths.is_contiguous() and depths.numel() == V * T * H * W
+    assert conf is None or (conf.dtype == torch.float32 and conf.is_contiguous() and conf.numel() == V * T * H * W)
+    assert _f32c(kinv).numel() == V * T * 9 and _f32c(einv).numel() == V * T * 12
+
+
+def mask_stats(labels, depths, conf, kinv, einv, V, T, H, W, min_depth, max_depth, conf_thresh, stats):
+    """stats (V, T, 256, MASK_STAT_WORDS) int64 <- per (view, frame, label): labelled pixels, valid pixels in range, their
+    fixed-point coordinate sums, valid pixels out of range.  labels (V, T, H, W) uint8; conf_thresh is read only with ``conf``."""
+    _mask_clip_check(labels, depths, conf, kinv, einv, V, T, H, W)
+    assert stats.dtype == torch.int64 and stats.is_contiguous() and stats.numel() == V * T * MASK_LABELS * MASK_STAT_WORDS
+    _call("mvt_mask_stats", _ptr(labels), _ptr(depths), _ptr(conf), _ptr(kinv), _ptr(einv), V, T, H, W, min_depth, max_depth,
+          0.0 if conf is None else conf_thresh, _ptr(stats), _stream())
+
+
+def mask_centroids(stats, V, T, min_pixels, centroid):
+    """centroid (V, T, 256, 3) fp64 <- sum / count * 2^-20 where count >= min_pixels, NaN elsewhere."""
+    assert stats.dtype == torch.int64 and stats.is_contiguous() and stats.numel() == V * T * MASK_LABELS * MASK_STAT_WORDS
+    assert centroid.dtype == torch.float64 and centroid.is_contiguous() and centroid.numel() == V * T * MASK_LABELS * 3
+    _call("mvt_mask_centroids", _ptr(stats), V, T, min_pixels, _ptr(centroid), _stream())
+
+
+def mask_match(centroid, V, T, min_common_frames, distance_threshold, match, ids, global_id, distance, state):
+    """global_id (V, 256) int32, distance (V, 256) fp64, state (2,) int32 = (objects, present ids) <- the greedy matching of the
+    centroids (V, T, 256, 3); ids: workspace (V * 256,) int32."""
+    assert centroid.dtype == torch.float64 and centroid.is_contiguous() and centroid.numel() == V * T * MASK_LABELS * 3
+    for a, n in ((ids, V * MASK_LABELS), (global_id, V * MASK_LABELS), (state, 2)):
+        assert a.dtype == torch.int32 and a.is_contiguous() and a.numel() == n
+    assert distance.dtype == torch.float64 and distance.is_contiguous() and distance.numel() == V * MASK_LABELS
+    _call("mvt_mask_match", _ptr(centroid), V, T, min_common_frames, distance_threshold, int(bool(match)), _ptr(ids), _ptr(global_id),
+          _ptr(distance), _ptr(state), _stream())
+
+
+def mask_relabel(labels, table, V, T, H, W, out):
+    """out (V, T, H, W) int32 <- table[v][label], -1 for background; table (V, 256) int32."""
+    assert labels.dtype == torch.uint8 and labels.is_contiguous() and tuple(labels.shape) == (V, T, H, W)
+    assert table.dtype == torch.int32 and table.is_contiguous() and table.numel() == V * MASK_LABELS
+    assert out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (V, T, H, W)
+    _call("mvt_mask_relabel", _ptr(labels), _ptr(table), V, T, H, W, _ptr(out), _stream())
+
+
+def mask_pool(labels, depths, conf, kinv, einv, V, T, t, H, W, min_depth, max_depth, conf_thresh, table, obj, pool, pixel, count, block_counts):
+    """The pool of (object ``obj``, frame t): pool (capacity, 3) fp32 <- world points, pixel (capacity,) int32 <- raster indices, in
+    raster order; count (1,) int32 <- the pool's size.  Nothing is written past ``capacity = len(pixel)`` rows."""
+    _mask_clip_check(labels, depths, conf, kinv, einv, V, T, H, W)
+    assert table.dtype == torch.int32 and table.is_contiguous() and table.numel() == V * MASK_LABELS
+    capacity = pixel.numel()
+    assert pool.dtype == torch.float32 and pool.is_contiguous() and pool.numel() == capacity * 3
+    assert pixel.dtype == torch.int32 and pixel.is_contiguous() and count.dtype == torch.int32 and count.numel() >= 1
+    assert block_counts.dtype == torch.int32 and block_counts.numel() >= (V * H * W + 255) // 256
+    _call("mvt_mask_pool", _ptr(labels), _ptr(depths), _ptr(conf), _ptr(kinv), _ptr(einv), V, T, t, H, W, min_depth, max_depth,
+          0.0 if conf is None else conf_thresh, _ptr(table), obj, capacity, _ptr(pool) if capacity else None, _ptr(pixel) if capacity else None,
+          _ptr(count), _ptr(block_counts), _stream())

@@ -153,6 +153,22 @@ class EvaluationPredictor(torch.nn.Module):
             return scene.auto_scene_normalization(depths, intrs, extrs, depths_conf=conf)
         raise ValueError(f'scene_transform must be None, a SceneTransform or "auto", got {scene_transform!r}')
 
+    def _query_groups(self, query_groups, num_points):
+        """``forward``'s ``query_groups`` -> the caller rows of every distinct id, in ascending id order."""
+        import numpy as np
+        if self.single_point:
+            raise NotImplementedError("query_groups with single_point: every query is a forward of its own there (group them with "
+                                      "single_point_group_size)")
+        if self.backward_tracking:
+            raise NotImplementedError("query_groups with backward_tracking: forward_grouped has no backward tracking")
+        if not hasattr(self.model, "forward_grouped"):
+            raise NotImplementedError("query_groups needs a model with forward_grouped")
+        ids = torch.as_tensor(query_groups)
+        if ids.dim() != 1 or ids.dtype.is_floating_point or ids.dtype == torch.bool or ids.shape[0] != num_points or num_points == 0:
+            raise ValueError(f"query_groups must be ({num_points},) integers, one per query, got {tuple(ids.shape)} {ids.dtype}")
+        ids = ids.cpu().numpy()
+        return [np.nonzero(ids == g)[0] for g in np.unique(ids)]
+
     def _support_rows(self, depth, pix, kinv, einv, t):
         z = _bilinear_sample_depth(depth, pix[:, 0], pix[:, 1])
         world = self._unproject(pix, z, kinv, einv)
@@ -177,9 +193,15 @@ class EvaluationPredictor(torch.nn.Module):
             camera_alignment=None,
             reprojection_check=None,
             track_overlay=None,
+            query_groups=None,
             **kwargs,
     ):
-        """``track_overlay``: a ``TrackOverlay``: after the tracking, the tracks are drawn into every view's frames on the device
+        """``query_groups``: (N,) integers, one per query (``mask_queries``' ``object_ids``): in joint mode the queries of every
+        distinct id, in ascending id order, are a query set of their own -- [its queries; the support rows] -- and all sets go
+        through ``MVTracker.forward_grouped``: per-object independent tracking in one encoder pass and one launch sequence, the
+        results scattered back to the caller's rows.  Refused with ``single_point``, ``backward_tracking`` and a model without
+        ``forward_grouped``.  None: the joint forward as it always was.
+        ``track_overlay``: a ``TrackOverlay``: after the tracking, the tracks are drawn into every view's frames on the device
         (``mvtracker_amd.render_track_overlays``) and ``(video, colors)`` is kept as ``last_track_overlay``.  The overlay is drawn
         on the raw input frames, at the caller's resolution and in the caller's world: ``traj_e`` as returned, the thresholded
         ``vis_e``, the query frames of ``query_points_3d[..., 0]``, the raw ``intrs`` and the ``extrs`` the tracker used before any
@@ -210,6 +232,7 @@ class EvaluationPredictor(torch.nn.Module):
             raise NotImplementedError
         if self.sift_size > 0:
             raise NotImplementedError
+        groups = None if query_groups is None else self._query_groups(query_groups, num_points)  # (refused before any launch)
         hip.require_device(rgbs)
         dev = rgbs.device
         V, T = num_views, num_frames
@@ -380,6 +403,15 @@ class EvaluationPredictor(torch.nn.Module):
                     nan_flags.append(getattr(self.model, "last_nan_flag", None))
             for s_ in streams:
                 main.wait_stream(s_)
+        elif groups is not None:  # joint mode per group: every id's queries with the support rows, one grouped forward
+            traj_e = torch.zeros(1, T, num_points, 3, device=dev)
+            vis_e = torch.zeros(1, T, num_points, device=dev)
+            rows = [torch.from_numpy(g).to(dev) for g in groups]
+            qs = [torch.cat([query_points_3d[0, r], support], 0)[None] for r in rows]
+            for r, res in zip(rows, self.model.forward_grouped(rgbs, depths, qs, **fwd)):
+                traj_e[:, :, r] = res["traj_e"][:, :, :len(r)]
+                vis_e[:, :, r] = res["vis_e"][:, :, :len(r)]
+            nan_flags.append(getattr(self.model, "last_nan_flag", None))
         else:  # joint mode, :341-360
             q = torch.cat([query_points_3d[0], support], 0)[None]
             res = self.model(rgbs, depths=depths, query_points=q, **fwd)
@@ -411,6 +443,14 @@ class EvaluationPredictor(torch.nn.Module):
         what moves (or on the static background)."""
         from . import queries
         return queries.sample_queries(depths, intrs, extrs, queries.DEFAULT_SPEC if spec is None else spec, **kw)
+
+    @staticmethod
+    def mask_queries(labels, depths, intrs, extrs, options=None, **kw):
+        """Query points per segmented object (``mvtracker_amd.masks.mask_queries``): ``(query_points (1, N, 4), object_ids (N,),
+        report)`` from per-camera instance masks; ``forward(query_points_3d=query_points, query_groups=object_ids)`` then tracks
+        every object on its own."""
+        from . import masks
+        return masks.mask_queries(labels, depths, intrs, extrs, masks.MaskQueries() if options is None else options, **kw)
 
     def open_stream(self, query_points_3d, ring_blocks=3, scene_transform=None, depth_cleaning=None):
         """Streaming form of ``forward`` in joint mode (``MVTracker.open_stream``): returns a session whose
