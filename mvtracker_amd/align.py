@@ -22,6 +22,7 @@ import math
 import torch
 
 from . import hip
+from .clip import MAX_POINTS, DepthClip, list_cloud
 
 
 class CameraAlignment:
@@ -206,38 +207,23 @@ class ClipAlignment:
 
     def __init__(self, depths, intrs, extrs, alignment, depths_conf=None):
         a = self.alignment = _check(alignment)
-        if depths.dim() != 5 or depths.shape[2] != 1:
-            raise ValueError(f"depths must be (V, T, 1, H, W), got {tuple(depths.shape)}")
-        V, T, _, H, W = depths.shape
-        if tuple(intrs.shape) != (V, T, 3, 3) or tuple(extrs.shape) != (V, T, 3, 4):
-            raise ValueError(f"intrs / extrs must be ({V}, {T}, 3, 3) / ({V}, {T}, 3, 4), got {tuple(intrs.shape)} / {tuple(extrs.shape)}")
-        if depths_conf is not None and tuple(depths_conf.shape) != tuple(depths.shape):
-            raise ValueError(f"depths_conf must have the shape of depths, got {tuple(depths_conf.shape)}")
+        clip = DepthClip(depths, intrs, extrs, depths_conf)
+        V, T, dev = clip.V, clip.T, clip.dev
         if not 2 <= V <= hip.ALIGN_MAX_TARGETS + 1:
             raise ValueError(f"camera alignment takes 2..{hip.ALIGN_MAX_TARGETS + 1} views, got {V}")
         if a.anchor >= V:
             raise ValueError(f"anchor {a.anchor} is not one of the {V} views")
         if max(a.frames) >= T:
             raise ValueError(f"frames {a.frames} reach past the clip's {T} frames")
-        hip.require_device(depths)
-        dev = depths.device
-        Hp, Wp = (H + 7) // 8 * 8, (W + 7) // 8 * 8
-        P, F = Hp * Wp, len(a.frames)
-        if V * P >= (1 << 31) - 64:
+        Hp, Wp, P = clip.padded_grid()
+        F = len(a.frames)
+        if V * P >= MAX_POINTS:
             raise ValueError(f"{V} clouds of {Hp} x {Wp} points are too large (the limit is 2^31 target points)")
-        d = depths.to(torch.float32).contiguous()
-        conf = None if (depths_conf is None or a.conf_thresh is None) else depths_conf.to(torch.float32).contiguous()
-        kinv = torch.empty(V * T, 9, device=dev)
-        einv = torch.empty(V * T, 12, device=dev)
-        hip.invert_cameras(intrs.to(torch.float32).reshape(V * T, 9).contiguous(), extrs.to(torch.float32).reshape(V * T, 12).contiguous(), kinv,
-                           einv, V * T)
         self.V, self.F, self.P, self.grid = V, F, P, (Wp, Hp)
         nt = P // 64
         self.xyz0 = torch.empty(V, F, P, 4, device=dev)
-        one = torch.empty(V, P, 4, device=dev)
         for fi, t in enumerate(a.frames):
-            hip.clean_points(d, conf, kinv, einv, V, T, t, 1, H, W, a.conf_thresh, None, one)
-            self.xyz0[:, fi] = one
+            self.xyz0[:, fi] = clip.clouds(t, 1, a.conf_thresh)
         self.xyz = self.xyz0.clone()  # (D = identity: the same bits)
         self.nrm = torch.empty(V, F, P, 4, device=dev)
         self.box = torch.empty(V, F, nt, 8, device=dev)
@@ -292,27 +278,7 @@ def align_cameras(depths, intrs, extrs, alignment, depths_conf=None):
     each other view v, in view order, is aligned by point-to-plane ICP onto the union of all other views as they stand at that
     moment (their current corrections applied), after which its clouds are moved and its boxes and normals rebuilt.  There is one
     rigid correction per view for the whole clip.  Returns a ``CameraCorrection``; the inputs are not written."""
-    batched = depths.dim() == 6
-    if batched and depths.shape[0] != 1:
-        raise ValueError(f"depths must be (V, T, 1, H, W) or (1, V, T, 1, H, W), got {tuple(depths.shape)}")
-    if batched and (intrs.dim() != 5 or extrs.dim() != 5 or (depths_conf is not None and depths_conf.dim() != 6)):
-        raise ValueError("intrs, extrs and depths_conf must have the leading batch dimension of depths")
-    sq = (lambda t: None if t is None else t[0]) if batched else (lambda t: t)
-    return align_clip(sq(depths), sq(intrs), sq(extrs), alignment, sq(depths_conf))
-
-
-def _list_cloud(points, what):
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"{what} must be (M, 3), got {tuple(points.shape)}")
-    M = points.shape[0]
-    if M == 0:
-        raise ValueError(f"{what} is empty")
-    if M >= (1 << 31) - 64:
-        raise ValueError(f"{M} points are too many (the limit is 2^31 per launch)")
-    p = points.to(torch.float32)
-    out = torch.zeros(1, M, 4, device=points.device)
-    out[0, :, :3] = torch.where(torch.isfinite(p).all(1, keepdim=True), p, torch.full((), float("nan"), device=points.device))
-    return out
+    return align_clip(depths, intrs, extrs, alignment, depths_conf)
 
 
 def list_problem(source, target, target_normals, max_distance, max_iterations, init=None, keep_queries=False, normal_radius=0.05,
@@ -323,20 +289,19 @@ def list_problem(source, target, target_normals, max_distance, max_iterations, i
         raise ValueError(f"max_distance must be finite and positive, got {max_distance!r}")
     if int(max_iterations) != max_iterations or not 1 <= int(max_iterations) <= 1000:
         raise ValueError(f"max_iterations must be an integer in 1..1000, got {max_iterations!r}")
-    src = _list_cloud(source, "source")
-    tgt = _list_cloud(target, "target")
+    src = list_cloud(source, "source")
+    tgt = list_cloud(target, "target")
     if target_normals is None:
         cloud.check_normal_search(normal_radius, normal_max_nn)
     elif tuple(target_normals.shape) != tuple(target.shape):
         raise ValueError(f"target_normals must have the shape of target, got {tuple(target_normals.shape)}")
     if init is not None and tuple(init.shape) != (4, 4):
         raise ValueError(f"init must be (4, 4), got {tuple(init.shape)}")
-    hip.require_device(source)
     dev = source.device
     M, N = source.shape[0], target.shape[0]
     if target_normals is None:
         target_normals = cloud.estimate_normals(target, normal_radius, normal_max_nn)
-    nrm = _list_cloud(target_normals, "target_normals")
+    nrm = list_cloud(target_normals, "target_normals")
     box, gbox = hip.cloud_boxes(tgt, 1, N, (0, 0))
     D = _eye_rows(1, dev)[0] if init is None else _rows12(init.to(device=dev, dtype=torch.float64))
     return IcpRun(src, M, (0, 0), 1, [dict(xyz=tgt, nrm=nrm, box=box, gbox=gbox, P=N, grid=(0, 0))], max_distance, 1, D, int(max_iterations),

@@ -17,6 +17,7 @@ import math
 import torch
 
 from . import hip
+from .clip import DepthClip, list_cloud
 
 METHODS = ("statistical", "radius")
 MAX_CHUNK_POINTS = 1 << 23  # padded points searched per launch sequence: under 22 bytes of workspace each, 176 MiB in all
@@ -92,46 +93,27 @@ def search_clouds(xyz, n_clouds, n_points, grid, cleaning):
 
 
 def clean_clip(depths, intrs, extrs, cleaning, depths_conf=None, details=False):
-    """``clean_depths`` on a clip (V,T,1,H,W) with cameras (V,T,3,3) / (V,T,3,4): the bool keep mask (V,T,1,H,W); with ``details``
-    also the per-pixel search values (V,T,H,W), the cloud states (V,T,4) and the clouds' points (V,T,H,W,4)."""
+    """``clean_depths`` without the ``where``: the bool keep mask of the shape of ``depths``; with ``details`` also the per-pixel
+    search values (V,T,H,W), the cloud states (V,T,4) and the clouds' points (V,T,H,W,4)."""
     c = _check(cleaning)
-    if depths.dim() != 5 or depths.shape[2] != 1:
-        raise ValueError(f"depths must be (V, T, 1, H, W), got {tuple(depths.shape)}")
-    V, T, _, H, W = depths.shape
-    if tuple(intrs.shape) != (V, T, 3, 3) or tuple(extrs.shape) != (V, T, 3, 4):
-        raise ValueError(f"intrs / extrs must be ({V}, {T}, 3, 3) / ({V}, {T}, 3, 4), got {tuple(intrs.shape)} / {tuple(extrs.shape)}")
-    if depths_conf is not None and tuple(depths_conf.shape) != tuple(depths.shape):
-        raise ValueError(f"depths_conf must have the shape of depths, got {tuple(depths_conf.shape)}")
-    hip.require_device(depths)
-    dev = depths.device
-    d = depths.to(torch.float32).contiguous()
-    conf = None if (depths_conf is None or c.conf_thresh is None) else depths_conf.to(torch.float32).contiguous()
-    kinv = torch.empty(V * T, 9, device=dev)
-    einv = torch.empty(V * T, 12, device=dev)
-    hip.invert_cameras(intrs.to(torch.float32).reshape(V * T, 9).contiguous(), extrs.to(torch.float32).reshape(V * T, 12).contiguous(), kinv, einv,
-                       V * T)
-    Hp, Wp = (H + 7) // 8 * 8, (W + 7) // 8 * 8
-    P = Hp * Wp
-    if P >= (1 << 31) - 64:
-        raise ValueError(f"a cloud of {Hp} x {Wp} points is too large (the limit is 2^31 per launch)")
-    step = max(1, min(T, MAX_CHUNK_POINTS // (V * P), 65535 // V))  # frames per launch sequence: bounded workspace
+    clip = DepthClip(depths, intrs, extrs, depths_conf)
+    V, T, H, W, dev = clip.V, clip.T, clip.H, clip.W, clip.dev
+    Hp, Wp, P = clip.padded_grid()
     keep = torch.empty(V, T, H, W, device=dev, dtype=torch.bool)
     vals = states = pts = None
     if details:
         vals = torch.empty(V, T, H, W, device=dev, dtype=torch.float32 if c.mode == hip.CLEAN_STATISTICAL else torch.int32)
         states = torch.empty(V, T, 4, device=dev, dtype=torch.float64)
         pts = torch.empty(V, T, H, W, 4, device=dev)
-    for t0 in range(0, T, step):
-        nt = min(step, T - t0)
-        xyz = torch.empty(V * nt, P, 4, device=dev)
-        hip.clean_points(d, conf, kinv, einv, V, T, t0, nt, H, W, c.conf_thresh, c.sphere, xyz)
+    for t0, nt in clip.frame_chunks(MAX_CHUNK_POINTS):  # frames per launch sequence: bounded workspace
+        xyz = clip.clouds(t0, nt, c.conf_thresh, c.sphere)
         v_, s_, k_ = search_clouds(xyz, V * nt, P, (Wp, Hp), c)
-        keep[:, t0:t0 + nt] = k_.reshape(V, nt, Hp, Wp)[:, :, :H, :W] != 0
+        keep[:, t0:t0 + nt] = clip.crop(k_, nt) != 0
         if details:
-            vals[:, t0:t0 + nt] = v_.reshape(V, nt, Hp, Wp)[:, :, :H, :W]
+            vals[:, t0:t0 + nt] = clip.crop(v_, nt)
             states[:, t0:t0 + nt] = s_.reshape(V, nt, 4)
-            pts[:, t0:t0 + nt] = xyz.reshape(V, nt, Hp, Wp, 4)[:, :, :H, :W]
-    keep = keep.reshape(V, T, 1, H, W)
+            pts[:, t0:t0 + nt] = clip.crop(xyz, nt)
+    keep = clip.rebatch(keep.reshape(V, T, 1, H, W))
     return (keep, vals, states, pts) if details else keep
 
 
@@ -142,15 +124,7 @@ def clean_depths(depths, intrs, extrs, cleaning, depths_conf=None):
     > 0, its confidence exceeds ``cleaning.conf_thresh`` (both given) and its point lies inside the sphere crop (given); the valid
     pixels of one depth map are one cloud, searched against itself.  Returns ``(depths_clean, keep)``: ``keep`` bool of the shape of
     ``depths`` (False on pixels that are not valid), ``depths_clean = where(keep, depths, 0)``.  The inputs are not written."""
-    batched = depths.dim() == 6
-    if batched and depths.shape[0] != 1:
-        raise ValueError(f"depths must be (V, T, 1, H, W) or (1, V, T, 1, H, W), got {tuple(depths.shape)}")
-    if batched and (intrs.dim() != 5 or extrs.dim() != 5 or (depths_conf is not None and depths_conf.dim() != 6)):
-        raise ValueError("intrs, extrs and depths_conf must have the leading batch dimension of depths")
-    sq = (lambda t: None if t is None else t[0]) if batched else (lambda t: t)
-    keep = clean_clip(sq(depths), sq(intrs), sq(extrs), cleaning, sq(depths_conf))
-    if batched:
-        keep = keep[None]
+    keep = clean_clip(depths, intrs, extrs, cleaning, depths_conf)
     return torch.where(keep, depths, torch.zeros((), dtype=depths.dtype, device=depths.device)), keep
 
 
@@ -159,15 +133,8 @@ def clean_point_cloud(points, cleaning):
     """The reference function's own signature on an unorganised cloud: points (M, 3) on the device -> keep (M,) bool.  Rows with a
     coordinate that is not finite take no part and come back False."""
     c = _check(cleaning)
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"points must be (M, 3), got {tuple(points.shape)}")
-    hip.require_device(points)
+    xyz = list_cloud(points, empty_ok=True)
     M = points.shape[0]
     if M == 0:
         return torch.zeros(0, dtype=torch.bool, device=points.device)
-    if M >= (1 << 31) - 64:
-        raise ValueError(f"{M} points are too many (the limit is 2^31 per launch)")
-    p = points.to(torch.float32)
-    xyz = torch.zeros(1, M, 4, device=points.device)
-    xyz[0, :, :3] = torch.where(torch.isfinite(p).all(1, keepdim=True), p, torch.full((), float("nan"), device=points.device))
     return search_clouds(xyz, 1, M, (0, 0), c)[2][0] != 0

@@ -20,6 +20,7 @@ import math
 import torch
 
 from . import hip
+from .clip import list_cloud
 
 
 def check_normal_search(radius, max_nn):
@@ -29,20 +30,6 @@ def check_normal_search(radius, max_nn):
     if int(max_nn) != max_nn or not 3 <= int(max_nn) <= hip.NORMALS_MAX_NN:
         raise ValueError(f"max_nn must be an integer in 3..{hip.NORMALS_MAX_NN}, got {max_nn!r}")
     return float(radius), int(max_nn)
-
-
-def _list_cloud(points, what="points"):
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"{what} must be (M, 3), got {tuple(points.shape)}")
-    M = points.shape[0]
-    if M == 0:
-        raise ValueError(f"{what} is empty")
-    if M >= (1 << 31) - 64:
-        raise ValueError(f"{M} points are too many (the limit is 2^31 per launch)")
-    p = points.to(torch.float32)
-    out = torch.zeros(M, 4, device=points.device)
-    out[:, :3] = torch.where(torch.isfinite(p).all(1, keepdim=True), p, torch.full((), float("nan"), device=points.device))
-    return out
 
 
 def normals_of_clouds(xyz, n_clouds, n_points, grid, radius, max_nn, nrm=None, box=None, gbox=None, viewpoint=None, details=False):
@@ -78,11 +65,10 @@ def estimate_normals(points, radius=0.05, max_nn=30, viewpoint=None, return_neig
         if len(v) != 3 or not all(math.isfinite(x) for x in v):
             raise ValueError(f"viewpoint must be three finite numbers, got {viewpoint!r}")
         vp = v
-    xyz = _list_cloud(points)
-    hip.require_device(points)
+    xyz = list_cloud(points)
     M = points.shape[0]
     vpt = None if vp is None else torch.tensor([vp], dtype=torch.float32, device=points.device)
-    out = normals_of_clouds(xyz[None], 1, M, (0, 0), radius, max_nn, viewpoint=vpt, details=return_neighbors)
+    out = normals_of_clouds(xyz, 1, M, (0, 0), radius, max_nn, viewpoint=vpt, details=return_neighbors)
     if return_neighbors:
         return out[0][0, :, :3], out[1][0], out[2][0]
     return out[0, :, :3]
@@ -97,8 +83,7 @@ def voxel_downsample(points, voxel_size, return_labels=False):
     word beside it."""
     if not (math.isfinite(float(voxel_size)) and float(voxel_size) > 0.0):
         raise ValueError(f"voxel_size must be finite and positive, got {voxel_size!r}")
-    xyz = _list_cloud(points)
-    hip.require_device(points)
+    xyz = list_cloud(points)[0]
     dev, M = points.device, points.shape[0]
     cap = hip.voxel_capacity(M)
     state = torch.zeros(hip.VOXEL_STATE_WORDS, dtype=torch.int64, device=dev)

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import hip
+from .clip import DepthClip, list_cloud
 
 DEFAULT_BOX = ((-0.08, 0.08), (-0.07, 0.07), (-0.04, 0.18))  # the reference's GRIPPER_BOUNDS (metres, the end effector's frame)
 MAX_CHUNK_POINTS = 1 << 23  # padded points clustered per launch sequence: under 31 bytes of workspace each, 260 MB in all
@@ -129,26 +130,13 @@ def _info(row):
     return {k: int(v) for k, v in zip(STATE_FIELDS, row.tolist())}
 
 
-def _list_cloud(points):
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"points must be (M, 3), got {tuple(points.shape)}")
-    M = points.shape[0]
-    if M >= (1 << 31) - 64:
-        raise ValueError(f"{M} points are too many (the limit is 2^31 per launch)")
-    hip.require_device(points)
-    p = points.to(torch.float32)
-    xyz = torch.zeros(1, M, 4, device=points.device)
-    xyz[0, :, :3] = torch.where(torch.isfinite(p).all(1, keepdim=True), p, torch.full((), float("nan"), device=points.device))
-    return xyz
-
-
 @hip.guarded
 def cluster_points(points, eps=0.03, min_samples=12, return_info=False):
     """``sklearn.cluster.DBSCAN(eps, min_samples).fit_predict`` on a point list: points (M, 3) on the device -> labels (M,) int32,
     -1 for noise and for rows that are not finite.  ``return_info``: also a dict of the cloud's state row (candidates, core,
     clusters, chosen, chosen_size, noise, fallback, status) plus ``core`` (M,) bool."""
     eps, min_samples = check_dbscan(eps, min_samples)
-    xyz = _list_cloud(points)
+    xyz = list_cloud(points, empty_ok=True)
     M = points.shape[0]
     if M == 0:
         labels = torch.zeros(0, dtype=torch.int32, device=points.device)
@@ -168,7 +156,7 @@ def select_region_points(points, pose, region=None):
     (M,) bool, True on the points of the largest cluster inside the region's box (all points in the box when there are fewer than
     min_samples of them or no cluster forms)."""
     c = RegionCluster() if region is None else _check(region)
-    xyz = _list_cloud(points)
+    xyz = list_cloud(points, empty_ok=True)
     M = points.shape[0]
     if M == 0:
         return torch.zeros(0, dtype=torch.bool, device=points.device)
@@ -207,34 +195,17 @@ class RegionReport:
 
 
 def region_clip(depths, intrs, extrs, poses, region, depths_conf=None, details=False):
-    """``region_masks`` on a clip (V,T,1,H,W) with cameras (V,T,3,3) / (V,T,3,4): (mask (V,T,1,H,W) bool, RegionReport); with
-    ``details`` also the labels (V,T,H,W) int32, the core flags (V,T,H,W) bool and the cropped clouds' points (V,T,H,W,4)."""
+    """``region_masks`` whose ``details`` stay in clip rank: (mask bool of the shape of ``depths``, RegionReport); with ``details``
+    also the labels (V,T,H,W) int32, the core flags (V,T,H,W) bool and the cropped clouds' points (V,T,H,W,4)."""
     c = _check(region)
-    if depths.dim() != 5 or depths.shape[2] != 1:
-        raise ValueError(f"depths must be (V, T, 1, H, W), got {tuple(depths.shape)}")
-    V, T, _, H, W = depths.shape
-    if tuple(intrs.shape) != (V, T, 3, 3) or tuple(extrs.shape) != (V, T, 3, 4):
-        raise ValueError(f"intrs / extrs must be ({V}, {T}, 3, 3) / ({V}, {T}, 3, 4), got {tuple(intrs.shape)} / {tuple(extrs.shape)}")
-    if depths_conf is not None and tuple(depths_conf.shape) != tuple(depths.shape):
-        raise ValueError(f"depths_conf must have the shape of depths, got {tuple(depths_conf.shape)}")
+    clip = DepthClip(depths, intrs, extrs, depths_conf)
+    V, T, H, W, dev = clip.V, clip.T, clip.H, clip.W, clip.dev
     rtw = None
     if c.box is not None:
         if poses is None:
             raise ValueError("a region with a box needs poses: (4, 4) or (T, 4, 4) world_T_region")
         rtw = invert_poses(poses, T)  # (T, 3, 4) on the host
-    hip.require_device(depths)
-    dev = depths.device
-    d = depths.to(torch.float32).contiguous()
-    conf = None if (depths_conf is None or c.conf_thresh is None) else depths_conf.to(torch.float32).contiguous()
-    kinv = torch.empty(V * T, 9, device=dev)
-    einv = torch.empty(V * T, 12, device=dev)
-    hip.invert_cameras(intrs.to(torch.float32).reshape(V * T, 9).contiguous(), extrs.to(torch.float32).reshape(V * T, 12).contiguous(), kinv, einv,
-                       V * T)
-    Hp, Wp = (H + 7) // 8 * 8, (W + 7) // 8 * 8
-    P = Hp * Wp
-    if P >= (1 << 31) - 64:
-        raise ValueError(f"a cloud of {Hp} x {Wp} points is too large (the limit is 2^31 per launch)")
-    step = max(1, min(T, MAX_CHUNK_POINTS // (V * P), 65535 // V))  # frames per launch sequence: bounded workspace
+    Hp, Wp, P = clip.padded_grid()
     mask = torch.empty(V, T, H, W, device=dev, dtype=torch.bool)
     states = torch.empty(V, T, hip.CLUSTER_STATE_WORDS, device=dev, dtype=torch.int64)
     labels = cores = pts = None
@@ -242,22 +213,20 @@ def region_clip(depths, intrs, extrs, poses, region, depths_conf=None, details=F
         labels = torch.empty(V, T, H, W, device=dev, dtype=torch.int32)
         cores = torch.empty(V, T, H, W, device=dev, dtype=torch.bool)
         pts = torch.empty(V, T, H, W, 4, device=dev)
-    for t0 in range(0, T, step):
-        nt = min(step, T - t0)
-        xyz = torch.empty(V * nt, P, 4, device=dev)
-        hip.clean_points(d, conf, kinv, einv, V, T, t0, nt, H, W, c.conf_thresh, None, xyz)
+    for t0, nt in clip.frame_chunks(MAX_CHUNK_POINTS):  # frames per launch sequence: bounded workspace
+        xyz = clip.clouds(t0, nt, c.conf_thresh)
         m = None if rtw is None else rtw[t0:t0 + nt][None].expand(V, nt, 3, 4).reshape(V * nt, 3, 4).contiguous().to(dev)  # cloud = v * nt + t
         r = cluster_clouds(xyz, V * nt, P, (Wp, Hp), c.eps, c.min_samples, m, c.bounds)
-        mask[:, t0:t0 + nt] = r["select"].reshape(V, nt, Hp, Wp)[:, :, :H, :W] != 0
+        mask[:, t0:t0 + nt] = clip.crop(r["select"], nt) != 0
         states[:, t0:t0 + nt] = r["state"].reshape(V, nt, hip.CLUSTER_STATE_WORDS)
         if details:
-            labels[:, t0:t0 + nt] = r["labels"].reshape(V, nt, Hp, Wp)[:, :, :H, :W]
-            cores[:, t0:t0 + nt] = r["core"].reshape(V, nt, Hp, Wp)[:, :, :H, :W] != 0
-            pts[:, t0:t0 + nt] = xyz.reshape(V, nt, Hp, Wp, 4)[:, :, :H, :W]
+            labels[:, t0:t0 + nt] = clip.crop(r["labels"], nt)
+            cores[:, t0:t0 + nt] = clip.crop(r["core"], nt) != 0
+            pts[:, t0:t0 + nt] = clip.crop(xyz, nt)
     tail = torch.cat([states.reshape(V * T, -1), mask.reshape(V * T, -1).sum(1, keepdim=True)], 1).cpu()  # the one host read
     check_status(tail[:, :hip.CLUSTER_STATE_WORDS])
     report = RegionReport(tail[:, :hip.CLUSTER_STATE_WORDS].reshape(V, T, -1).numpy(), tail[:, -1].reshape(V, T).numpy())
-    mask = mask.reshape(V, T, 1, H, W)
+    mask = clip.rebatch(mask.reshape(V, T, 1, H, W))
     return (mask, report, labels, cores, pts) if details else (mask, report)
 
 
@@ -269,11 +238,4 @@ def region_masks(depths, intrs, extrs, poses, region, depths_conf=None, details=
     region's box are one cloud, clustered on its own, and its largest cluster is the mask (every point in the box when there are
     fewer than ``min_samples`` or no cluster forms).  Returns ``(mask, report)``: ``mask`` bool of the shape of ``depths``, ``report``
     a RegionReport.  The inputs are not written."""
-    batched = depths.dim() == 6
-    if batched and depths.shape[0] != 1:
-        raise ValueError(f"depths must be (V, T, 1, H, W) or (1, V, T, 1, H, W), got {tuple(depths.shape)}")
-    if batched and (intrs.dim() != 5 or extrs.dim() != 5 or (depths_conf is not None and depths_conf.dim() != 6)):
-        raise ValueError("intrs, extrs and depths_conf must have the leading batch dimension of depths")
-    sq = (lambda t: None if t is None else t[0]) if batched else (lambda t: t)
-    out = region_clip(sq(depths), sq(intrs), sq(extrs), poses, region, sq(depths_conf), details)
-    return ((out[0][None],) + tuple(out[1:])) if batched else out
+    return region_clip(depths, intrs, extrs, poses, region, depths_conf, details)

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import hip
+from .clip import DepthClip
 
 L = hip.MASK_LABELS
 
@@ -148,43 +149,30 @@ def _labels(labels):
     return labels.clone() if labels.data_ptr() % 16 else labels
 
 
-class _Clip:
-    """The checked inputs of one call: labels (V,T,H,W) uint8, depths / conf (V,T,1,H,W) fp32, the inverted cameras."""
+class _Clip(DepthClip):
+    """The checked inputs of one call: the depth clip (1,V,T,...) with its labels ``lab`` (V,T,H,W) uint8 and the options ``opt``."""
 
     def __init__(self, labels, depths, intrs, extrs, depths_conf, options):
         self.opt = _check(options)
-        if depths.dim() != 6 or depths.shape[0] != 1 or depths.shape[3] != 1:
-            raise ValueError(f"depths must be (1, V, T, 1, H, W), got {tuple(depths.shape)}")
-        _, V, T, _, H, W = depths.shape
+        super().__init__(depths, intrs, extrs, depths_conf, batch="required")
+        V, T, H, W = self.V, self.T, self.H, self.W
         self.lab = _labels(labels)
         if tuple(self.lab.shape) != (V, T, H, W):
             raise ValueError(f"labels {tuple(self.lab.shape)} and depths {tuple(depths.shape)} differ in (V, T, H, W)")
-        if depths_conf is not None and depths_conf.shape != depths.shape:
-            raise ValueError(f"depths_conf must have the shape of depths, got {tuple(depths_conf.shape)}")
         if self.opt.conf_thresh is not None and depths_conf is None:
             raise ValueError("conf_thresh needs depths_conf")
         if V > hip.MASK_MAX_VIEWS or V * T > 65535 or H * W > 1 << 24 or V * H * W >= 1 << 31:
             raise ValueError(f"{V} views x {T} frames of {H} x {W} are too many for one call (at most {hip.MASK_MAX_VIEWS} views, 65535 "
                              f"images, 2^24 pixels per image)")
-        if tuple(intrs.shape) != (1, V, T, 3, 3) or tuple(extrs.shape) != (1, V, T, 3, 4):
-            raise ValueError(f"intrs must be (1, V, T, 3, 3) and extrs (1, V, T, 3, 4), got {tuple(intrs.shape)} and {tuple(extrs.shape)}")
         if isinstance(self.opt.anchor, int) and self.opt.anchor >= T:
             raise ValueError(f"anchor frame {self.opt.anchor} is beyond the clip's {T} frames")
-        hip.require_device(depths)
-        if self.lab.device != depths.device:
-            raise ValueError(f"labels on {self.lab.device}, depths on {depths.device}")
-        self.V, self.T, self.H, self.W, self.dev = V, T, H, W, depths.device
-        self.d = depths[0].to(torch.float32).contiguous()
-        # (the confidence map is read only under a threshold)
-        self.conf = None if self.opt.conf_thresh is None else depths_conf[0].to(torch.float32).contiguous()
-        self.kinv = torch.empty(V * T, 9, device=self.dev)
-        self.einv = torch.empty(V * T, 12, device=self.dev)
-        hip.invert_cameras(intrs[0].to(torch.float32).reshape(V * T, 9).contiguous(), extrs[0].to(torch.float32).reshape(V * T, 12).contiguous(),
-                           self.kinv, self.einv, V * T)
+        if self.lab.device != self.dev:
+            raise ValueError(f"labels on {self.lab.device}, depths on {self.dev}")
+        self.kinv  # (inverted here: ahead of whatever the call launches, also when that is nothing)
 
     def pool_args(self, t):
-        o = self.opt
-        return (self.lab, self.d, self.conf, self.kinv, self.einv, self.V, self.T, int(t), self.H, self.W, o.min_depth, o.max_depth,
+        o = self.opt  # (the confidence map is read only under a threshold)
+        return (self.lab, self.d, self.conf(o.conf_thresh), self.kinv, self.einv, self.V, self.T, int(t), self.H, self.W, o.min_depth, o.max_depth,
                 0.0 if o.conf_thresh is None else o.conf_thresh)
 
 
@@ -238,7 +226,7 @@ class MaskStatistics:
 def _statistics(clip):
     tables = _Tables(clip.V, clip.T, clip.dev)
     o = clip.opt
-    hip.mask_stats(clip.lab, clip.d, clip.conf, clip.kinv, clip.einv, clip.V, clip.T, clip.H, clip.W, o.min_depth, o.max_depth,
+    hip.mask_stats(clip.lab, clip.d, clip.conf(o.conf_thresh), clip.kinv, clip.einv, clip.V, clip.T, clip.H, clip.W, o.min_depth, o.max_depth,
                    0.0 if o.conf_thresh is None else o.conf_thresh, tables.stats)
     hip.mask_centroids(tables.stats, clip.V, clip.T, o.min_pixels, tables.centroid)
     return MaskStatistics(tables, o.min_pixels)

@@ -17,6 +17,7 @@ import math
 import torch
 
 from . import hip
+from .clip import DepthClip
 
 DEFAULT_SPEC = [(0, -0.1, 4.2, 2.1, 1000, "kmeans")]  # the evaluator's row for unknown datasets (:341-343)
 LLOYD_CHUNK = 8  # Lloyd iterations enqueued between two reads of the device's converged flag
@@ -156,11 +157,11 @@ def sample_queries(depths, intrs, extrs, spec, depths_conf=None, conf_threshold=
     (``motion_keep="static"``: static).  With a region as well a pixel must pass both.  The clip's mask is computed once per call,
     whatever the number of rows; ``motion_reports``: a dict that receives {"clip": MotionReport}.  Without ``motion`` nothing of that
     runs."""
-    if depths.dim() != 6 or depths.shape[0] != 1 or depths.shape[3] != 1:
-        raise ValueError(f"depths must be (1, V, T, 1, H, W), got {tuple(depths.shape)}")
     for row in spec:
         if row[5] not in ("", "kmeans"):
             raise NotImplementedError(f"sampling method {row[5]!r} (the reference knows '' and 'kmeans')")
+    clip = DepthClip(depths, intrs, extrs, depths_conf, batch="required")
+    V, T, H, W, dev = clip.V, clip.T, clip.H, clip.W, clip.dev
     if region is not None:  # (refused before any launch)
         from . import cluster
         if not isinstance(region, cluster.RegionCluster):
@@ -168,7 +169,7 @@ def sample_queries(depths, intrs, extrs, spec, depths_conf=None, conf_threshold=
         if region.box is not None:
             if region_poses is None:
                 raise ValueError("a region with a box needs region_poses: (4, 4) or (T, 4, 4) world_T_region")
-            cluster.invert_poses(region_poses, depths.shape[2])
+            cluster.invert_poses(region_poses, T)
     elif region_poses is not None:
         raise ValueError("region_poses without a region")
     frames = None
@@ -181,21 +182,11 @@ def sample_queries(depths, intrs, extrs, spec, depths_conf=None, conf_threshold=
         if rgbs is None:
             raise ValueError("motion needs rgbs: the clip's frames (1, V, T, 3, H, W)")
         frames = motion_.clip_frames(rgbs)
-        if (frames.shape[0], frames.shape[1], frames.shape[3], frames.shape[4]) != (depths.shape[1], depths.shape[2], depths.shape[4], depths.shape[5]):
+        if (frames.shape[0], frames.shape[1], frames.shape[3], frames.shape[4]) != (V, T, H, W):
             raise ValueError(f"rgbs {tuple(rgbs.shape)} and depths {tuple(depths.shape)} differ in (V, T, H, W)")
     elif rgbs is not None:
         raise ValueError("rgbs without motion")
-    hip.require_device(depths)
-    _, V, T, _, H, W = depths.shape
-    dev = depths.device
-    d = depths[0].to(torch.float32).contiguous()
-    conf = None if depths_conf is None else depths_conf[0].to(torch.float32).contiguous()
-    if conf is not None and conf.shape != d.shape:
-        raise ValueError(f"depths_conf must have the shape of depths, got {tuple(depths_conf.shape)}")
-    kinv = torch.empty(V * T, 9, device=dev)
-    einv = torch.empty(V * T, 12, device=dev)
-    hip.invert_cameras(intrs[0].to(torch.float32).reshape(V * T, 9).contiguous(), extrs[0].to(torch.float32).reshape(V * T, 12).contiguous(),
-                       kinv, einv, V * T)
+    d, conf, kinv, einv = clip.d, clip.conf(conf_threshold), clip.kinv, clip.einv
     g = torch.Generator(device="cpu").manual_seed(int(seed))
     out = []
     masks = {}  # frame -> (mask, report): rows that share a frame share the mask
@@ -206,7 +197,7 @@ def sample_queries(depths, intrs, extrs, spec, depths_conf=None, conf_threshold=
         mask = None
         if region is not None:
             if t not in masks:
-                masks[t] = _region_mask(d, conf, intrs[0], extrs[0], t, region, region_poses)
+                masks[t] = _region_mask(d, conf, clip.intrs, clip.extrs, t, region, region_poses)
                 if region_reports is not None:
                     region_reports[t] = masks[t][1]
             mask = masks[t][0]

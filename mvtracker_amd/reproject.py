@@ -20,6 +20,7 @@ import math
 import torch
 
 from . import hip
+from .clip import DepthClip
 
 SOURCES = ("others", "all")
 SPLATS = (1, 3, 5)
@@ -108,19 +109,14 @@ def render_point_cloud(points, colors, intr, extr, height, width, min_depth=0.01
 
 
 def reproject_clip(rgbs, depths, intrs, extrs, frames=None, sources="others", min_depth=0.01, splat=1, depths_conf=None, conf_thresh=None):
-    """``reproject_views`` on a clip: rgbs (V,T,3,H,W), depths (V,T,1,H,W), cameras (V,T,3,3) / (V,T,3,4)."""
+    """``reproject_views`` whose results stay in clip rank: (V,F,3,H,W), (V,F,1,H,W), (V,F,H,W) with or without the leading batch."""
     min_depth, splat = _check_render(min_depth, splat)
     if sources not in SOURCES:
         raise ValueError(f"sources must be one of {SOURCES}, got {sources!r}")
-    if depths.dim() != 5 or depths.shape[2] != 1:
-        raise ValueError(f"depths must be (V, T, 1, H, W), got {tuple(depths.shape)}")
-    V, T, _, H, W = depths.shape
-    if tuple(rgbs.shape) != (V, T, 3, H, W):
-        raise ValueError(f"rgbs must be ({V}, {T}, 3, {H}, {W}), got {tuple(rgbs.shape)}")
-    if tuple(intrs.shape) != (V, T, 3, 3) or tuple(extrs.shape) != (V, T, 3, 4):
-        raise ValueError(f"intrs / extrs must be ({V}, {T}, 3, 3) / ({V}, {T}, 3, 4), got {tuple(intrs.shape)} / {tuple(extrs.shape)}")
-    if depths_conf is not None and tuple(depths_conf.shape) != tuple(depths.shape):
-        raise ValueError(f"depths_conf must have the shape of depths, got {tuple(depths_conf.shape)}")
+    clip = DepthClip(depths, intrs, extrs, depths_conf)
+    V, T, H, W, dev = clip.V, clip.T, clip.H, clip.W, clip.dev
+    if tuple(rgbs.shape) != tuple(depths.shape[:-3]) + (3, H, W):
+        raise ValueError(f"rgbs must be {tuple(depths.shape[:-3]) + (3, H, W)}, got {tuple(rgbs.shape)}")
     fr = tuple(range(T)) if frames is None else _check_frames(frames)
     if max(fr) >= T:
         raise ValueError(f"frames {fr} reach past the clip's {T} frames")
@@ -130,20 +126,14 @@ def reproject_clip(rgbs, depths, intrs, extrs, frames=None, sources="others", mi
         raise ValueError('sources="others" needs at least 2 views')
     if V * H * W >= 1 << 31:
         raise ValueError(f"{V} views of {H} x {W} pixels are too large (the limit is 2^31 source pixels)")
-    hip.require_device(depths)
-    dev = depths.device
     F, HW = len(fr), H * W
-    d = depths.to(torch.float32).contiguous()
-    c = rgbs.contiguous() if rgbs.dtype == torch.uint8 else rgbs.to(torch.float32).contiguous()
-    conf = None if (depths_conf is None or conf_thresh is None) else depths_conf.to(torch.float32).contiguous()
-    K = intrs.to(torch.float32).reshape(V, T, 9).contiguous()
-    E = extrs.to(torch.float32).reshape(V, T, 12).contiguous()
-    kinv = torch.empty(V * T, 9, device=dev)
-    einv = torch.empty(V * T, 12, device=dev)
-    hip.invert_cameras(K.reshape(V * T, 9), E.reshape(V * T, 12), kinv, einv, V * T)
+    d, conf = clip.d, clip.conf(conf_thresh)
+    c = clip.squeeze(rgbs)
+    c = c.contiguous() if c.dtype == torch.uint8 else c.to(torch.float32).contiguous()
+    kinv, einv = clip.kinv, clip.einv
     idx = torch.tensor(fr, dtype=torch.long, device=dev)
-    Kf = K.index_select(1, idx).transpose(0, 1).contiguous()  # (F, V, 9): the target cameras of a frame are contiguous rows
-    Ef = E.index_select(1, idx).transpose(0, 1).contiguous()
+    Kf = clip.K.index_select(1, idx).transpose(0, 1).contiguous()  # (F, V, 9): the target cameras of a frame are contiguous rows
+    Ef = clip.E.index_select(1, idx).transpose(0, 1).contiguous()
     color = torch.empty(V, F, 3, H, W, dtype=torch.uint8, device=dev)
     depth = torch.empty(V, F, 1, H, W, device=dev)
     index = torch.empty(V, F, H, W, dtype=torch.int32, device=dev)
@@ -163,17 +153,6 @@ def reproject_clip(rgbs, depths, intrs, extrs, frames=None, sources="others", mi
     return color, depth, index
 
 
-def _squeeze(tensors, lead):
-    """The clip-rank tensors of inputs that may carry a leading batch of 1 (``lead``: the rank with it), and whether they did."""
-    first = tensors[0]
-    batched = first.dim() == lead
-    if batched and first.shape[0] != 1:
-        raise ValueError(f"a leading batch dimension must be 1, got {tuple(first.shape)}")
-    if batched and any(t is not None and t.dim() != r for t, r in zip(tensors, (6, 6, 5, 5, 6))):
-        raise ValueError("rgbs, depths, intrs, extrs and depths_conf must all have the leading batch dimension, or none")
-    return [t if (t is None or not batched) else t[0] for t in tensors], batched
-
-
 @hip.guarded
 def reproject_views(rgbs, depths, intrs, extrs, frames=None, sources="others", min_depth=0.01, splat=1, depths_conf=None, conf_thresh=None):
     """Every view of a clip rendered from the views' depth maps.  rgbs (V,T,3,H,W) uint8 or float (0..255), depths (V,T,1,H,W),
@@ -182,9 +161,8 @@ def reproject_views(rgbs, depths, intrs, extrs, frames=None, sources="others", m
     conf > conf_thresh when both are given).  Returns ``(color (V,F,3,H,W) uint8, depth (V,F,1,H,W) fp32 with 0 = nothing drawn,
     index (V,F,H,W) int32)``: ``index = view * H * W + y * W + x`` of the source pixel that won, -1 where nothing was drawn: a
     cross-view correspondence map.  With the batch the outputs carry it too."""
-    (r, d, K, E, cf), batched = _squeeze([rgbs, depths, intrs, extrs, depths_conf], 6)
-    out = reproject_clip(r, d, K, E, frames, sources, min_depth, splat, cf, conf_thresh)
-    return tuple(o[None] for o in out) if batched else out
+    out = reproject_clip(rgbs, depths, intrs, extrs, frames, sources, min_depth, splat, depths_conf, conf_thresh)
+    return tuple(o[None] for o in out) if depths.dim() == 6 else out
 
 
 class ReprojectionReport:
@@ -289,9 +267,10 @@ def reprojection_report(rgbs, depths, intrs, extrs, check, depths_conf=None):
     the view's own frame and depth map.  Inputs as ``reproject_views`` takes them.  Returns a ``ReprojectionReport``; the records
     are read back once, the inputs are not written."""
     ck = _check(check)
-    (r, d, K, E, cf), _ = _squeeze([rgbs, depths, intrs, extrs, depths_conf], 6)
-    if min(d.shape[-2:]) < 6:  # (before the render: nothing is launched for a clip the scores refuse)
-        raise ValueError(f"the SSIM window needs images of at least 6 x 6 pixels, got {d.shape[-2]} x {d.shape[-1]}")
-    color, depth, index = reproject_clip(r, d, K, E, ck.frames, ck.sources, ck.min_depth, ck.splat, cf, ck.conf_thresh)
-    scores = score_renders(color, depth, index, r, d, ck.frames, ck.depth_tol)
+    if min(depths.shape[-2:]) < 6:  # (before the render: nothing is launched for a clip the scores refuse)
+        raise ValueError(f"the SSIM window needs images of at least 6 x 6 pixels, got {depths.shape[-2]} x {depths.shape[-1]}")
+    color, depth, index = reproject_clip(rgbs, depths, intrs, extrs, ck.frames, ck.sources, ck.min_depth, ck.splat, depths_conf, ck.conf_thresh)
+    if depths.dim() == 6:  # (a leading batch of 1 on both: the render has checked it)
+        rgbs, depths = rgbs[0], depths[0]
+    scores = score_renders(color, depth, index, rgbs, depths, ck.frames, ck.depth_tol)
     return ReprojectionReport(scores.cpu(), ck.frames, ck)

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import hip
+from .clip import DepthClip
 
 MIN_POINTS = 100  # a view with fewer valid pixels is left out; fewer kept points in all is an error (reference :314-315, :330-331)
 FLOOR_QUANTILE, RADIUS_QUANTILE = 0.12, 0.95
@@ -92,30 +93,17 @@ class SceneTransform:
 def scene_statistics(depths, intrs, extrs, depths_conf=None, conf_thresh=4.8, frame=0, radius_quantile=None):
     """The pool statistics of frame ``frame`` as the kernels leave them, still on the device: (state int64 (SN_WORDS,), the frame's
     world->camera translation columns (V, 3) fp64).  Inputs as ``forward`` takes them (1,V,T,...)."""
-    if depths.dim() != 6 or depths.shape[0] != 1 or depths.shape[3] != 1:
-        raise ValueError(f"depths must be (1, V, T, 1, H, W), got {tuple(depths.shape)}")
-    _, V, T, _, H, W = depths.shape
-    if tuple(intrs.shape) != (1, V, T, 3, 3) or tuple(extrs.shape) != (1, V, T, 3, 4):
-        raise ValueError(f"intrs / extrs must be (1, {V}, {T}, 3, 3) / (1, {V}, {T}, 3, 4), got {tuple(intrs.shape)} / {tuple(extrs.shape)}")
+    clip = DepthClip(depths, intrs, extrs, depths_conf, batch="required")
+    V, T, H, W, dev = clip.V, clip.T, clip.H, clip.W, clip.dev
     if not 0 <= int(frame) < T:
         raise ValueError(f"frame {frame} outside the clip of {T} frames")
-    hip.require_device(depths)
-    dev = depths.device
-    d = depths[0].to(torch.float32).contiguous()
-    conf = None if depths_conf is None else depths_conf[0].to(torch.float32).contiguous()
-    if conf is not None and conf.shape != d.shape:
-        raise ValueError(f"depths_conf must have the shape of depths, got {tuple(depths_conf.shape)}")
-    e32 = extrs[0].to(torch.float32)
-    kinv = torch.empty(V * T, 9, device=dev)
-    einv = torch.empty(V * T, 12, device=dev)
-    hip.invert_cameras(intrs[0].to(torch.float32).reshape(V * T, 9).contiguous(), e32.reshape(V * T, 12).contiguous(), kinv, einv, V * T)
     state = torch.empty(hip.SN_WORDS, device=dev, dtype=torch.int64)
     keys = torch.empty(V * H * W, device=dev, dtype=torch.int32)
     partial = torch.empty(hip.SCENE_BLOCKS * 3, device=dev, dtype=torch.float64)
     iws = torch.empty(hip.SELECT_WS_WORDS + V, device=dev, dtype=torch.int32)
-    hip.scene_stats(d, conf, kinv, einv, V, T, int(frame), H, W, float(conf_thresh), MIN_POINTS, FLOOR_QUANTILE, radius_quantile, keys, partial,
-                    iws, state)
-    return state, e32[:, int(frame), :, 3].to(torch.float64)
+    hip.scene_stats(clip.d, clip.conf(conf_thresh), clip.kinv, clip.einv, V, T, int(frame), H, W, float(conf_thresh), MIN_POINTS, FLOOR_QUANTILE,
+                    radius_quantile, keys, partial, iws, state)
+    return state, clip.E[:, int(frame), 3::4].to(torch.float64)
 
 
 def read_statistics(state):
