@@ -7,6 +7,9 @@ evaluation_predictor_3dpt.py:17-414): same constructor, same ``forward`` keyword
 can drive it unchanged.  The heavy lifting is ``self.model`` (mvtracker_amd.tracker.MVTracker);
 the resize runs in the HIP library, the support-grid synthesis is a few hundred points of
 bookkeeping on device tensors.
+
+``forward`` is a list of stages, each written once ("The predictor's stages"); a streaming session's ``push``
+runs the same cast, clean, normalise and resize on every block, and the global support grid on the first.
 """
 from __future__ import annotations
 
@@ -14,11 +17,16 @@ import contextlib
 import logging
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import hip
 
 log = logging.getLogger(__name__)
+
+
+def _f32(t: torch.Tensor) -> torch.Tensor:
+    return t.to(torch.float32).contiguous()
 
 
 def _bilinear_sample_depth(depth: torch.Tensor, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
@@ -48,6 +56,17 @@ def _bilinear_sample_depth_multi(depths: torch.Tensor, v: torch.Tensor, t: torch
             + (x1 - x) * (y - y0) * flat[base + cy1 * W + cx0] + (x - x0) * (y - y0) * flat[base + cy1 * W + cx1])
 
 
+def _lift(depths, vid, fid, x, y, kinv, einv):
+    """The batched lift: pixels (x, y) of the depth maps (vid, fid) into the world.  depths (V,T,H,W), vid,fid,x,y (M,), kinv
+    (V,T,3,3), einv (V,T,3,4) -> (M,4) rows (frame, world xyz).  (The global grid does NOT come through here: it keeps the
+    per-camera matmul of ``_support_rows``, whose rounding the stream-equals-forward promise and the golden fixtures rest on.)"""
+    z = _bilinear_sample_depth_multi(depths, vid, fid, x, y)
+    cam = torch.einsum("mij,mj->mi", kinv[vid, fid], torch.stack([x, y, torch.ones_like(x)], 1)) * z[:, None]
+    ei = einv[vid, fid]
+    world = torch.einsum("mij,mj->mi", ei[:, :, :3], cam) + ei[:, :, 3]
+    return torch.cat([fid[:, None].to(world.dtype), world], 1)
+
+
 def get_uniformly_sampled_pts(size: int, num_frames: int, extent: Tuple[float, ...], device="cpu") -> torch.Tensor:
     """(1, size, 3) rows (t, a, b): t uniform in [0, num_frames), a uniform in [0, extent[1]), b in [0, extent[0]) -- reference
     evaluation_predictor_3dpt.py:417-429, the same draws in the same order (torch.randint, then torch.rand)."""
@@ -67,6 +86,45 @@ def points_on_a_grid(size: int, extent: Tuple[float, float], center=None, device
     xs = torch.linspace(m - extent[1] / 2 + center[1], extent[1] / 2 + center[1] - m, size, device=device)
     gy, gx = torch.meshgrid(ys, xs, indexing="ij")
     return torch.stack([gx, gy], dim=-1).reshape(-1, 2)
+
+
+# ---- clip stages without state: ``forward`` and a streaming session's ``push`` run the same ones ----------------------------------
+def _cast(rgbs, depths, intrs, extrs, interp_shape):
+    """(uint8 frames stay uint8 unless they have to be resized: the encoder's first kernel converts them)"""
+    if not (rgbs.dtype == torch.uint8 and interp_shape is None):
+        rgbs = rgbs.to(torch.float32)
+    return rgbs.contiguous(), _f32(depths), intrs.to(torch.float32), extrs.to(torch.float32)
+
+
+def _clean(depths, intrs, extrs, depth_cleaning, depths_conf):
+    """The raw clip's depths cleaned of outliers (the radius is in the caller's units).  None: not one launch."""
+    if depth_cleaning is None:
+        return depths
+    from . import clean
+    return clean.clean_depths(depths, intrs, extrs, depth_cleaning, depths_conf=depths_conf)[0]
+
+
+def _normalise(xf, depths, extrs, query_points=None):
+    """Depths, extrinsics and queries (``forward`` only: a stream transforms its queries once, when it is opened) of the raw-resolution
+    clip in the normalised scene.  The support points are built from these, so they need nothing of their own."""
+    if xf is None:
+        return depths, extrs, query_points
+    return xf.apply(depths=depths, extrs=extrs, query_points=query_points)[:3]
+
+
+def _resize(rgbs, depths, intrs, interp_shape):
+    """Frames and depths at ``interp_shape`` (nearest) with the intrinsics rescaled, evaluation_predictor_3dpt.py:72-87.  None: not one launch."""
+    if interp_shape is None:
+        return rgbs, depths, intrs
+    dev = rgbs.device
+    _, V, T, _, height_raw, width_raw = rgbs.shape
+    height, width = interp_shape
+    r = torch.empty(1, V, T, 3, height, width, device=dev)
+    hip.resize_nearest(rgbs, r, V * T * 3, height_raw, width_raw, height, width)
+    d = torch.empty(1, V, T, 1, height, width, device=dev)
+    hip.resize_nearest(depths, d, V * T, height_raw, width_raw, height, width)
+    rs = torch.tensor([[width / width_raw, 0, 0], [0, height / height_raw, 0], [0, 0, 1]], device=dev, dtype=intrs.dtype)
+    return r, d, torch.einsum("ij,BVTjk->BVTik", rs, intrs)
 
 
 class EvaluationPredictor(torch.nn.Module):
@@ -155,7 +213,6 @@ class EvaluationPredictor(torch.nn.Module):
 
     def _query_groups(self, query_groups, num_points):
         """``forward``'s ``query_groups`` -> the caller rows of every distinct id, in ascending id order."""
-        import numpy as np
         if self.single_point:
             raise NotImplementedError("query_groups with single_point: every query is a forward of its own there (group them with "
                                       "single_point_group_size)")
@@ -169,10 +226,167 @@ class EvaluationPredictor(torch.nn.Module):
         ids = ids.cpu().numpy()
         return [np.nonzero(ids == g)[0] for g in np.unique(ids)]
 
+    # ---- clip stages that leave a ``last_*`` attribute --------------------------------------------------------------------------
+    def _align(self, depths, intrs, extrs, camera_alignment, depths_conf):
+        """(corrected extrs, uncorrected extrs) of a ``CameraAlignment`` (refined here, on the cleaned raw clip) or a ready
+        ``CameraCorrection``, kept as ``last_camera_correction``.  None: (extrs, None) and not one launch."""
+        self.last_camera_correction = None
+        if camera_alignment is None:
+            return extrs, None
+        from . import align
+        if isinstance(camera_alignment, align.CameraCorrection):
+            correction = camera_alignment
+        elif isinstance(camera_alignment, align.CameraAlignment):
+            correction = align.align_cameras(depths, intrs, extrs, camera_alignment, depths_conf=depths_conf)
+        else:
+            raise ValueError(f"camera_alignment must be None, a CameraAlignment or a CameraCorrection, got {camera_alignment!r}")
+        self.last_camera_correction = correction
+        return correction.apply(extrs), extrs
+
+    def _reproject(self, rgbs, depths, intrs, extrs, extrs_uncorrected, reprojection_check, depths_conf):
+        """``last_reprojection_report`` of the cameras the tracker is about to use and, after an alignment, ``..._before`` of the
+        uncorrected ones; both on the cleaned depths at raw resolution.  None: not one launch."""
+        self.last_reprojection_report = self.last_reprojection_report_before = None
+        if reprojection_check is None:
+            return
+        from . import reproject
+        if extrs_uncorrected is not None:
+            self.last_reprojection_report_before = reproject.reprojection_report(rgbs, depths, intrs, extrs_uncorrected, reprojection_check,
+                                                                                 depths_conf=depths_conf)
+        self.last_reprojection_report = reproject.reprojection_report(rgbs, depths, intrs, extrs, reprojection_check, depths_conf=depths_conf)
+
+    # ---- support points: rows (frame, world xyz) from the clip the model is about to see ------------------------------------------
     def _support_rows(self, depth, pix, kinv, einv, t):
         z = _bilinear_sample_depth(depth, pix[:, 0], pix[:, 1])
         world = self._unproject(pix, z, kinv, einv)
         return torch.cat([torch.full_like(world[:, :1], float(t)), world], 1)
+
+    def _grid_rows(self, depths, kinv, einv, frames):
+        """The global support grid (:101-120) of every view at ``frames`` (frame-major, then view), through the per-camera lift."""
+        pix = points_on_a_grid(self.grid_size, tuple(depths.shape[-2:]), device=depths.device)
+        return torch.cat([self._support_rows(depths[0, v, t, 0], pix, kinv[v, t], einv[v, t], t)
+                          for t in frames for v in range(depths.shape[1])], 0)
+
+    def _uniform_rows(self, depths, kinv, einv):
+        """Uniformly sampled support points (:147-190): (t, y, x) rows from get_uniformly_sampled_pts -- the same two torch draws as
+        the reference, from the global generator of the tensors' device -- lifted into the world through EVERY view's depth map
+        (sample-major, then view), with the reference's argument order kept as it is: the column it calls y is scaled by the WIDTH
+        and the one it calls x by the HEIGHT (:424-426), and out-of-map coordinates are clamped by the sampler."""
+        _, V, T, _, height, width = depths.shape
+        sp = get_uniformly_sampled_pts(self.num_uniformly_sampled_pts, T, (height, width), device=depths.device)[0]
+        t_s, y_s, x_s = sp[:, 0].long(), sp[:, 1].float(), sp[:, 2].float()
+        vid = torch.arange(V, device=depths.device).repeat(sp.shape[0])
+        fid, xs, ys = t_s.repeat_interleave(V), x_s.repeat_interleave(V), y_s.repeat_interleave(V)
+        return _lift(depths[0, :, :, 0], vid, fid, xs, ys, kinv, einv)
+
+    def _local_grid_rows(self, queries, qt_d, qt, depths, intrs, extrs, kinv, einv):
+        """Local support grids of ALL queries in one pass (:221-252): project every query into every view at its own frame (one
+        device op, ONE readback instead of two .item() syncs per view and query), lay the grids out and clip them to the image on
+        the host, then lift all surviving pixels at once on the device.  queries (N,4) with frames qt_d (device) = qt (host list)
+        -> per query, the list of its views' rows (a view whose grid is wholly outside the image gives none)."""
+        num_points, V, dev = queries.shape[0], depths.shape[1], queries.device
+        height, width = depths.shape[-2:]
+        local_rows = [[] for _ in range(num_points)]
+        if not (self.local_grid_size > 0 and num_points > 0):
+            return local_rows
+        qh = torch.cat([queries[:, 1:], torch.ones(num_points, 1, device=dev)], 1)
+        cam = torch.einsum("vnij,nj->vni", extrs[0][:, qt_d], qh)
+        ph = torch.einsum("vnij,vnj->vni", intrs[0][:, qt_d], cam)
+        centres = (ph[..., :2] / ph[..., 2:]).cpu()  # (V, N, 2) pixel (x, y)
+        pix_l, vid_l, fid_l, counts = [], [], [], []
+        for i in range(num_points):
+            for v in range(V):
+                px, py = centres[v, i, 0].item(), centres[v, i, 1].item()
+                pix = points_on_a_grid(self.local_grid_size, (self.local_extent, self.local_extent), (py, px), "cpu")
+                ok = (pix[:, 0] >= 0) & (pix[:, 0] < width) & (pix[:, 1] >= 0) & (pix[:, 1] < height)
+                k = int(ok.sum())
+                counts.append(k)
+                if k:
+                    pix_l.append(pix[ok])
+                    vid_l.append(torch.full((k,), v, dtype=torch.long))
+                    fid_l.append(torch.full((k,), qt[i], dtype=torch.long))
+        if pix_l:
+            pix_all = torch.cat(pix_l).to(dev)
+            rows_all = _lift(depths[0, :, :, 0], torch.cat(vid_l).to(dev), torch.cat(fid_l).to(dev), pix_all[:, 0], pix_all[:, 1], kinv, einv)
+            o = 0
+            for j, k in enumerate(counts):  # (query-major, then view; empty grids have no rows)
+                if k:
+                    local_rows[j // V].append(rows_all[o:o + k])
+                    o += k
+        return local_rows
+
+    # ---- dispatch: each mode returns (traj_e (1,T,N,3), vis_e (1,T,N), the model's NaN flags) ------------------------------------
+    def _run_joint(self, rgbs, depths, queries, support, fwd):
+        """One forward of [the queries; the support rows] (:341-360)."""
+        n = queries.shape[0]
+        res = self.model(rgbs, depths=depths, query_points=torch.cat([queries, support], 0)[None], **fwd)
+        return res["traj_e"][:, :, :n, :], res["vis_e"][:, :, :n], [getattr(self.model, "last_nan_flag", None)]
+
+    def _run_groups(self, rgbs, depths, queries, support, fwd, groups):
+        """Joint mode per group: every id's queries with the support rows, all sets through one grouped forward."""
+        T, dev = rgbs.shape[2], rgbs.device
+        traj_e = torch.zeros(1, T, queries.shape[0], 3, device=dev)
+        vis_e = torch.zeros(1, T, queries.shape[0], device=dev)
+        rows = [torch.from_numpy(g).to(dev) for g in groups]
+        qs = [torch.cat([queries[r], support], 0)[None] for r in rows]
+        for r, res in zip(rows, self.model.forward_grouped(rgbs, depths, qs, **fwd)):
+            traj_e[:, :, r] = res["traj_e"][:, :, :len(r)]
+            vis_e[:, :, r] = res["vis_e"][:, :, :len(r)]
+        return traj_e, vis_e, [getattr(self.model, "last_nan_flag", None)]
+
+    def _run_single_point(self, rgbs, depths, queries, support, fwd, kinv, einv):
+        """One forward per query (or per ``single_point_group_size`` queries) with its local grids (:191-339)."""
+        T, dev, num_points = rgbs.shape[2], rgbs.device, queries.shape[0]
+        intrs, extrs = fwd["intrs"], fwd["extrs"]
+        traj_e = torch.zeros(1, T, num_points, 3, device=dev)
+        vis_e = torch.zeros(1, T, num_points, device=dev)
+        qt_d = queries[:, 0].long()
+        qt = qt_d.cpu().tolist()
+        # The N forwards differ only in their queries: encoder, feature pyramid and point clouds are built ONCE and
+        # shared (SURVEY section 8f rank 1; the reference re-encodes the clip for every query).  Every forward reads
+        # frames >= its own first query frame only, so one store from the earliest query frame serves them all.
+        if hasattr(self.model, "build_frame_store"):
+            # (the global support grid starts at frame 0; backward tracking reads every frame before a query's too)
+            t_first = 0 if (self.grid_size > 0 or self.backward_tracking or not qt) else max(0, min(qt))
+            r0 = rgbs[0].contiguous() if rgbs.dtype == torch.uint8 else _f32(rgbs[0])
+            fwd = dict(fwd, frame_store=self.model.build_frame_store(r0, _f32(depths[0]), _f32(intrs[0]), _f32(extrs[0]), t0=t_first))
+        local_rows = self._local_grid_rows(queries, qt_d, qt, depths, intrs, extrs, kinv, einv)
+        # The per-query forwards are independent (each has its own 64 virtual tracks, :254-275) and tiny -- a few hundred
+        # tracks, pure launch-latency chains -- so they are issued round-robin on a few HIP streams and overlap on the GPU.
+        G = max(1, int(self.single_point_group_size))
+        if G > 1 and not hasattr(self.model, "forward_grouped"):
+            raise NotImplementedError("single_point_group_size > 1 needs a model with forward_grouped")
+        n_calls = (num_points + G - 1) // G
+        n_streams = max(1, min(self.single_point_streams, n_calls)) if dev.type == "cuda" else 1
+        main = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
+        streams = self._streams(dev, n_streams) if n_streams > 1 else []
+        nan_flags = []
+        for s_ in streams:
+            s_.wait_stream(main)
+        for c in range(n_calls):
+            ctx = torch.cuda.stream(streams[c % n_streams]) if streams else contextlib.nullcontext()
+            with ctx:  # (everything of a call, its input rows included, is enqueued on its own stream)
+                ids = range(c * G, min((c + 1) * G, num_points))
+                qs = [torch.cat([queries[i:i + 1]] + local_rows[i] + [support], 0)[None] for i in ids]
+                if G == 1:
+                    res_l = [self.model(rgbs, depths=depths, query_points=qs[0], **fwd)]
+                else:  # G query sets through one launch sequence (MVTracker.forward_grouped)
+                    res_l = self.model.forward_grouped(rgbs, depths, qs, **fwd)  # (the same options as the per-query calls)
+                for i, res in zip(ids, res_l):
+                    traj_e[:, :, i] = res["traj_e"][:, :, 0]
+                    vis_e[:, :, i] = res["vis_e"][:, :, 0]
+                nan_flags.append(getattr(self.model, "last_nan_flag", None))
+        for s_ in streams:
+            main.wait_stream(s_)
+        return traj_e, vis_e, nan_flags
+
+    def _nan_guard(self, flags):
+        """Deferred NaN guard of the model (reference mvtracker.py:401-404 logs in the iteration where the NaN appears): the caller is
+        about to copy the tracks to the host anyway, so ONE flag read at the end of ``forward`` / ``finish`` costs nothing."""
+        flags = [f.reshape(()) for f in flags if f is not None]
+        self.last_nan = bool(flags) and int(torch.stack(flags).max().item()) != 0
+        if self.last_nan:
+            log.error("Got NaN values in coords, perhaps the training exploded")
 
     # ---- forward ---------------------------------------------------------------------------
     @torch.no_grad()
@@ -232,92 +446,31 @@ class EvaluationPredictor(torch.nn.Module):
             raise NotImplementedError
         if self.sift_size > 0:
             raise NotImplementedError
-        groups = None if query_groups is None else self._query_groups(query_groups, num_points)  # (refused before any launch)
+        groups = None if query_groups is None else self._query_groups(query_groups, num_points)
         hip.require_device(rgbs)
-        dev = rgbs.device
-        V, T = num_views, num_frames
         self.last_track_overlay = None
-        if track_overlay is not None:  # checked before anything is launched; drawn after the tracking, on the raw frames
+        if track_overlay is not None:  # checked before anything is launched; drawn after the tracking
             from . import overlay
             overlay._check(track_overlay)
-            overlay_rgbs, overlay_query_frames = rgbs, query_points_3d[0, :, 0]
-        # (uint8 frames stay uint8 unless they have to be resized: the encoder's first kernel converts them)
-        if not (rgbs.dtype == torch.uint8 and self.interp_shape is None):
-            rgbs = rgbs.to(torch.float32)
-        rgbs = rgbs.contiguous()
-        depths = depths.to(torch.float32).contiguous()
-        intrs = intrs.to(torch.float32)
-        extrs = extrs.to(torch.float32)
-        query_points_3d = query_points_3d.to(torch.float32)
-        if depth_cleaning is not None:  # before the normalisation and the resize
-            from . import clean
-            depths = clean.clean_depths(depths, intrs, extrs, depth_cleaning, depths_conf=depths_conf)[0]
-        self.last_camera_correction = None
-        if camera_alignment is not None:  # after the cleaning, before the normalisation and the resize
-            from . import align
-            if isinstance(camera_alignment, align.CameraCorrection):
-                correction = camera_alignment
-            elif isinstance(camera_alignment, align.CameraAlignment):
-                correction = align.align_cameras(depths, intrs, extrs, camera_alignment, depths_conf=depths_conf)
-            else:
-                raise ValueError(f"camera_alignment must be None, a CameraAlignment or a CameraCorrection, got {camera_alignment!r}")
-            self.last_camera_correction = correction
-            extrs_uncorrected, extrs = extrs, correction.apply(extrs)
-        self.last_reprojection_report = self.last_reprojection_report_before = None
-        if reprojection_check is not None:  # after the cleaning and the alignment, before the normalisation and the resize
-            from . import reproject
-            if camera_alignment is not None:
-                self.last_reprojection_report_before = reproject.reprojection_report(rgbs, depths, intrs, extrs_uncorrected, reprojection_check,
-                                                                                     depths_conf=depths_conf)
-            self.last_reprojection_report = reproject.reprojection_report(rgbs, depths, intrs, extrs, reprojection_check, depths_conf=depths_conf)
-        if track_overlay is not None:  # the caller's cameras: before the normalisation and the resize
-            overlay_intrs, overlay_extrs = intrs, extrs
-        # scene normalisation, from the raw inputs (a nearest resize with rescaled intrinsics keeps world points); the support
-        # points below are built from the transformed depths and cameras, so they need nothing of their own
-        xf = self._scene_transform(scene_transform, (depths, intrs, extrs, depths_conf))
-        self.last_scene_transform = xf
-        if xf is not None:
-            depths, extrs, query_points_3d, _ = xf.apply(depths=depths, extrs=extrs, query_points=query_points_3d)
-
-        if self.interp_shape is None:  # evaluation_predictor_3dpt.py:72-87
-            height, width = height_raw, width_raw
-        else:
-            height, width = self.interp_shape
-            r = torch.empty(1, V, T, 3, height, width, device=dev)
-            hip.resize_nearest(rgbs, r, V * T * 3, height_raw, width_raw, height, width)
-            d = torch.empty(1, V, T, 1, height, width, device=dev)
-            hip.resize_nearest(depths, d, V * T, height_raw, width_raw, height, width)
-            rgbs, depths = r, d
-            rs = torch.tensor([[width / width_raw, 0, 0], [0, height / height_raw, 0], [0, 0, 1]], device=dev,
-                              dtype=intrs.dtype)
-            intrs = torch.einsum("ij,BVTjk->BVTik", rs, intrs)
-
+        caller_rgbs, caller_query_frames = rgbs, query_points_3d[0, :, 0]  # the overlay is drawn on the caller's own frames
+        # the clip stages, in the order the docstring promises; everything up to the resize works on the raw-resolution clip
+        rgbs, depths, intrs, extrs = _cast(rgbs, depths, intrs, extrs, self.interp_shape)
+        queries = query_points_3d.to(torch.float32)
+        depths = _clean(depths, intrs, extrs, depth_cleaning, depths_conf)
+        extrs, extrs_uncorrected = self._align(depths, intrs, extrs, camera_alignment, depths_conf)
+        self._reproject(rgbs, depths, intrs, extrs, extrs_uncorrected, reprojection_check, depths_conf)
+        caller_intrs, caller_extrs = intrs, extrs  # the overlay's cameras: before the normalisation and the resize
+        xf = self.last_scene_transform = self._scene_transform(scene_transform, (depths, intrs, extrs, depths_conf))
+        depths, extrs, queries = _normalise(xf, depths, extrs, queries)
+        rgbs, depths, intrs = _resize(rgbs, depths, intrs, self.interp_shape)
+        # support points, in the reference's order: grid rows, then uniform rows
         kinv, einv = self._invert(intrs[0], extrs[0])
-        support = torch.zeros(0, 4, device=dev)
-        if self.grid_size > 0:  # :101-120
-            pix = points_on_a_grid(self.grid_size, (height, width), device=dev)
-            rows = []
-            for t in range(0, T, max(1, T // self.n_grids_per_view)):
-                for v in range(V):
-                    rows.append(self._support_rows(depths[0, v, t, 0], pix, kinv[v, t], einv[v, t], t))
-            support = torch.cat(rows, 0)
-
-        if self.num_uniformly_sampled_pts > 0:  # :147-190
-            # Uniformly sampled support points: (t, y, x) rows from get_uniformly_sampled_pts -- the same two torch draws as the
-            # reference, from the global generator of the tensors' device -- lifted into the world through EVERY view's depth map
-            # (sample-major, then view), with the reference's argument order kept as it is: the column it calls y is scaled by the
-            # WIDTH and the one it calls x by the HEIGHT (:424-426), and out-of-map coordinates are clamped by the sampler.
-            sp = get_uniformly_sampled_pts(self.num_uniformly_sampled_pts, T, (height, width), device=dev)[0]
-            t_s, y_s, x_s = sp[:, 0].long(), sp[:, 1].float(), sp[:, 2].float()
-            vid = torch.arange(V, device=dev).repeat(sp.shape[0])
-            fid, xs, ys = t_s.repeat_interleave(V), x_s.repeat_interleave(V), y_s.repeat_interleave(V)
-            z = _bilinear_sample_depth_multi(depths[0, :, :, 0], vid, fid, xs, ys)
-            camm = torch.einsum("mij,mj->mi", kinv[vid, fid], torch.stack([xs, ys, torch.ones_like(xs)], 1)) * z[:, None]
-            ei = einv[vid, fid]
-            world = torch.einsum("mij,mj->mi", ei[:, :, :3], camm) + ei[:, :, 3]
-            support = torch.cat([support, torch.cat([fid[:, None].to(world.dtype), world], 1)], 0)
-
-        nan_flags = []
+        support = torch.zeros(0, 4, device=rgbs.device)
+        if self.grid_size > 0:
+            support = self._grid_rows(depths, kinv, einv, range(0, num_frames, max(1, num_frames // self.n_grids_per_view)))
+        if self.num_uniformly_sampled_pts > 0:
+            support = torch.cat([support, self._uniform_rows(depths, kinv, einv)], 0)
+        # dispatch: the model's keyword arguments are the same in every mode
         fwd = dict(intrs=intrs, extrs=extrs, iters=self.n_iters, save_debug_logs=save_debug_logs,
                    debug_logs_path=debug_logs_path, query_points_view=query_points_view, **kwargs)
         if self.backward_tracking:
@@ -325,112 +478,18 @@ class EvaluationPredictor(torch.nn.Module):
                 raise NotImplementedError("backward_tracking with single_point_group_size > 1: forward_grouped has no backward tracking "
                                           "(use group size 1)")
             fwd["backward_tracking"] = True
-        if self.single_point:  # :191-339, one forward per query with its local grids
-            traj_e = torch.zeros(1, T, num_points, 3, device=dev)
-            vis_e = torch.zeros(1, T, num_points, device=dev)
-            qt_d = query_points_3d[0, :, 0].long()
-            qt = qt_d.cpu().tolist()
-            # The N forwards differ only in their queries: encoder, feature pyramid and point clouds are built ONCE and
-            # shared (the reference re-encodes the clip for every query).  Every forward reads
-            # frames >= its own first query frame only, so one store from the earliest query frame serves them all.
-            if hasattr(self.model, "build_frame_store"):
-                f32 = lambda t_: t_.to(torch.float32).contiguous()
-                # (the global support grid starts at frame 0; backward tracking reads every frame before a query's too)
-                t_first = 0 if (self.grid_size > 0 or self.backward_tracking or not qt) else max(0, min(qt))
-                r0 = rgbs[0].contiguous() if rgbs.dtype == torch.uint8 else f32(rgbs[0])
-                fwd["frame_store"] = self.model.build_frame_store(r0, f32(depths[0]), f32(intrs[0]), f32(extrs[0]),
-                                                                  t0=t_first)
-            # Local support grids of ALL queries in one pass (:221-252): project every query into every view at its own frame
-            # (one device op, ONE readback instead of two .item() syncs per view and query), lay the grids out and clip them to
-            # the image on the host, then sample depth / unproject all surviving pixels at once on the device.
-            local_rows = [[] for _ in range(num_points)]
-            if self.local_grid_size > 0 and num_points > 0:
-                qh = torch.cat([query_points_3d[0, :, 1:], torch.ones(num_points, 1, device=dev)], 1)
-                cam = torch.einsum("vnij,nj->vni", extrs[0][:, qt_d], qh)
-                ph = torch.einsum("vnij,vnj->vni", intrs[0][:, qt_d], cam)
-                centres = (ph[..., :2] / ph[..., 2:]).cpu()  # (V, N, 2) pixel (x, y)
-                pix_l, vid_l, fid_l, counts = [], [], [], []
-                for i in range(num_points):
-                    for v in range(V):
-                        px, py = centres[v, i, 0].item(), centres[v, i, 1].item()
-                        pix = points_on_a_grid(self.local_grid_size, (self.local_extent, self.local_extent), (py, px), "cpu")
-                        ok = (pix[:, 0] >= 0) & (pix[:, 0] < width) & (pix[:, 1] >= 0) & (pix[:, 1] < height)
-                        k = int(ok.sum())
-                        counts.append(k)
-                        if k:
-                            pix_l.append(pix[ok])
-                            vid_l.append(torch.full((k,), v, dtype=torch.long))
-                            fid_l.append(torch.full((k,), qt[i], dtype=torch.long))
-                if pix_l:
-                    pix_all = torch.cat(pix_l).to(dev)
-                    vid, fid = torch.cat(vid_l).to(dev), torch.cat(fid_l).to(dev)
-                    z = _bilinear_sample_depth_multi(depths[0, :, :, 0], vid, fid, pix_all[:, 0], pix_all[:, 1])
-                    phm = torch.cat([pix_all, torch.ones_like(pix_all[:, :1])], 1)
-                    camm = torch.einsum("mij,mj->mi", kinv[vid, fid], phm) * z[:, None]
-                    ei = einv[vid, fid]
-                    world = torch.einsum("mij,mj->mi", ei[:, :, :3], camm) + ei[:, :, 3]
-                    rows_all = torch.cat([fid[:, None].to(world.dtype), world], 1)
-                    o = 0
-                    for i in range(num_points):
-                        for v in range(V):
-                            k = counts[i * V + v]
-                            if k:
-                                local_rows[i].append(rows_all[o:o + k])
-                                o += k
-            # The per-query forwards are independent (each has its own 64 virtual tracks, :254-275) and tiny -- a few hundred
-            # tracks, pure launch-latency chains -- so they are issued round-robin on a few HIP streams and overlap on the GPU.
-            G = max(1, int(self.single_point_group_size))
-            if G > 1 and not hasattr(self.model, "forward_grouped"):
-                raise NotImplementedError("single_point_group_size > 1 needs a model with forward_grouped")
-            n_calls = (num_points + G - 1) // G
-            n_streams = max(1, min(self.single_point_streams, n_calls)) if dev.type == "cuda" else 1
-            main = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
-            streams = self._streams(dev, n_streams) if n_streams > 1 else []
-            for s_ in streams:
-                s_.wait_stream(main)
-            for c in range(n_calls):
-                ctx = torch.cuda.stream(streams[c % n_streams]) if streams else contextlib.nullcontext()
-                with ctx:  # (everything of a call, its input rows included, is enqueued on its own stream)
-                    ids = range(c * G, min((c + 1) * G, num_points))
-                    qs = [torch.cat([query_points_3d[0, i:i + 1]] + local_rows[i] + [support], 0)[None] for i in ids]
-                    if G == 1:
-                        res_l = [self.model(rgbs, depths=depths, query_points=qs[0], **fwd)]
-                    else:  # G query sets through one launch sequence (MVTracker.forward_grouped)
-                        res_l = self.model.forward_grouped(rgbs, depths, qs, **fwd)  # (the same options as the per-query calls)
-                    for i, res in zip(ids, res_l):
-                        traj_e[:, :, i] = res["traj_e"][:, :, 0]
-                        vis_e[:, :, i] = res["vis_e"][:, :, 0]
-                    nan_flags.append(getattr(self.model, "last_nan_flag", None))
-            for s_ in streams:
-                main.wait_stream(s_)
-        elif groups is not None:  # joint mode per group: every id's queries with the support rows, one grouped forward
-            traj_e = torch.zeros(1, T, num_points, 3, device=dev)
-            vis_e = torch.zeros(1, T, num_points, device=dev)
-            rows = [torch.from_numpy(g).to(dev) for g in groups]
-            qs = [torch.cat([query_points_3d[0, r], support], 0)[None] for r in rows]
-            for r, res in zip(rows, self.model.forward_grouped(rgbs, depths, qs, **fwd)):
-                traj_e[:, :, r] = res["traj_e"][:, :, :len(r)]
-                vis_e[:, :, r] = res["vis_e"][:, :, :len(r)]
-            nan_flags.append(getattr(self.model, "last_nan_flag", None))
-        else:  # joint mode, :341-360
-            q = torch.cat([query_points_3d[0], support], 0)[None]
-            res = self.model(rgbs, depths=depths, query_points=q, **fwd)
-            traj_e = res["traj_e"][:, :, :num_points, :]
-            vis_e = res["vis_e"][:, :, :num_points]
-            nan_flags.append(getattr(self.model, "last_nan_flag", None))
-        # deferred NaN guard of the model (reference mvtracker.py:401-404 logs in the iteration where the NaN appears): the
-        # caller is about to copy the tracks to the host anyway, so one flag read here costs nothing
-        flags = [f for f in nan_flags if f is not None]
-        if flags and int(torch.stack([f.reshape(()) for f in flags]).max().item()) != 0:
-            log.error("Got NaN values in coords, perhaps the training exploded")
-            self.last_nan = True
+        if self.single_point:
+            traj_e, vis_e, nan_flags = self._run_single_point(rgbs, depths, queries[0], support, fwd, kinv, einv)
+        elif groups is not None:
+            traj_e, vis_e, nan_flags = self._run_groups(rgbs, depths, queries[0], support, fwd, groups)
         else:
-            self.last_nan = False
+            traj_e, vis_e, nan_flags = self._run_joint(rgbs, depths, queries[0], support, fwd)
+        self._nan_guard(nan_flags)
         if xf is not None:
             traj_e = xf.restore_tracks(traj_e)
         if track_overlay is not None:
-            self.last_track_overlay = overlay.render_track_overlays(overlay_rgbs[0], traj_e[0], vis_e[0] > self.visibility_threshold, overlay_query_frames,
-                                                                    overlay_intrs[0], overlay_extrs[0], track_overlay)
+            self.last_track_overlay = overlay.render_track_overlays(caller_rgbs[0], traj_e[0], vis_e[0] > self.visibility_threshold, caller_query_frames,
+                                                                    caller_intrs[0], caller_extrs[0], track_overlay)
         return {"traj_e": traj_e, "vis_e": vis_e > self.visibility_threshold, "vis_e_as_prob": vis_e}
 
     @staticmethod
@@ -475,14 +534,13 @@ class EvaluationPredictor(torch.nn.Module):
         if depth_cleaning is not None:
             from . import clean
             clean._check(depth_cleaning)
-        xf = self._scene_transform(scene_transform)
-        self.last_scene_transform = xf
+        xf = self.last_scene_transform = self._scene_transform(scene_transform)
         return _PredictorStream(self, query_points_3d, ring_blocks, xf, depth_cleaning)
 
 
 class _PredictorStream:
-    """``EvaluationPredictor.open_stream``: per-block resize, intrinsics rescale and threshold exactly as in ``forward``; the
-    support grid is added as queries (behind the caller's) when the first frame arrives."""
+    """``EvaluationPredictor.open_stream``: every pushed block goes through ``forward``'s own cast, clean, normalise and resize and
+    comes back thresholded as there; the support grid is added as queries (behind the caller's) when the first frame arrives."""
 
     def __init__(self, predictor, query_points_3d, ring_blocks, scene_transform=None, depth_cleaning=None):
         self.p = predictor
@@ -501,50 +559,25 @@ class _PredictorStream:
         traj = res["traj_e"][:, :, :self.num_points, :]
         if self.xf is not None:
             traj = self.xf.restore_tracks(traj)
-        return {"frames": res["frames"], "traj_e": traj, "vis_e": vis > self.p.visibility_threshold,
-                "vis_e_as_prob": vis}
+        return {"frames": res["frames"], "traj_e": traj, "vis_e": vis > self.p.visibility_threshold, "vis_e_as_prob": vis}
 
     @torch.no_grad()
     def push(self, rgbs, depths, intrs, extrs, depths_conf=None):
         p = self.p
         with hip.device_guard(rgbs):
             hip.require_device(rgbs)
-            dev = rgbs.device
-            _, V, b, _, height_raw, width_raw = rgbs.shape
-            if not (rgbs.dtype == torch.uint8 and p.interp_shape is None):
-                rgbs = rgbs.to(torch.float32)
-            rgbs = rgbs.contiguous()
-            depths = depths.to(torch.float32).contiguous()
-            intrs, extrs = intrs.to(torch.float32), extrs.to(torch.float32)
-            if self.cleaning is not None:
-                from . import clean
-                depths = clean.clean_depths(depths, intrs, extrs, self.cleaning, depths_conf=depths_conf)[0]
-            if self.xf is not None:
-                depths, extrs, _, _ = self.xf.apply(depths=depths, extrs=extrs)
-            if p.interp_shape is not None:  # evaluation_predictor_3dpt.py:72-87, block by block
-                height, width = p.interp_shape
-                r = torch.empty(1, V, b, 3, height, width, device=dev)
-                hip.resize_nearest(rgbs, r, V * b * 3, height_raw, width_raw, height, width)
-                d = torch.empty(1, V, b, 1, height, width, device=dev)
-                hip.resize_nearest(depths, d, V * b, height_raw, width_raw, height, width)
-                rgbs, depths = r, d
-                rs = torch.tensor([[width / width_raw, 0, 0], [0, height / height_raw, 0], [0, 0, 1]], device=dev, dtype=intrs.dtype)
-                intrs = torch.einsum("ij,BVTjk->BVTik", rs, intrs)
+            rgbs, depths, intrs, extrs = _cast(rgbs, depths, intrs, extrs, p.interp_shape)
+            depths = _clean(depths, intrs, extrs, self.cleaning, depths_conf)
+            depths, extrs, _ = _normalise(self.xf, depths, extrs)
+            rgbs, depths, intrs = _resize(rgbs, depths, intrs, p.interp_shape)
             if self.first and p.grid_size > 0:  # the reference's t = 0 support grid (:101-120), from the first pushed frame
-                height, width = rgbs.shape[-2:]
                 kinv, einv = p._invert(intrs[0, :, :1], extrs[0, :, :1])
-                pix = points_on_a_grid(p.grid_size, (height, width), device=dev)
-                rows = [p._support_rows(depths[0, v, 0, 0], pix, kinv[v, 0], einv[v, 0], 0) for v in range(V)]
-                self.session.add_queries(torch.cat(rows, 0)[None])
+                self.session.add_queries(p._grid_rows(depths, kinv, einv, [0])[None])
             self.first = False
             return self._result(self.session.push(rgbs, depths, intrs, extrs))
 
     @torch.no_grad()
     def finish(self):
         res = self.session.finish()
-        if int(self.session.nan_flag.item()) != 0:  # (the deferred NaN guard, as at the end of ``forward``)
-            log.error("Got NaN values in coords, perhaps the training exploded")
-            self.p.last_nan = True
-        else:
-            self.p.last_nan = False
+        self.p._nan_guard([self.session.nan_flag])
         return self._result(res)
