@@ -10,6 +10,7 @@
 // so scores and probabilities never leave registers and the output lands with the query on the lane (row stores).
 // KS > 1 splits the keys of one query chunk over KS waves; their (m, l, O^T) states are merged through LDS.
 #include "common.h"
+#include "launch_plan.h"
 
 namespace {
 
@@ -459,9 +460,10 @@ extern "C" int mvt_attention_bf16(const void* q, int ldq, long long q_gs, long l
     else LAUNCH_T(KS, false, dim3((unsigned)(BLOCKS)), THREADS, WS);       \
   } while (0)
   constexpr int NSPLIT = MVT_ATTN_NSPLIT;
-  MVT_REQUIRE(!partials_only || (nk >= 512 && nchunk < 256 && workspace && ((nk + 31) / 32) % NSPLIT == 0));
-  if (nk >= 512 && nchunk < 256 && workspace && ((nk + 31) / 32) % NSPLIT == 0) {
-    // too few (group, head) chunks to fill the chip: cut the keys over NSPLIT workgroups per chunk as well
+  const mvt_plan::AttnForm form = mvt_plan::attn_form(groups, heads, nq, nk, workspace != nullptr);
+  MVT_REQUIRE(!partials_only || form.kernel == mvt_plan::ATTN_KEYSPLIT);
+  if (form.kernel == mvt_plan::ATTN_KEYSPLIT) {
+    // too few (group, head) chunks to fill the chip: the keys are cut over NSPLIT workgroups per chunk as well
     MVT_REQUIRE((uintptr_t)workspace % 16 == 0);
 #define WS workspace
     if (bf_in) LAUNCH_T(4, true, dim3((unsigned)nchunk, NSPLIT), 256, workspace);
@@ -473,10 +475,10 @@ extern "C" int mvt_attention_bf16(const void* q, int ldq, long long q_gs, long l
     return mvt_launch_status();
   }
 #define WS nullptr
-  if (nk >= 512 && nchunk < 1024) {
-    LAUNCH(4, nchunk, 256);
+  if (form.kernel == mvt_plan::ATTN_KS4) {
+    LAUNCH(4, form.blocks, 256);
   } else {
-    LAUNCH(1, mvt_cdiv(nchunk, 4), 256);
+    LAUNCH(1, form.blocks, 256);
   }
 #undef WS
 #undef LAUNCH
@@ -499,19 +501,15 @@ extern "C" int mvt_attention_bf16_segmented(const void* q, int ldq, long long q_
   constexpr int NSPLIT = MVT_ATTN_NSPLIT;
   // the form of the ungrouped call with this segment's (nq, nk): 0 key split over NSPLIT workgroups (+ merge), 1 KS 4, 2 KS 1
   auto form_of = [&](int s, long long* blocks) {
-    const long long nchunk = (long long)groups * heads * ((nq[s] + 63) / 64);
-    if (nk[s] >= 512 && nchunk < 256 && workspace && ((nk[s] + 31) / 32) % NSPLIT == 0) {
-      *blocks = nchunk;
-      return 0;
-    }
-    *blocks = nk[s] >= 512 && nchunk < 1024 ? nchunk : mvt_cdiv(nchunk, 4);
-    return nk[s] >= 512 && nchunk < 1024 ? 1 : 2;
+    const mvt_plan::AttnForm f = mvt_plan::attn_form(groups, heads, nq[s], nk[s], workspace != nullptr);
+    *blocks = f.blocks;
+    return (int)f.kernel;
   };
   long long ws_need = 0;
   for (int s = 0; s < nseg; ++s) {
     MVT_REQUIRE(nq[s] > 0 && nk[s] > 0 && q_row0[s] >= 0 && k_row0[s] >= 0);
     long long nb;
-    if (form_of(s, &nb) == 0) ws_need += (long long)NSPLIT * nb * MVT_PART_FLOATS;
+    if (form_of(s, &nb) == 0) ws_need += mvt_plan::attn_partials_floats(nb);
   }
   MVT_REQUIRE(ws_need <= ws_floats || ws_need == 0);
   long long ws_next = 0;  // each key-split segment owns NSPLIT * nchunk partial records of the workspace
@@ -528,7 +526,7 @@ extern "C" int mvt_attention_bf16_segmented(const void* q, int ldq, long long q_
         t.qrow[i] = tm.qrow[i] = q_row0[s];
         t.krow[i] = tm.krow[i] = k_row0[s];
         t.ws[i] = tm.ws[i] = form == 0 ? ws_next : 0;
-        if (form == 0) ws_next += (long long)NSPLIT * nb * MVT_PART_FLOATS;
+        if (form == 0) ws_next += mvt_plan::attn_partials_floats(nb);
         t.blk[i + 1] = t.blk[i] + nb;
         tm.blk[i + 1] = tm.blk[i] + mvt_cdiv(nb, 4);
         t.n = tm.n = i + 1;

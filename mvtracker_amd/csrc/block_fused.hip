@@ -17,6 +17,7 @@
 //                                    gelu(H) is written to LDS as bf16 [m][j] for fc2 (double buffered, one barrier
 //                                    per chunk)
 #include "common.h"
+#include "launch_plan.h"
 #include <stdlib.h>
 
 namespace {
@@ -1597,6 +1598,71 @@ extern "C" int mvt_pack_frag_bf16(const unsigned short* w, int ld, int N, int K,
   return mvt_launch_status();
 }
 
+using mvt_plan::BlockPlan;
+using mvt_plan::BlockSwitches;
+
+// The once-per-process tuning switches of the block kernels (launch_plan.h has what each one selects), read on the first call that
+// asks for them: MVT_BLOCK_NMB forces the row blocks per workgroup (atoi of the value), MVT_BLOCK_NOSPLIT set keeps a block with a
+// workspace off the split path, MVT_TIME_NMB1=0 / MVT_FRAME_NMB1=0 switch the small-tile forms of the time / per-frame blocks off.
+static const BlockSwitches& block_switches() {
+  static const char* force = getenv("MVT_BLOCK_NMB");
+  static const bool no_split = getenv("MVT_BLOCK_NOSPLIT") != nullptr;
+  static const char* time_nmb1 = getenv("MVT_TIME_NMB1");
+  static const char* frame_nmb1 = getenv("MVT_FRAME_NMB1");
+  static const BlockSwitches sw = {force ? atoi(force) : 0, force != nullptr, no_split, !(time_nmb1 && atoi(time_nmb1) == 0),
+                                   !(frame_nmb1 && atoi(frame_nmb1) == 0)};
+  return sw;
+}
+// ... for the composite updater call (updater.hip), whose launch sequence depends on the forms the block entries will take
+__attribute__((visibility("hidden"))) BlockSwitches mvt_detail_block_switches() { return block_switches(); }
+
+// The follow-up projections of an entry into a.next (row_hi = 0: up to the last row); false: an argument is refused.
+static bool take_nexts(BlockArgs& a, const mvt_block_next* next, int n_next, long long M) {
+  if (n_next < 0 || n_next > MVT_BLOCK_MAX_NEXT || (n_next > 0 && !next)) return false;
+  a.n_next = n_next;
+  for (int q = 0; q < n_next; ++q) {
+    const mvt_block_next& nx = next[q];
+    if (!(nx.w && nx.b && nx.y && nx.N > 0 && nx.N <= 4 * C && nx.ldy % 4 == 0 && nx.ldy >= nx.N)) return false;
+    if (!(nx.y_bf16 == 0 || nx.y_bf16 == 1) || (nx.lnw == nullptr) != (nx.lnb == nullptr)) return false;
+    if (((uintptr_t)nx.lnw % 16) || ((uintptr_t)nx.lnb % 16) || ((uintptr_t)nx.w % 16) || ((uintptr_t)nx.y % 16)) return false;
+    if (!(nx.row_lo >= 0 && (nx.row_hi == 0 || nx.row_hi > nx.row_lo))) return false;
+    a.next[q] = nx;
+    if (nx.row_hi == 0) a.next[q].row_hi = M;
+  }
+  return true;
+}
+
+// Launches a plan: every instantiation of block_fused_bf16 that the library holds is named here, once (the order of the cases is the
+// order of the kernels in the code object).  A refused plan launches nothing.
+static int launch_plan(const BlockPlan& p, const BlockArgs& a, void* stream) {
+  MVT_REQUIRE(p.ok && (!p.uses_ws || (uintptr_t)a.ws % 16 == 0));
+  for (int i = 0; i < p.n; ++i) {
+    const mvt_plan::BlockLaunch& l = p.l[i];
+    const dim3 g(l.gx, l.gy, l.gz), b(NT);
+    hipStream_t s = mvt_stream(stream);
+    switch (l.nmb * 100 + l.mode * 10 + l.att) {
+      case 200: hipLaunchKernelGGL((block_fused_bf16<2, 0, 0>), g, b, 0, s, a); break;
+      case 110: hipLaunchKernelGGL((block_fused_bf16<1, 1, 0>), g, b, 0, s, a); break;
+      case 120: hipLaunchKernelGGL((block_fused_bf16<1, 2, 0>), g, b, 0, s, a); break;
+      case 100: hipLaunchKernelGGL((block_fused_bf16<1, 0, 0>), g, b, 0, s, a); break;
+      case 101: hipLaunchKernelGGL((block_fused_bf16<1, 0, 1>), g, b, 0, s, a); break;
+      case 201: hipLaunchKernelGGL((block_fused_bf16<2, 0, 1>), g, b, 0, s, a); break;
+      case 113: hipLaunchKernelGGL((block_fused_bf16<1, 1, 3>), g, b, 0, s, a); break;
+      case 125: hipLaunchKernelGGL((block_fused_bf16<1, 2, 5>), g, b, 0, s, a); break;
+      case 102: hipLaunchKernelGGL((block_fused_bf16<1, 0, 2>), g, b, 0, s, a); break;
+      case 202: hipLaunchKernelGGL((block_fused_bf16<2, 0, 2>), g, b, 0, s, a); break;
+      case 112: hipLaunchKernelGGL((block_fused_bf16<1, 1, 2>), g, b, 0, s, a); break;
+      case 206: hipLaunchKernelGGL((block_fused_bf16<2, 0, 6>), g, b, 0, s, a); break;
+      case 234: hipLaunchKernelGGL((block_fused_bf16<2, 3, 4>), g, b, 0, s, a); break;
+      case 230: hipLaunchKernelGGL((block_fused_bf16<2, 3, 0>), g, b, 0, s, a); break;
+      default: return MVT_ERR_ARG;  // (no plan function returns another form)
+    }
+  }
+  return mvt_launch_status();
+}
+
+// Every block entry: argument checks, BlockArgs, take_nexts, plan_deal, the plan of launch_plan.h, launch.
+
 extern "C" int mvt_block_fused_bf16(float* x, int ldx, const void* att, int att_bf16, int ldatt, int Ko, const unsigned short* wo, int ldwo,
                                     const float* bo, const unsigned short* w1, int ldw1, const float* b1, const unsigned short* w2,
                                     int ldw2, const float* b2, int H, const mvt_block_next* next, int n_next, long long M, int Cc,
@@ -1604,48 +1670,22 @@ extern "C" int mvt_block_fused_bf16(float* x, int ldx, const void* att, int att_
   MVT_REQUIRE(x && w1 && b1 && w2 && b2 && M > 0 && Cc == C && H > 0 && H % 256 == 0 && H <= 4 * C);
   MVT_REQUIRE(ldx % 4 == 0 && ldx >= C);
   MVT_REQUIRE(!att || (wo && bo && Ko == 288 && ldatt % 4 == 0 && ldatt >= Ko));
-  MVT_REQUIRE(n_next >= 0 && n_next <= MVT_BLOCK_MAX_NEXT && (n_next == 0 || next));
   MVT_REQUIRE(((uintptr_t)x % 16 == 0) && ((uintptr_t)att % 16 == 0) && ((uintptr_t)wo % 16 == 0) && ((uintptr_t)w1 % 16 == 0) &&
               ((uintptr_t)w2 % 16 == 0));
   BlockArgs a{};
   a.x = x; a.ldx = ldx; a.att = (const float*)att; a.att_bf16 = att_bf16 ? 1 : 0; a.ldatt = ldatt; a.Ko = Ko; a.wo = wo; a.bo = bo; a.ldwo = ldwo;
-  a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.ldw1 = ldw1; a.ldw2 = ldw2; a.H = H; a.M = M; a.n_next = n_next;
-  for (int q = 0; q < n_next; ++q) {
-    const mvt_block_next& nx = next[q];
-    MVT_REQUIRE(nx.w && nx.b && nx.y && nx.N > 0 && nx.N <= 4 * C && nx.ldy % 4 == 0 && nx.ldy >= nx.N);
-    MVT_REQUIRE(nx.y_bf16 == 0 || nx.y_bf16 == 1);
-    MVT_REQUIRE((nx.lnw == nullptr) == (nx.lnb == nullptr) && ((uintptr_t)nx.lnw % 16 == 0) && ((uintptr_t)nx.lnb % 16 == 0) && ((uintptr_t)nx.w % 16 == 0) && ((uintptr_t)nx.y % 16 == 0));
-    MVT_REQUIRE(nx.row_lo >= 0 && (nx.row_hi == 0 || nx.row_hi > nx.row_lo));
-    a.next[q] = nx;
-    if (nx.row_hi == 0) a.next[q].row_hi = M;
-  }
+  a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.ldw1 = ldw1; a.ldw2 = ldw2; a.H = H; a.M = M; a.ws = workspace;
+  MVT_REQUIRE(take_nexts(a, next, n_next, M));
   plan_deal(a);
-  static const char* force = getenv("MVT_BLOCK_NMB");  // tuning override
-  const int nmb = force ? atoi(force) : (M >= 4096 ? 2 : 1);  // 64-row workgroups measured 1.6x faster than 128-row ones at M = 12288
-  static const bool no_split = getenv("MVT_BLOCK_NOSPLIT") != nullptr;
-  a.ws = workspace;
-  if (nmb == 2) {
-    hipLaunchKernelGGL((block_fused_bf16<2, 0, 0>), dim3((unsigned)mvt_cdiv(M, 64)), dim3(NT), 0, mvt_stream(stream), a);
-  } else if (workspace && !no_split && M <= 2048 && M % 32 == 0) {  // (whole 32-row tiles: the workspace is tile-native)
-    MVT_REQUIRE((uintptr_t)workspace % 16 == 0);
-    const unsigned tiles = (unsigned)mvt_cdiv(M, 32);
-    hipLaunchKernelGGL((block_fused_bf16<1, 1, 0>), dim3(tiles, (unsigned)(H / 256)), dim3(NT), 0, mvt_stream(stream), a);
-    int maxblk = 1;
-    for (int q = 0; q < n_next; ++q) maxblk = (next[q].N + 31) / 32 > maxblk ? (next[q].N + 31) / 32 : maxblk;
-    const unsigned slices = n_next ? (unsigned)mvt_cdiv(maxblk, 8) : 1u;
-    hipLaunchKernelGGL((block_fused_bf16<1, 2, 0>), dim3(tiles, slices), dim3(NT), 0, mvt_stream(stream), a);
-  } else {
-    hipLaunchKernelGGL((block_fused_bf16<1, 0, 0>), dim3((unsigned)mvt_cdiv(M, 32)), dim3(NT), 0, mvt_stream(stream), a);
-  }
-  return mvt_launch_status();
+  return launch_plan(mvt_plan::plan_block(M, H, workspace != nullptr, mvt_plan::pass2_slices(next, n_next), block_switches()), a, stream);
 }
 
-// The block with its attention inside (ATT 1 / 2 of block_fused_bf16).
+// The block with its attention inside (ATT 1 / 2 / 3 / 6 of block_fused_bf16).
 extern "C" int mvt_attn_block_fused_bf16(float* x, int ldx, const mvt_block_attn* attn, const unsigned short* wo, const float* bo,
                                          const unsigned short* w1, const float* b1, const unsigned short* w2, const float* b2, int H,
                                          const mvt_block_next* next, int n_next, long long M, int Cc, float* workspace, void* stream) {
   MVT_REQUIRE(x && attn && wo && bo && w1 && b1 && w2 && b2 && M > 0 && Cc == C && H > 0 && H % 256 == 0 && H <= 4 * C);
-  MVT_REQUIRE(ldx % 4 == 0 && ldx >= C && n_next >= 0 && n_next <= MVT_BLOCK_MAX_NEXT && (n_next == 0 || next));
+  MVT_REQUIRE(ldx % 4 == 0 && ldx >= C);
   MVT_REQUIRE(attn->heads == 6 && attn->dim_head == DHA && attn->S >= 1 && M % attn->S == 0);
   MVT_REQUIRE(attn->kind == MVT_ATTN_PARTIALS || (attn->kind == MVT_ATTN_FRAME_CTX && attn->q && attn->ldq % 8 == 0 && attn->ldq >= 288) ||
               (attn->q && attn->k && attn->v && attn->ldq % 8 == 0 && attn->ldkv % 8 == 0 && attn->ldq >= 288 && attn->ldkv >= 288));
@@ -1653,117 +1693,54 @@ extern "C" int mvt_attn_block_fused_bf16(float* x, int ldx, const mvt_block_attn
   MVT_REQUIRE(((uintptr_t)attn->q % 16 == 0) && ((uintptr_t)attn->k % 16 == 0) && ((uintptr_t)attn->v % 16 == 0));
   BlockArgs a{};
   a.x = x; a.ldx = ldx; a.att = nullptr; a.Ko = 288; a.wo = wo; a.bo = bo; a.ldwo = 288;
-  a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.ldw1 = C; a.ldw2 = H; a.H = H; a.M = M; a.n_next = n_next; a.ws = workspace;
+  a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.ldw1 = C; a.ldw2 = H; a.H = H; a.M = M; a.ws = workspace;
   a.aq = attn->q; a.ak = attn->k; a.av = attn->v; a.ldaq = attn->ldq; a.ldakv = attn->ldkv; a.S = attn->S; a.nkeys = attn->n_keys;
-  for (int q = 0; q < n_next; ++q) {
-    const mvt_block_next& nx = next[q];
-    MVT_REQUIRE(nx.w && nx.b && nx.y && nx.N > 0 && nx.N <= 4 * C && nx.ldy % 4 == 0 && nx.ldy >= nx.N);
-    MVT_REQUIRE((nx.y_bf16 == 0 || nx.y_bf16 == 1) && (nx.lnw == nullptr) == (nx.lnb == nullptr) && ((uintptr_t)nx.lnw % 16 == 0) && ((uintptr_t)nx.lnb % 16 == 0));
-    MVT_REQUIRE(((uintptr_t)nx.w % 16 == 0) && ((uintptr_t)nx.y % 16 == 0) && nx.row_lo >= 0 && (nx.row_hi == 0 || nx.row_hi > nx.row_lo));
-    a.next[q] = nx;
-    if (nx.row_hi == 0) a.next[q].row_hi = M;
-  }
+  MVT_REQUIRE(take_nexts(a, next, n_next, M));
   plan_deal(a);
-  const int S = attn->S;
+  const int S = attn->S, slices = mvt_plan::pass2_slices(next, n_next);
+  const bool ws = workspace != nullptr, defer = attn->defer_pass2 != 0;
+  BlockPlan plan{};
   if (attn->kind == MVT_ATTN_TIME) {
-    // tiles of whole tracks: S <= 32 keys per track (one MFMA key block), 64 / S tracks per 64-row tile
-    MVT_REQUIRE(S <= 32 && !workspace);
-    // Round 4, the small-M form: 32-row tiles (S = 12: two whole tracks, 24 rows) while they fit ONE round of workgroups at one per
-    // CU -- twice the weight bytes in total, half the work per workgroup: a whole updater call 903 -> 819 us at 342 tracks, 932 -> 861
-    // at 448; at 512 tracks (288 workgroups) 929 -> 977: not there.  MVT_TIME_NMB1=0: the 64-row tiles everywhere.
-    static const bool small_tiles = !(getenv("MVT_TIME_NMB1") && atoi(getenv("MVT_TIME_NMB1")) == 0);
-    if (small_tiles && mvt_cdiv(M, (32 / S) * S) <= 256) {
-      a.bmv = (32 / S) * S;
-      hipLaunchKernelGGL((block_fused_bf16<1, 0, 1>), dim3((unsigned)mvt_cdiv(M, a.bmv)), dim3(NT), 0, mvt_stream(stream), a);
-      return mvt_launch_status();
-    }
-    a.bmv = (64 / S) * S;
-    hipLaunchKernelGGL((block_fused_bf16<2, 0, 1>), dim3((unsigned)mvt_cdiv(M, a.bmv)), dim3(NT), 0, mvt_stream(stream), a);
+    plan = mvt_plan::plan_time(M, S, ws, block_switches());
   } else if (attn->kind == MVT_ATTN_PARTIALS) {
-    // attention tile from the key-split partials (64 queries = the virtual tokens, frame = group): split path only
-    MVT_REQUIRE(attn->partials && attn->n_splits >= 1 && attn->n_splits <= MVT_ATTN_NSPLIT && attn->n_keys == 64 && M == 64LL * S);
-    MVT_REQUIRE(workspace && (uintptr_t)workspace % 16 == 0 && M <= 2048 && (uintptr_t)attn->partials % 16 == 0);
+    MVT_REQUIRE(attn->partials && (uintptr_t)attn->partials % 16 == 0);
     a.parts = attn->partials; a.nsplit = attn->n_splits;
-    const unsigned tiles = (unsigned)mvt_cdiv(M, 32);
-    a.S = S;
-    hipLaunchKernelGGL((block_fused_bf16<1, 1, 3>), dim3(2, (unsigned)(H / 256), (unsigned)S), dim3(NT), 0, mvt_stream(stream), a);
-    int maxblk = 1;
-    for (int q = 0; q < n_next; ++q) maxblk = (next[q].N + 31) / 32 > maxblk ? (next[q].N + 31) / 32 : maxblk;
-    const unsigned slices = n_next ? (unsigned)mvt_cdiv(maxblk, 8) : 1u;
-    (void)tiles;  // pass 2 on the SAME frame-major tiles (the workspace is tile-native)
-    if (!attn->defer_pass2)
-      hipLaunchKernelGGL((block_fused_bf16<1, 2, 5>), dim3(2, slices, (unsigned)S), dim3(NT), 0, mvt_stream(stream), a);
+    plan = mvt_plan::plan_partials(M, S, H, attn->n_keys, attn->n_splits, ws, defer, slices);
   } else if (attn->kind == MVT_ATTN_FRAME) {
     MVT_REQUIRE(attn->n_keys >= 1 && attn->n_keys <= 64);
-    const long long ntok = M / S;
-    // Round 4, the small-M form (BASELINE config C5: 512 tracks per GPU = 6 144 point rows): 32-token tiles.  At 64 tokens per tile
-    // the launch is 96 workgroups on 256 CUs; 192 workgroups of 32 tokens stream twice the weight bytes in total but finish the launch
-    // sooner -- a whole updater call 929 -> 882 us (tools/time_updater.py 512).  MVT_FRAME_NMB1=0: the 64-token tiles.
-    // Only while the 32-token tiles still fit ONE round of workgroups at one per CU (680 tracks: 264 workgroups, 927 -> 1 026 us).
-    static const bool small_tiles = !(getenv("MVT_FRAME_NMB1") && atoi(getenv("MVT_FRAME_NMB1")) == 0);
-    if (small_tiles && mvt_frame_small_tiles(ntok, S)) {
-      MVT_REQUIRE(!workspace);
-      hipLaunchKernelGGL((block_fused_bf16<1, 0, 2>), dim3((unsigned)mvt_cdiv(ntok, 32), 1, (unsigned)S), dim3(NT), 0, mvt_stream(stream), a);
-    } else if (ntok * S >= 4096) {
-      MVT_REQUIRE(!workspace);
-      hipLaunchKernelGGL((block_fused_bf16<2, 0, 2>), dim3((unsigned)mvt_cdiv(ntok, 64), 1, (unsigned)S), dim3(NT), 0, mvt_stream(stream), a);
-    } else {
-      // few rows (the 64 virtual tracks): two-launch split path; pass 1 (frame-major tiles, attention recomputed by each of the
-      // H / 256 chunk workgroups: it is tiny) leaves x and the MLP partials in the workspace by GLOBAL row, pass 2 is unchanged
-      MVT_REQUIRE(workspace && (uintptr_t)workspace % 16 == 0 && M <= 2048 && ntok % 32 == 0);  // (whole tiles: tile-native workspace)
-      hipLaunchKernelGGL((block_fused_bf16<1, 1, 2>), dim3((unsigned)(ntok / 32), (unsigned)(H / 256), (unsigned)S), dim3(NT), 0,
-                         mvt_stream(stream), a);
-      int maxblk = 1;
-      for (int q = 0; q < n_next; ++q) maxblk = (next[q].N + 31) / 32 > maxblk ? (next[q].N + 31) / 32 : maxblk;
-      const unsigned slices = n_next ? (unsigned)mvt_cdiv(maxblk, 8) : 1u;
-      if (!attn->defer_pass2)
-        hipLaunchKernelGGL((block_fused_bf16<1, 2, 5>), dim3((unsigned)(ntok / 32), slices, (unsigned)S), dim3(NT), 0, mvt_stream(stream), a);
-    }
+    plan = mvt_plan::plan_frame(M, S, H, ws, defer, slices, block_switches());
   } else if (attn->kind == MVT_ATTN_FRAME_CTX) {
-    // per-frame attention whose 64 context tokens are the rows of a split-path block with a deferred pass 2 (ATT 6)
     const mvt_block_ctx* cx = attn->ctx;
-    const long long ntok = M / S;
-    MVT_REQUIRE(cx && attn->n_keys == 64 && ntok * S >= 4096 && !workspace && !attn->defer_pass2);
-    MVT_REQUIRE(cx->ws && cx->b2 && cx->x && cx->chunks >= 1 && cx->chunks <= 4 && cx->ldx % 4 == 0 && cx->ldx >= C);
+    MVT_REQUIRE(cx && cx->ws && cx->b2 && cx->x && cx->ldx % 4 == 0 && cx->ldx >= C);
     MVT_REQUIRE(((uintptr_t)cx->ws % 16 == 0) && ((uintptr_t)cx->b2 % 16 == 0) && ((uintptr_t)cx->x % 16 == 0));
     MVT_REQUIRE(cx->kv.w && cx->kv.b && cx->kv.N == 2 * 288 && (cx->kv.lnw == nullptr) == (cx->kv.lnb == nullptr));
     MVT_REQUIRE(((uintptr_t)cx->kv.w % 16 == 0) && ((uintptr_t)cx->kv.lnw % 16 == 0) && ((uintptr_t)cx->kv.lnb % 16 == 0));
-    const unsigned tiles = (unsigned)mvt_cdiv(ntok, 64);
     if (cx->next.w) {
       const mvt_block_next& nx = cx->next;
       MVT_REQUIRE(nx.b && nx.y && nx.N > 0 && nx.N <= 4 * C && nx.ldy % 4 == 0 && nx.ldy >= nx.N && (nx.y_bf16 == 0 || nx.y_bf16 == 1));
       MVT_REQUIRE((nx.lnw == nullptr) == (nx.lnb == nullptr) && ((uintptr_t)nx.lnw % 16 == 0) && ((uintptr_t)nx.lnb % 16 == 0));
-      MVT_REQUIRE(((uintptr_t)nx.w % 16 == 0) && ((uintptr_t)nx.y % 16 == 0) && (nx.N + 31) / 32 <= 8 * (int)tiles);
+      MVT_REQUIRE(((uintptr_t)nx.w % 16 == 0) && ((uintptr_t)nx.y % 16 == 0));
     }
     a.c_ws = cx->ws; a.c_b2 = cx->b2; a.c_x = cx->x; a.c_ldx = cx->ldx; a.c_nch = cx->chunks; a.c_kv = cx->kv; a.c_next = cx->next;
-    hipLaunchKernelGGL((block_fused_bf16<2, 0, 6>), dim3(tiles, 1, (unsigned)S), dim3(NT), 0, mvt_stream(stream), a);
-  } else {
-    return MVT_ERR_ARG;
-  }
-  return mvt_launch_status();
+    plan = mvt_plan::plan_frame_ctx(M, S, attn->n_keys, ws, defer, cx->chunks, cx->next.w ? cx->next.N : 0);
+  }  // (any other kind: the empty plan, refused)
+  a.bmv = plan.bmv;
+  return launch_plan(plan, a, stream);
 }
 
 // Input transform + virtual tokens + first projections in one launch (ATT 4 of MODE 3).
 extern "C" int mvt_input_proj_bf16(const float* tokens, int ldtok, int token_dim, long long Mp, const unsigned short* win, const float* bin,
                                    const float* virtual_tokens, int S, float* x, int ldx, const mvt_block_next* next, int n_next, long long M,
                                    int Cc, void* stream) {
-  MVT_REQUIRE(tokens && win && bin && virtual_tokens && x && next && n_next >= 1 && n_next <= MVT_BLOCK_MAX_NEXT && Cc == C);
+  MVT_REQUIRE(tokens && win && bin && virtual_tokens && x && next && n_next >= 1 && Cc == C);
   MVT_REQUIRE(M > 0 && Mp >= 0 && Mp <= M && S >= 1 && (M - Mp) % S == 0 && token_dim >= 1 && token_dim <= 37 * 16 && ldtok >= token_dim);
   MVT_REQUIRE(ldtok % 4 == 0 && ldx % 4 == 0 && ldx >= C && ((uintptr_t)tokens % 16 == 0) && ((uintptr_t)win % 16 == 0) && ((uintptr_t)x % 16 == 0));
   BlockArgs a{};
-  a.x = x; a.ldx = ldx; a.M = M; a.n_next = n_next; a.H = 4 * C; a.ws = nullptr; a.S = S;
+  a.x = x; a.ldx = ldx; a.M = M; a.H = 4 * C; a.ws = nullptr; a.S = S;
   a.tokx = tokens; a.ldtok = ldtok; a.win = win; a.bin = bin; a.virt = virtual_tokens; a.Mp = Mp;
-  for (int q = 0; q < n_next; ++q) {
-    const mvt_block_next& nx = next[q];
-    MVT_REQUIRE(nx.w && nx.b && nx.y && nx.N > 0 && nx.N <= 4 * C && nx.ldy % 4 == 0 && nx.ldy >= nx.N);
-    MVT_REQUIRE((nx.lnw == nullptr) == (nx.lnb == nullptr) && ((uintptr_t)nx.lnw % 16 == 0) && ((uintptr_t)nx.lnb % 16 == 0) && ((uintptr_t)nx.w % 16 == 0) && ((uintptr_t)nx.y % 16 == 0));
-    MVT_REQUIRE(nx.row_lo >= 0 && (nx.row_hi == 0 || nx.row_hi > nx.row_lo) && (nx.y_bf16 == 0 || nx.y_bf16 == 1));
-    a.next[q] = nx;
-    if (nx.row_hi == 0) a.next[q].row_hi = M;
-  }
+  MVT_REQUIRE(take_nexts(a, next, n_next, M));
   plan_deal(a);
-  hipLaunchKernelGGL((block_fused_bf16<2, 3, 4>), dim3((unsigned)mvt_cdiv(M, 64)), dim3(NT), 0, mvt_stream(stream), a);
-  return mvt_launch_status();
+  return launch_plan(mvt_plan::plan_input_proj(M), a, stream);
 }
 
 // ... the same with the token rows assembled in the kernel (no token matrix): mvt_token_assemble + mvt_input_proj_bf16 in one launch.
@@ -1772,51 +1749,29 @@ extern "C" int mvt_token_input_proj_bf16(const float* coords, const float* fcorr
                                          const unsigned short* win, const float* bin, const float* virtual_tokens, float* x, int ldx,
                                          const mvt_block_next* next, int n_next, long long M, int Cc, void* stream) {
   MVT_REQUIRE(coords && fcorr && ffeats && mask_vis && pos && time_embed && win && bin && virtual_tokens && x && next);
-  MVT_REQUIRE(n_next >= 1 && n_next <= MVT_BLOCK_MAX_NEXT && Cc == C && n_tracks > 0 && S >= 1 && E > 0 && E % 2 == 0 && Fc > 0 && Cf > 0);
+  MVT_REQUIRE(n_next >= 1 && Cc == C && n_tracks > 0 && S >= 1 && E > 0 && E % 2 == 0 && Fc > 0 && Cf > 0);
   const int D = 3 * E + 3 + Fc + Cf + 2;
   const long long Mp = (long long)n_tracks * S;
   MVT_REQUIRE(D <= 37 * 16 && M >= Mp && (M - Mp) % S == 0 && ldx % 4 == 0 && ldx >= C);
   MVT_REQUIRE(((uintptr_t)win % 16 == 0) && ((uintptr_t)x % 16 == 0));
   BlockArgs a{};
-  a.x = x; a.ldx = ldx; a.M = M; a.n_next = n_next; a.H = 4 * C; a.ws = nullptr; a.S = S;
+  a.x = x; a.ldx = ldx; a.M = M; a.H = 4 * C; a.ws = nullptr; a.S = S;
   a.tokx = nullptr; a.win = win; a.bin = bin; a.virt = virtual_tokens; a.Mp = Mp;
   a.t_coords = coords; a.t_fcorr = fcorr; a.t_ffeats = ffeats; a.t_maskvis = mask_vis; a.t_pos = pos; a.t_time = time_embed;
   a.t_E = E; a.t_Fc = Fc; a.t_Cf = Cf; a.t_D = D;
-  for (int q = 0; q < n_next; ++q) {
-    const mvt_block_next& nx = next[q];
-    MVT_REQUIRE(nx.w && nx.b && nx.y && nx.N > 0 && nx.N <= 4 * C && nx.ldy % 4 == 0 && nx.ldy >= nx.N);
-    MVT_REQUIRE((nx.lnw == nullptr) == (nx.lnb == nullptr) && ((uintptr_t)nx.lnw % 16 == 0) && ((uintptr_t)nx.lnb % 16 == 0) && ((uintptr_t)nx.w % 16 == 0) && ((uintptr_t)nx.y % 16 == 0));
-    MVT_REQUIRE(nx.row_lo >= 0 && (nx.row_hi == 0 || nx.row_hi > nx.row_lo) && (nx.y_bf16 == 0 || nx.y_bf16 == 1));
-    a.next[q] = nx;
-    if (nx.row_hi == 0) a.next[q].row_hi = M;
-  }
+  MVT_REQUIRE(take_nexts(a, next, n_next, M));
   plan_deal(a);
-  hipLaunchKernelGGL((block_fused_bf16<2, 3, 4>), dim3((unsigned)mvt_cdiv(M, 64)), dim3(NT), 0, mvt_stream(stream), a);
-  return mvt_launch_status();
+  return launch_plan(mvt_plan::plan_input_proj(M), a, stream);
 }
 
 // LayerNorm + projections only: y_i = LayerNorm_i(x) . Wn_i^T + bn_i (the first time-attention q|k|v of an updater call, which no
 // preceding block can produce): pass 2 of the split path without a workspace -- x is read, never written.
 extern "C" int mvt_ln_proj_bf16(const float* x, int ldx, const mvt_block_next* next, int n_next, long long M, int Cc, void* stream) {
-  MVT_REQUIRE(x && next && n_next >= 1 && n_next <= MVT_BLOCK_MAX_NEXT && M > 0 && Cc == C && ldx % 4 == 0 && ldx >= C);
+  MVT_REQUIRE(x && next && n_next >= 1 && M > 0 && Cc == C && ldx % 4 == 0 && ldx >= C);
   MVT_REQUIRE((uintptr_t)x % 16 == 0);
   BlockArgs a{};
-  a.x = const_cast<float*>(x); a.ldx = ldx; a.M = M; a.n_next = n_next; a.H = 4 * C; a.ws = nullptr;
-  int maxblk = 1;
-  for (int q = 0; q < n_next; ++q) {
-    const mvt_block_next& nx = next[q];
-    MVT_REQUIRE(nx.w && nx.b && nx.y && nx.N > 0 && nx.N <= 4 * C && nx.ldy % 4 == 0 && nx.ldy >= nx.N);
-    MVT_REQUIRE((nx.lnw == nullptr) == (nx.lnb == nullptr) && ((uintptr_t)nx.lnw % 16 == 0) && ((uintptr_t)nx.lnb % 16 == 0) && ((uintptr_t)nx.w % 16 == 0) && ((uintptr_t)nx.y % 16 == 0));
-    MVT_REQUIRE(nx.row_lo >= 0 && (nx.row_hi == 0 || nx.row_hi > nx.row_lo) && (nx.y_bf16 == 0 || nx.y_bf16 == 1));
-    a.next[q] = nx;
-    if (nx.row_hi == 0) a.next[q].row_hi = M;
-    maxblk = (nx.N + 31) / 32 > maxblk ? (nx.N + 31) / 32 : maxblk;
-  }
+  a.x = const_cast<float*>(x); a.ldx = ldx; a.M = M; a.H = 4 * C; a.ws = nullptr;
+  MVT_REQUIRE(take_nexts(a, next, n_next, M));
   plan_deal(a);
-  if (M >= 4096)  // whole 64-row tiles, every column block in the workgroup: x and its LayerNorm are read / computed once per tile
-    hipLaunchKernelGGL((block_fused_bf16<2, 3, 0>), dim3((unsigned)mvt_cdiv(M, 64)), dim3(NT), 0, mvt_stream(stream), a);
-  else
-    hipLaunchKernelGGL((block_fused_bf16<1, 2, 0>), dim3((unsigned)mvt_cdiv(M, 32), (unsigned)mvt_cdiv(maxblk, 8)), dim3(NT), 0,
-                       mvt_stream(stream), a);
-  return mvt_launch_status();
+  return launch_plan(mvt_plan::plan_ln_proj(M, mvt_plan::pass2_slices(next, n_next)), a, stream);
 }

@@ -24,11 +24,6 @@ static inline hipStream_t mvt_stream(void* s) { return (hipStream_t)s; }
 
 static inline long long mvt_cdiv(long long a, long long b) { return (a + b - 1) / b; }
 
-// The small-M rule of the point<-virtual block (mvt_attn_block_fused_bf16, MVT_ATTN_FRAME), in one place for the kernel's entry and
-// for the updater's launch sequence, which must agree on it: 32-token tiles while the block has at least 4 096 rows and the tiles
-// still fit ONE round of workgroups at one per CU.
-static inline bool mvt_frame_small_tiles(long long ntok, long long S) { return ntok * S >= 4096 && mvt_cdiv(ntok, 32) * S <= 256; }
-
 __device__ __forceinline__ float mvt_gelu_tanh(float x) {
   // 0.5 x (1 + tanh(k)) = x * sigmoid(2k), k = sqrt(2/pi) (x + 0.044715 x^3).  ocml tanhf costs ~150 instructions
   // and dominated the fc1 epilogue; v_exp_f32 + v_rcp_f32 are 1-ulp hardware ops (relative error ~2e-7).
@@ -89,11 +84,7 @@ __device__ __forceinline__ void store_act4(float* base, long long off, const f32
   }
 }
 
-// Key-split attention partials in global memory (attention_mfma.hip writes, its merge variants and block_fused.hip's ATT 3 read):
-// one record per (split, chunk) = 17 quads x 64 lanes x 4 floats, QUAD-major, so that every access of a wave is one contiguous
-// 1-KiB piece (lane-major 68-float records made every load and store of a wave touch 64 different cache lines).  Quad 0 =
-// (m[0], m[1], l[0], l[1]); quad 1 + (mb*2 + db)*4 + g = accumulator registers 4g..4g+3 of O^T block (mb, db).
-#define MVT_PART_FLOATS (17 * 64 * 4)
+// Offset of (record, quad, lane) in the key-split attention partials (records of MVT_PART_FLOATS floats: launch_plan.h has the layout).
 __device__ __forceinline__ long long mvt_part_off(long long rec, int quad, int lane) { return (rec * 17 + quad) * 256 + lane * 4; }
 
 // Segment table of the segmented attention launches (attention.hip, attention_mfma.hip), passed BY VALUE as a kernel argument:

@@ -7,7 +7,11 @@
 //   virtual self attention -> virtual block (-> p2v k|v and the NEXT layer's time q|k|v of the virtual rows)
 //   point<-virtual attention -> point block (-> the next layer's time q|k|v of the point rows)
 #include "common.h"
+#include "launch_plan.h"
 #include <stdlib.h>
+
+// the once-per-process tuning switches of the block entries (block_fused.hip)
+__attribute__((visibility("hidden"))) mvt_plan::BlockSwitches mvt_detail_block_switches();
 
 namespace {
 
@@ -18,7 +22,8 @@ struct Layout {
   int ldh;
 };
 
-constexpr int H_ = 256, HEADS = 6, DH_ = 48, INNER = HEADS * DH_, NV = 64, MLP = 1024, OUT = 131;
+constexpr int H_ = 256, HEADS = mvt_plan::UPD_HEADS, DH_ = mvt_plan::UPD_DIM_HEAD, INNER = mvt_plan::UPD_INNER, NV = mvt_plan::UPD_NV,
+              MLP = mvt_plan::UPD_MLP, OUT = 131;
 
 // G > 1: G independent query sets (mvt_updateformer_forward_tokens_grouped), each with its own NV virtual tracks
 inline Layout layout(long long n, long long S, long long G = 1) {
@@ -32,7 +37,7 @@ inline Layout layout(long long n, long long S, long long G = 1) {
   L.qp = take(Mp * INNER * 2);
   L.att = take(M * INNER * 2);
   L.split_ws = take((MLP / 256 + 1) * Mv * H_ * 4);
-  L.attn_ws = take(G * 4LL * S * HEADS * 1 * 64 * 68 * 4);  // key-split partials of the 64-query virtual<-point attention (per set)
+  L.attn_ws = take(mvt_plan::attn_partials_floats(G, S, HEADS) * 4);  // key-split partials of the 64-query virtual<-point attention (per set)
   L.vrep = G > 1 ? take(G * NV * H_ * 4) : 0;               // the learned virtual tokens repeated for every set
   L.ldh = (OUT + 3) / 4 * 4;
   L.h1 = take(Mp * L.ldh * 4);
@@ -136,8 +141,13 @@ static int updater_run(const mvt_updater_weights* w, const float* x, int ldx, co
     return mvt_attn_block_fused_bf16(xr, H_, &at, b.out.w, b.out.b, b.fc1.w, b.fc1.b, b.fc2.w, b.fc2.b, MLP, nx, nn, rows, H_, ws, stream);
   };
   const bool grouped = G > 1;
-  const bool fuse_time = (w->fuse_attention & 1) && S <= 32, fuse_p2v = (w->fuse_attention & 2) && !grouped,
-             fuse_vs = (w->fuse_attention & 4) && !grouped;
+  // the forms of this call's launches (launch_plan.h): which attentions run inside their block kernels.  FRAME_CTX / deferred (bit 5):
+  // the virtual-self block's pass 2 runs inside the point<-virtual block, whose first workgroups of a frame also evaluate the next
+  // layer's time q|k|v of the virtual rows
+  const mvt_plan::UpdaterForms forms = mvt_plan::updater_forms(n, S, G, w->fuse_attention, mvt_detail_block_switches());
+  const bool fuse_time = forms.time == mvt_plan::TIME_FUSED, parts = forms.v2p == mvt_plan::V2P_PARTIALS,
+             fold_vs = forms.vself == mvt_plan::VSELF_DEFERRED, fuse_vs = forms.vself == mvt_plan::VSELF_FRAME,
+             fuse_p2v = forms.p2v == mvt_plan::P2V_FRAME;
   // segment tables of the space attentions (G > 1): point rows of set g from row off_g * S, virtual rows from Mp + g * NV * S
   // (relative to the point / virtual bases the calls below pass)
   long long* prow = nullptr;
@@ -169,16 +179,6 @@ static int updater_run(const mvt_updater_weights* w, const float* x, int ldx, co
     MVT_TRY(mvt_broadcast_rows_repeat(w->virtual_tokens, vrep, H_, NV, 1, H_, G, stream));
     vtokens = vrep;
   }
-  // bit 5: the virtual-self block's pass 2 runs inside the point<-virtual block (needs both attentions in their block kernels)
-  // (the first workgroups of a frame also evaluate the next layer's time q|k|v of the virtual rows, 8 column blocks each: enough tiles)
-  // (not in the small-M form: while 32-token tiles of the point<-virtual block fit one round of workgroups -- ceil(n / 32) * S <= 256,
-  //  the same rule as in mvt_attn_block_fused_bf16 -- that block runs on them, twice the workgroups, and the virtual-self block keeps
-  //  its own second launch: measured faster at 400 / 512 tracks, 958 -> 906 / 929 -> 882 us per call)
-  static const bool small_m = !(getenv("MVT_FRAME_NMB1") && atoi(getenv("MVT_FRAME_NMB1")) == 0);
-  const bool small_form = small_m && mvt_frame_small_tiles(n, S);
-  const bool fold_vs = (w->fuse_attention & 32) && !grouped && fuse_p2v && fuse_vs && (long long)n * S >= 4096 && !small_form && MLP / 256 <= 4 &&
-                       8 * ((n + 63) / 64) >= (3 * INNER + 31) / 32;
-
   // tokens: input transform of the point rows, learned virtual tokens repeated over the S frames (blocks.py:456-459), and the
   // first time-attention q|k|v projection -- one launch when the fragment-major input weights are available
   {
@@ -218,11 +218,10 @@ static int updater_run(const mvt_updater_weights* w, const float* x, int ldx, co
     // ---- virtual <- point cross attention, per frame: group = frame (stride 1 row), items stride S rows
     unsigned short* qv = qkv + Mp * ld3;  // q|k|v rows of the virtual tokens
     unsigned short* av = att + Mp * INNER;
-    // the key-split path of mvt_attention_bf16 needs >= 512 keys in 4 x whole 32-key blocks; otherwise the plain form
-    const bool parts = (w->fuse_attention & 16) && !grouped && n >= 512 && ((n + 31) / 32) % MVT_ATTN_NSPLIT == 0;
+    // (parts: mvt_attention_bf16 takes its key-split path and leaves the merge to the block kernel; otherwise the plain form)
     if (grouped)
       MVT_TRY(mvt_attention_bf16_segmented(qv, ld3, 1, S, qkv + INNER, qkv + 2 * INNER, ld3, 1, S, av, INNER, S, HEADS, DH_, BF, G, vrow, nvs,
-                                           prow, gn, attn_ws, G * 4LL * S * HEADS * 64 * 68, stream));
+                                           prow, gn, attn_ws, mvt_plan::attn_partials_floats(G, S, HEADS), stream));
     else
       MVT_TRY(mvt_attention_bf16(qv, ld3, 1, S, qkv + INNER, qkv + 2 * INNER, ld3, 1, S, av, INNER, S, NV, n, HEADS, DH_,
                                  BF | (parts ? MVT_ATTN_PARTIALS_ONLY : 0), attn_ws, stream));
@@ -276,7 +275,7 @@ static int updater_run(const mvt_updater_weights* w, const float* x, int ldx, co
         at.q = qp; at.ctx = &cx;
         MVT_TRY(mvt_attn_block_fused_bf16(tok, H_, &at, p2v.out.w, p2v.out.b, p2v.fc1.w, p2v.fc1.b, p2v.fc2.w, p2v.fc2.b, MLP, &nx, last ? 0 : 1,
                                           Mp, H_, nullptr, stream));
-      } else if (fuse_p2v && Mp >= 4096) {
+      } else if (fuse_p2v) {
         MVT_TRY(attn_block(p2v, tok, Mp, MVT_ATTN_FRAME, qp, INNER, qv + INNER, qv + 2 * INNER, NV, &nx, last ? 0 : 1, nullptr));
       } else {
         if (grouped)

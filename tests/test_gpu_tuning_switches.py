@@ -1,7 +1,8 @@
 """The exact suites once more under every tuning switch that a process reads only once.
 
-The library reads a handful of tuning variables as `static const ... = getenv("MVT_...")` on the first call of an entry.
-`monkeypatch.setenv` inside the pytest process cannot reach them, and the code behind them -- row tiles of 16 and of 4 output rows,
+The library reads a handful of tuning variables as `static const ... = getenv("MVT_...")`, once per process: on the first call of
+the entry that holds the line, or -- the four of the block kernels, which block_fused.hip keeps together in block_switches() -- on
+the first call of any block entry or of the composite updater.  `monkeypatch.setenv` inside the pytest process cannot reach them, and the code behind them -- row tiles of 16 and of 4 output rows,
 1 / 2 / 4 / 8 kNN queries per wave on either side of the default, the 64-row block tiles on a few rows and the 32-row ones on many,
 the folded context form at a few hundred tracks, the generic bf16 apply / concat kernels, the unfolded strided blocks of the
 composite encoder -- is what the next change of a threshold or a default puts under production shapes.  The exact suites give
@@ -144,7 +145,7 @@ Row = collections.namedtuple("Row", "name env reaches nodes expect child timeout
 # One row per (variable, value).  `child`: the rows with the same letter share one child process (CHILDREN below).  One child per
 # row measured 89 s on the MI355X -- about 4 s of interpreter start, imports and code-object load per child, 60 s in all -- against
 # 43 s for the five exact files themselves, so rows whose variables are read in disjoint source files are merged (DESIGN.md "Tuning
-# switches under test" has both sets of times).  No variable of the block kernels (block_fused.hip / updater.hip) shares a child
+# switches under test" has both sets of times).  No variable of the block kernels (all read in block_fused.hip) shares a child
 # with another, nor do the two of encoder.hip: five children, as many as MVT_KNN_Q has values.
 # Disjoint source files are not disjoint code paths: the composite-encoder nodes of fold-downsample-0 call mvt_instnorm_apply and so
 # also run under MVT_APPLY_GENERIC=1 (child c).  The updater nodes of time-nmb1-0 / frame-nmb1-0 run with the MVT_KNN_Q of their child
@@ -397,7 +398,7 @@ def test_table_names_every_once_per_process_switch():
         assert len(set(ch.nodes)) == len(ch.nodes) == ch.expect, ch.name
     assert sum(ch.expect for ch in CHILDREN) == sum(r.expect for r in SWITCHES)
     # the sources that hold the switches of two rows are disjoint for every pair the table could merge later
-    assert {f for f, _ in sites["MVT_FRAME_NMB1"]} == {"block_fused.hip", "updater.hip"} and {f for f, _ in sites["MVT_KNN_Q"]} == {"knn_corr.hip"}
+    assert {f for f, _ in sites["MVT_FRAME_NMB1"]} == {"block_fused.hip"} and {f for f, _ in sites["MVT_KNN_Q"]} == {"knn_corr.hip"}
 
 
 @pytest.mark.parametrize("env", [{}, {"MVT_ROWS_NW8": "1"}, {"MVT_ROWS_NW8": "2"}], ids=lambda e: "-".join(e.values()) or "default")
