@@ -16,6 +16,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "conv_detail.h"
 
 namespace {
 
@@ -72,16 +73,18 @@ struct RowsArgs {
   int ldw2;
 };
 
-constexpr int TR = 8;            // output rows per workgroup (stem and the stride-1 3x3 kernels)
-constexpr int TC = 32;           // output columns per workgroup
-constexpr int CK = 32;           // channels per chunk
-constexpr int LDP = CK + 8;      // bf16 per pixel / weight-row slot (80 B)
-constexpr int MAXC = 512;        // input channels the in-kernel normalisation supports
+// tile constants that the dispatch uses too (conv_plan.h has their meaning)
+using mvt_plan::TR;
+using mvt_plan::TC;
+using mvt_plan::CK;
+using mvt_plan::LDP;
+using mvt_plan::MAXC;
+using mvt_plan::SKW;
+using mvt_plan::BG_BN;
+using mvt_plan::stage_elems;
 
 // Shared epilogue of the row-tile kernels: bias, output (fp32 / bf16), per-32-pixel statistics.  acc[i][j] is the 32 x 32
 // block (row i of this wave, 32-channel block j); yw = first output row of the wave.
-// Elements of the per-wave LDS staging tile of the bf16 epilogue: 32 pixels x (BN + 8) channels
-template <int TN> constexpr int stage_elems() { return 32 * (TN * 32 + 8); }
 
 // Statistics: every (tile row, channel) leaves its (sum, sum of squares) over the row's 32 pixels in the workgroup's LDS table
 // wst[tile row][BN][2] (pre-zeroed; lrow0 = first tile row of this wave); the kernel adds the rows up in a fixed order and writes
@@ -92,7 +95,7 @@ __device__ __forceinline__ void epilogue_rows(const f32x16 (&acc)[TM][TN], const
   constexpr int BNS = WLD;  // channels per row of the statistics table (the workgroup's channel count)
   const int r = lane & 31, h = lane >> 5;
 #ifndef MVT_EPI_NO_TR
-  if constexpr (STAGED && TN * 32 * 36 <= stage_elems<TN>()) {  // (96-channel tiles: the transposed tile does not fit their staging area)
+  if constexpr (STAGED && TN * 32 * 36 <= stage_elems(TN)) {  // (96-channel tiles: the transposed tile does not fit their staging area)
     // Round 3: bf16 output through a TRANSPOSED staging tile.  The accumulator layout has the channel on the lane and four runs of
     // four consecutive pixels in the registers: as [pixel][channel] staging every value was its own 2-byte LDS store (16 per 32 x 32
     // block and lane; in-kernel stamps: the epilogue of a 64-channel tile cost as much as its MFMAs).  Staged as [channel][pixel]
@@ -379,6 +382,7 @@ template <int TM, int KS, int S, int NW> struct Geo {
   static constexpr bool SPLITROW = KS == 3 && S == 2;
   static constexpr int RS = SPLITROW ? 2 * HALF : PC;                  // slots per patch row
   static constexpr int NSLOT = PR * RS;
+  static_assert(NSLOT == mvt_plan::patch_slots(TM, KS, S, NW), "the dispatch sizes the staged epilogue by the same patch");
   static constexpr int PAD = KS == 3 ? 1 : 0;
   static constexpr int PSTEP = KS == 1 ? S : 1;                        // input pixels per patch pixel (1x1: only the sampled ones)
   __host__ __device__ static constexpr int tap_col(int kw) { return SPLITROW ? (kw & 1) * HALF + (kw >> 1) : kw; }
@@ -398,7 +402,7 @@ __global__ __launch_bounds__(64 * NW, DS ? 2 : ((TM == 2 && TN == 2 && INB && NW
   constexpr int NWF = (KS * BN * 4 + NT - 1) / NT;        // 16-B weight pieces per thread per stage (KS taps x BN rows x 64 B)
   __shared__ __attribute__((aligned(16))) unsigned short Ps[G::NSLOT * LDP];
   __shared__ __attribute__((aligned(16))) unsigned short Ws[KS * BN * LDP];
-  static_assert(!STAGED || NW * stage_elems<TN>() <= G::NSLOT * LDP, "the bf16 epilogue's staging tiles reuse the patch LDS");
+  static_assert(!STAGED || NW * stage_elems(TN) <= G::NSLOT * LDP, "the bf16 epilogue's staging tiles reuse the patch LDS");
   __shared__ __attribute__((aligned(16))) float Sst[2 * MAXC];  // (mean, rstd) of the input channels of this image
   __shared__ float wst[G::ROWS * BN * 2];                       // per (tile row, channel) output statistics
 
@@ -699,7 +703,7 @@ __global__ __launch_bounds__(64 * NW, DS ? 2 : ((TM == 2 && TN == 2 && INB && NW
   // same channels of pixel e+1 -- one 4-byte (bf16) / 8-byte (fp32) store per lane and register PAIR instead of a 2-byte
   // store per register (the scalar bf16 stores alone were a third of the 64-channel layers' time).
   // (the loop above ended with a barrier: patch and weights are dead, the staging tiles reuse their LDS)
-  epilogue_rows<TM, TN, TN == 3, STAGED>(acc, p, img, Ho, Wo, y0 + wm * TM, x0, n0, tiles_x, tx, lane, Ps + wm * stage_elems<TN>(), wst,
+  epilogue_rows<TM, TN, TN == 3, STAGED>(acc, p, img, Ho, Wo, y0 + wm * TM, x0, n0, tiles_x, tx, lane, Ps + wm * stage_elems(TN), wst,
                                          wm * TM);
   CSTAMP(121);
   if (p.out_part) {
@@ -714,7 +718,7 @@ __global__ __launch_bounds__(64 * NW, DS ? 2 : ((TM == 2 && TN == 2 && INB && NW
     __syncthreads();  // (write_tile_stats has read the table the second epilogue overwrites)
     RowsArgs p2 = p;
     p2.out = p.out2; p2.bias = p.bias2; p2.out_part = p.out_part2;
-    epilogue_rows<TM, TN, TN == 3, STAGED>(dacc, p2, img, Ho, Wo, y0 + wm * TM, x0, n0, tiles_x, tx, lane, Ps + wm * stage_elems<TN>(), wst,
+    epilogue_rows<TM, TN, TN == 3, STAGED>(dacc, p2, img, Ho, Wo, y0 + wm * TM, x0, n0, tiles_x, tx, lane, Ps + wm * stage_elems(TN), wst,
                                            wm * TM);
     if (p2.out_part) {
       __syncthreads();
@@ -735,7 +739,6 @@ __global__ __launch_bounds__(64 * NW, DS ? 2 : ((TM == 2 && TN == 2 && INB && NW
 // generic im2col GEMM spent 680 us per 24 images on this layer (45 GFLOP); the output write is the only real cost.
 constexpr int SPR = 2 * TR + 5, SPC = 2 * TC + 6;   // 21 x 70 patch pixels (one spare column keeps rows 16-B aligned)
 constexpr int SNP = SPR * SPC;
-constexpr int SKW = 7 * 32;                         // K
 constexpr int SLW = SKW + 8;                        // LDS weight row stride (bf16): 464 B, conflict-free b128 reads
 
 template <int TN, bool STAGED>
@@ -839,8 +842,8 @@ __global__ __launch_bounds__(256) void stem7x7_rows_bf16(RowsArgs p) {
   }
 
   __syncthreads();  // every wave is done with the patch / weights: Ws becomes the staging area
-  static_assert(4 * stage_elems<TN>() <= BN * SLW, "staging tiles fit the weight buffer");
-  epilogue_rows<TM, TN, true, STAGED>(acc, p, img, Ho, Wo, y0 + wm * TM, x0, 0, tiles_x, tx, lane, Ws + wm * stage_elems<TN>(), wst, wm * TM);
+  static_assert(4 * stage_elems(TN) <= BN * SLW, "staging tiles fit the weight buffer");
+  epilogue_rows<TM, TN, true, STAGED>(acc, p, img, Ho, Wo, y0 + wm * TM, x0, 0, tiles_x, tx, lane, Ws + wm * stage_elems(TN), wst, wm * TM);
   if (p.out_part) {
     __syncthreads();
     write_tile_stats<TR, BN>(p, wst, img, ty * tiles_x + tx, 0, t);
@@ -866,7 +869,6 @@ __global__ __launch_bounds__(256) void stem7x7_rows_bf16(RowsArgs p) {
 //   * the input patch is fetched ONCE per pixel tile (the 64-channel tiles re-read it four times through L2).
 // Same accumulation order per accumulator (chunk, kh, kw, k-step) and the same epilogue as conv_rows_bf16: bit-identical outputs
 // and statistics (tests/test_gpu_ops.py::test_conv_big_tile_bit_identical).
-constexpr int BG_BN = 256;                               // output channels per workgroup
 constexpr int BG_PC = TC + 2;                            // 34 patch columns (10 patch rows)
 constexpr int BG_PSLOTS = (TR + 2) * BG_PC;              // 340 pixel slots of 64 B
 constexpr int BG_PINSTR = 24;                            // DMA wave-instructions per patch chunk: 3 per wave (21.25 carry pixels)
@@ -878,7 +880,7 @@ constexpr int BG_LDS = 2 * BG_PBYTES + 2 * BG_WBYTES;    // 147 456 B of the 163
 static_assert(BG_PSLOTS * 64 <= BG_PBYTES, "patch slots fit the buffer");
 static_assert(BG_WBYTES / 1024 == 6 * 8, "six weight DMA wave-instructions per wave and stage");
 static_assert(BG_LDS <= 160 * 1024 && BG_WST <= 2 * BG_WBYTES, "one workgroup per CU");
-static_assert(8 * stage_elems<2>() * 2 <= 2 * BG_PBYTES, "the epilogue's staging tiles reuse the patch buffers");
+static_assert(8 * stage_elems(2) * 2 <= 2 * BG_PBYTES, "the epilogue's staging tiles reuse the patch buffers");
 
 __device__ __attribute__((aligned(64))) unsigned mvt_conv_zero_page[16];  // source of the DMA lanes that fall outside the image
 
@@ -1066,7 +1068,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_big_bf16(RowsArgs p) {
   for (int i = lane; i < TM * 64 * 2; i += 64) wst[((wm * TM + (i >> 7)) * BG_BN + wn * 64) * 2 + (i & 127)] = 0.f;
 
   epilogue_rows<TM, TN, false, true, BG_BN>(acc, p, img, Ho, Wo, y0 + wm * TM, x0, n0 + wn * 64, tiles_x, tx, lane,
-                                             reinterpret_cast<unsigned short*>(Pb) + wave * stage_elems<TN>(), wst + wn * 64 * 2, wm * TM);
+                                             reinterpret_cast<unsigned short*>(Pb) + wave * stage_elems(TN), wst + wn * 64 * 2, wm * TM);
   CSTAMP(125);
   if (p.out_part) {
     __syncthreads();
@@ -1088,154 +1090,106 @@ extern "C" int mvt_debug_clear_conv_stamps() {
 }
 #endif
 
-// tile rows of the variant the launcher picks for (kernel size, stride) -- shared with mvt_conv2d_stat_slots
-static int rows_nw8() {
-  static const int v = getenv("MVT_ROWS_NW8") ? atoi(getenv("MVT_ROWS_NW8")) : 0;  // tuning override
-  return v;
+// The one reading place of the convolution dispatch's switches (tuning overrides; conv_plan.h says what each selects).
+// MVT_ROWS_NW8 and MVT_FOLD_DOWNSAMPLE hold for the process; MVT_CONV_BIG is read on every call (A/B runs, tests).
+static mvt_plan::ConvSwitches conv_switches() {
+  static const int nw8 = getenv("MVT_ROWS_NW8") ? atoi(getenv("MVT_ROWS_NW8")) : 0;
+  static const bool no_fold = getenv("MVT_FOLD_DOWNSAMPLE") && atoi(getenv("MVT_FOLD_DOWNSAMPLE")) == 0;
+  const char* big = getenv("MVT_CONV_BIG");
+  return mvt_plan::ConvSwitches{nw8, !big || atoi(big) != 0, !no_fold};
 }
-__attribute__((visibility("hidden"))) int mvt_detail_conv_rows_tile_rows(int ksize, int stride, int Ho) {
-  if (ksize == 3 && stride == 1) return (rows_nw8() == 1 && Ho % 16 == 0) ? 16 : (rows_nw8() == 2 ? 4 : 8);
-  if (ksize == 3) return 4;
-  if (ksize == 7) return TR;  // stem
-  return 8;
+mvt_plan::ConvSwitches mvt_detail_conv_switches() { return conv_switches(); }
+
+// (no dynamic LDS anywhere in this library: every kernel's group segment is its static size, checked at compile time against
+//  the 160 KiB a workgroup may own -- see DESIGN.md section 5, "a queue abort worth remembering")
+
+// The instantiations of conv_rows_bf16 without the fused downsample: six (TM, KS, S, NW) geometries x 64- / 96-channel tiles x
+// fp32 / bf16 input, each with the plain epilogue and, where its staging tiles fit the patch, with the staged one.
+template <int TM, int TN, int KS, int S, int NW, bool INB>
+static void launch_rows_tile(const mvt_plan::ConvPlan& p, const RowsArgs& a, hipStream_t stream) {
+  constexpr bool fits = mvt_plan::rows_staged_fits(TM, TN, KS, S, NW);
+  const dim3 grid((unsigned)p.grid), wg(64 * NW);
+  if (fits && p.staged) hipLaunchKernelGGL((conv_rows_bf16<TM, TN, KS, S, INB, NW, fits>), grid, wg, 0, stream, a);
+  else hipLaunchKernelGGL((conv_rows_bf16<TM, TN, KS, S, INB, NW, false>), grid, wg, 0, stream, a);
 }
-// slots of the fused statistics: one per workgroup tile (tile rows x 32 output pixels)
-__attribute__((visibility("hidden"))) int mvt_detail_conv_rows_slots(int Ho, int Wo, int tile_rows) {
-  return (int)(mvt_cdiv(Ho, tile_rows) * mvt_cdiv(Wo, TC));
+template <int TM, int KS, int S, int NW>
+static void launch_rows_geo(const mvt_plan::ConvPlan& p, const RowsArgs& a, hipStream_t stream) {
+  if (p.tn == 3) {
+    if (p.inb) launch_rows_tile<TM, 3, KS, S, NW, true>(p, a, stream);
+    else launch_rows_tile<TM, 3, KS, S, NW, false>(p, a, stream);
+  } else {
+    if (p.inb) launch_rows_tile<TM, 2, KS, S, NW, true>(p, a, stream);
+    else launch_rows_tile<TM, 2, KS, S, NW, false>(p, a, stream);
+  }
+}
+static int launch_rows(const mvt_plan::ConvPlan& p, const RowsArgs& a, hipStream_t stream) {
+  // the geometry as the decimal digits TM KS S NW: <2, 3, 1, 8> is 2318.  These six are the ones plan_conv produces (tile_rows 16,
+  // 4, 8 of the 3x3 / stride 1; 3x3 / stride 2; 1x1 at either stride) -- the GEOS of tests/test_conv_plan_host.py
+  switch (((p.tm * 10 + p.ks) * 10 + p.s) * 10 + p.nw) {
+    case 2318: launch_rows_geo<2, 3, 1, 8>(p, a, stream); break;
+    case 1314: launch_rows_geo<1, 3, 1, 4>(p, a, stream); break;
+    case 2314: launch_rows_geo<2, 3, 1, 4>(p, a, stream); break;
+    case 1324: launch_rows_geo<1, 3, 2, 4>(p, a, stream); break;
+    case 2114: launch_rows_geo<2, 1, 1, 4>(p, a, stream); break;
+    case 2124: launch_rows_geo<2, 1, 2, 4>(p, a, stream); break;
+    default: return MVT_ERR_ARG;
+  }
+  return mvt_launch_status();
 }
 
-// 3x3 (pad 1) or 1x1 (pad 0) convolution, stride 1 or 2, Cin % 32 == 0, bf16 mode
-__attribute__((visibility("hidden"))) int mvt_detail_conv_rows(const void* in, const unsigned short* w, int ldw, const float* bias, void* out,
-                                                               int n, int H, int W, int Cin, int Cout, int ksize, int stride, int ldo,
-                                                               int io_flags, const float* in_stats, float* out_partial,
-                                                               hipStream_t stream) {
-  MVT_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2));
-  MVT_REQUIRE((!in_stats || Cin <= MAXC) && Cin % CK == 0 && (long long)H * W * Cin < (1LL << 31) && (long long)Cout * ldw < (1LL << 31));
-  MVT_REQUIRE((long long)(TC + 8) * ldo * 4 < (1LL << 31));
-  const int pad = ksize == 3 ? 1 : 0;
-  const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
+int mvt_detail_conv_rows(const mvt_plan::ConvPlan& p, const void* in, const unsigned short* w, const float* bias, void* out, int n, int H,
+                         int W, int Cin, int Cout, int ldo, const float* in_stats, float* out_partial, hipStream_t stream) {
   RowsArgs a{};
   a.in = (const float*)in; a.w = w; a.bias = bias; a.out = (float*)out; a.in_stats = in_stats; a.out_part = out_partial;
-  a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ldw = ldw; a.ldo = ldo;
-  a.slots = mvt_detail_conv_rows_slots(Ho, Wo, mvt_detail_conv_rows_tile_rows(ksize, stride, Ho));
-  a.in_bf16 = io_flags & MVT_IO_IN_BF16 ? 1 : 0;
-  a.out_bf16 = io_flags & MVT_IO_OUT_BF16 ? 1 : 0;
-  // (no dynamic LDS anywhere in this library: every kernel's group segment is its static size, checked at compile time against
-  //  the 160 KiB a workgroup may own -- see DESIGN.md section 5, "a queue abort worth remembering")
-  const bool n96 = Cout % 64 != 0 && Cout % 96 == 0;
-  const int bn = n96 ? 96 : 64;
-  // (64-channel tiles keep three workgroups per CU with bf16 tensors: measured 1.4x faster than 128-channel tiles at one per CU)
-  // bf16 output goes through the LDS-staged epilogue when the tensor allows 16-byte pieces (and the staging tiles fit the patch)
-  const bool st_ok = a.out_bf16 && Cout % 8 == 0 && ldo % 8 == 0 && ((uintptr_t)out & 15) == 0;
-#define LAUNCH2(TM_, TN_, KS_, S_, NW_, INB_)                                                                                       \
-  do {                                                                                                                             \
-    constexpr bool fits = NW_ * stage_elems<TN_>() <= Geo<TM_, KS_, S_, NW_>::NSLOT * LDP;                                          \
-    if (fits && st_ok) hipLaunchKernelGGL((conv_rows_bf16<TM_, TN_, KS_, S_, INB_, NW_, fits>), grid, dim3(64 * NW_), 0, stream, a); \
-    else hipLaunchKernelGGL((conv_rows_bf16<TM_, TN_, KS_, S_, INB_, NW_, false>), grid, dim3(64 * NW_), 0, stream, a);            \
-  } while (0)
-#define LAUNCH(TM_, KS_, S_, NW_)                                                                                                   \
-  do {                                                                                                                             \
-    const long long tiles = (long long)n * mvt_cdiv(Ho, NW_ * TM_) * mvt_cdiv(Wo, TC) * mvt_cdiv(Cout, bn);                        \
-    MVT_REQUIRE(tiles < (1LL << 31));                                                                                              \
-    const dim3 grid((unsigned)tiles);                                                                                              \
-    if (n96) {                                                                                                                     \
-      if (a.in_bf16) LAUNCH2(TM_, 3, KS_, S_, NW_, true);                                                                          \
-      else LAUNCH2(TM_, 3, KS_, S_, NW_, false);                                                                                   \
-    } else {                                                                                                                       \
-      if (a.in_bf16) LAUNCH2(TM_, 2, KS_, S_, NW_, true);                                                                          \
-      else LAUNCH2(TM_, 2, KS_, S_, NW_, false);                                                                                   \
-    }                                                                                                                              \
-  } while (0)
-  const int nw8 = rows_nw8();
-  // wide 3x3 / stride-1 layers without normalise-on-load (conv2): one 512-thread workgroup per 8 x 32 pixel tile and 256-channel
-  // block, LDS-DMA staging (conv3x3_big_bf16).  MVT_CONV_BIG=0 keeps the 64-channel row tiles (read per call: A/B runs, tests)
-  // Its statistics slots are its own 8-row tiles, while a.slots and mvt_conv2d_stat_slots -- by which the caller sized
-  // out_partial -- follow the row tile that MVT_ROWS_NW8 selects: where the two differ (16 rows: slots written past the image's
-  // part of the buffer; 4 rows: slots never written), a launch that takes statistics stays on the row tiles.
-  const bool big_slots_ok = !out_partial || mvt_detail_conv_rows_tile_rows(ksize, stride, Ho) == TR;
-  if (ksize == 3 && stride == 1 && !in_stats && big_slots_ok && !(io_flags & MVT_IO_SHORT_WG) && a.in_bf16 && st_ok && Cout % BG_BN == 0 && ((uintptr_t)in & 15) == 0 && Cin % 8 == 0 &&
-      ldw % 8 == 0 && ((uintptr_t)w & 15) == 0 && (long long)Cout * ldw * 2 < (1LL << 31) && (long long)H * W * Cin * 2 < (1LL << 31)) {
-    const char* e = getenv("MVT_CONV_BIG");
-    if (!e || atoi(e) != 0) {
-      const long long tiles = (long long)n * mvt_cdiv(Ho, TR) * mvt_cdiv(Wo, TC) * (Cout / BG_BN);
-      MVT_REQUIRE(tiles < (1LL << 31));
-      hipLaunchKernelGGL(conv3x3_big_bf16, dim3((unsigned)tiles), dim3(512), 0, stream, a);
-      return mvt_launch_status();
-    }
-  }
-  if (ksize == 3 && stride == 1 && nw8 == 1 && Ho % 16 == 0) LAUNCH(2, 3, 1, 8);
-  else if (ksize == 3 && stride == 1 && nw8 == 2) LAUNCH(1, 3, 1, 4);
-  else if (ksize == 3 && stride == 1) LAUNCH(2, 3, 1, 4);
-  else if (ksize == 3) LAUNCH(1, 3, 2, 4);   // the stride-2 patch is four times larger per output pixel: 4 x 32 pixel tiles
-  else if (stride == 1) LAUNCH(2, 1, 1, 4);
-  else LAUNCH(2, 1, 2, 4);
-#undef LAUNCH2
-#undef LAUNCH
+  a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ldw = p.ldw; a.ldo = ldo;
+  a.slots = p.slots;
+  a.in_bf16 = p.inb;
+  a.out_bf16 = p.out_bf16;
+  if (p.family == mvt_plan::CONV_ROWS) return launch_rows(p, a, stream);
+  MVT_REQUIRE(p.family == mvt_plan::CONV_BIG);
+  hipLaunchKernelGGL(conv3x3_big_bf16, dim3((unsigned)p.grid), dim3(512), 0, stream, a);
   return mvt_launch_status();
 }
 
 // The stride-2 3x3 convolution of a ResidualBlock together with the block's 1x1 / stride-2 downsample branch of the same input
 // (blocks.py:112-128) in ONE launch: the downsample is the centre tap of the 3x3 window with its own weights, so the input patch is
 // staged once, one launch, one InstanceNorm-finish and one full read of the block input fewer per block.
-__attribute__((visibility("hidden"))) int mvt_detail_conv3x3s2_down(const void* in, const unsigned short* w3, int ldw3, const float* b3,
-                                                                    const unsigned short* wd, int ldwd, const float* bd, void* out3,
-                                                                    void* outd, int n, int H, int W, int Cin, int Cout, int ldo,
-                                                                    float* part3, float* partd, hipStream_t stream) {
-  MVT_REQUIRE(in && w3 && wd && out3 && outd && n > 0 && Cin % CK == 0 && Cout % 32 == 0 && Cout % 8 == 0 && ldo % 8 == 0 && ldo >= Cout);
-  MVT_REQUIRE((long long)H * W * Cin < (1LL << 31) && (long long)Cout * ldw3 < (1LL << 31) && ldwd >= Cin && ldw3 >= 9 * Cin);
-  MVT_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)out3 & 15) == 0 && ((uintptr_t)outd & 15) == 0 && ((uintptr_t)w3 & 15) == 0 &&
-              ((uintptr_t)wd & 15) == 0 && ldw3 % 8 == 0 && ldwd % 8 == 0 && (!part3) == (!partd));
-  const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+int mvt_detail_conv3x3s2_down(const mvt_plan::DownPlan& p, const void* in, const unsigned short* w3, const float* b3, const unsigned short* wd,
+                              const float* bd, void* out3, void* outd, int n, int H, int W, int Cin, int Cout, int ldo, float* part3,
+                              float* partd, hipStream_t stream) {
+  MVT_REQUIRE(p.ok);
   RowsArgs a{};
   a.in = (const float*)in; a.w = w3; a.bias = b3; a.out = (float*)out3; a.in_stats = nullptr; a.out_part = part3;
-  a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ldw = ldw3; a.ldo = ldo;
-  a.slots = mvt_detail_conv_rows_slots(Ho, Wo, 4);
+  a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ldw = p.ldw; a.ldo = ldo;
+  a.slots = p.slots;
   a.in_bf16 = 1; a.out_bf16 = 1;
-  a.w2 = wd; a.bias2 = bd; a.out2 = (float*)outd; a.out_part2 = partd; a.ldw2 = ldwd;
-  const bool n96 = Cout % 64 != 0 && Cout % 96 == 0;
-  const long long tiles = (long long)n * mvt_cdiv(Ho, 4) * mvt_cdiv(Wo, TC) * mvt_cdiv(Cout, n96 ? 96 : 64);
-  MVT_REQUIRE(tiles < (1LL << 31));
-  static_assert(4 * stage_elems<2>() <= Geo<1, 3, 2, 4>::NSLOT * LDP && 4 * stage_elems<3>() <= Geo<1, 3, 2, 4>::NSLOT * LDP, "staged epilogue");
-  if (n96) hipLaunchKernelGGL((conv_rows_bf16<1, 3, 3, 2, true, 4, true, true>), dim3((unsigned)tiles), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((conv_rows_bf16<1, 2, 3, 2, true, 4, true, true>), dim3((unsigned)tiles), dim3(256), 0, stream, a);
+  a.w2 = wd; a.bias2 = bd; a.out2 = (float*)outd; a.out_part2 = partd; a.ldw2 = p.ldwd;
+  const dim3 grid((unsigned)p.grid), wg(p.threads);
+  if (p.tn == 3) hipLaunchKernelGGL((conv_rows_bf16<1, 3, 3, 2, true, 4, true, true>), grid, wg, 0, stream, a);
+  else hipLaunchKernelGGL((conv_rows_bf16<1, 2, 3, 2, true, 4, true, true>), grid, wg, 0, stream, a);
   return mvt_launch_status();
 }
 
-// 7x7 stride-2 pad-3 stem with Cin padded to 4 and Cout <= 64 (bf16 mode); the input is either the normalised [n][H][W][4] fp32
-// tensor `in`, or (in == null) the planar clip `rgb` (V,T,3,H,W), fp32 or uint8, images rgb_img0 .. rgb_img0 + n - 1 frame-major
-__attribute__((visibility("hidden"))) int mvt_detail_stem7x7_rows_src(const float* in, const void* rgb, int rgb_u8, int rgb_V, int rgb_T,
-                                                                      long long rgb_img0, const unsigned short* w, int ldw,
-                                                                      const float* bias, void* out, int n, int H, int W, int Cout, int ldo,
-                                                                      int io_flags, float* out_partial, hipStream_t stream);
-__attribute__((visibility("hidden"))) int mvt_detail_stem7x7_rows(const float* in, const unsigned short* w, int ldw, const float* bias,
-                                                                  void* out, int n, int H, int W, int Cout, int ldo, int io_flags,
-                                                                  float* out_partial, hipStream_t stream) {
-  return mvt_detail_stem7x7_rows_src(in, nullptr, 0, 0, 0, 0, w, ldw, bias, out, n, H, W, Cout, ldo, io_flags, out_partial, stream);
-}
-__attribute__((visibility("hidden"))) int mvt_detail_stem7x7_rows_src(const float* in, const void* rgb, int rgb_u8, int rgb_V, int rgb_T,
-                                                                      long long rgb_img0, const unsigned short* w, int ldw,
-                                                                      const float* bias, void* out, int n, int H, int W, int Cout, int ldo,
-                                                                      int io_flags, float* out_partial, hipStream_t stream) {
-  MVT_REQUIRE(Cout > 0 && Cout <= 64 && ldw >= SKW && (long long)H * W * 4 < (1LL << 31) && !(io_flags & MVT_IO_IN_BF16));
-  MVT_REQUIRE((in != nullptr) != (rgb != nullptr));
+// 7x7 stride-2 pad-3 stem with Cin padded to 4 and Cout <= 64 (bf16 mode), from the [n][H][W][4] tensor or from the planar clip
+int mvt_detail_stem7x7_rows_src(const mvt_plan::ConvPlan& p, const float* in, const void* rgb, int rgb_u8, int rgb_V, int rgb_T,
+                                long long rgb_img0, const unsigned short* w, const float* bias, void* out, int n, int H, int W, int Cout,
+                                int ldo, float* out_partial, hipStream_t stream) {
+  MVT_REQUIRE(p.family == mvt_plan::CONV_STEM_ROWS && (in != nullptr) != (rgb != nullptr));
   MVT_REQUIRE(!rgb || (rgb_V > 0 && rgb_T > 0 && rgb_img0 >= 0 && rgb_img0 + n <= (long long)rgb_V * rgb_T && (rgb_u8 == 0 || rgb_u8 == 1)));
-  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   RowsArgs a{};
   a.rgb = rgb; a.rgb_u8 = rgb_u8; a.rgb_V = rgb_V; a.rgb_T = rgb_T; a.rgb_img0 = rgb_img0;
   a.in = in; a.w = w; a.bias = bias; a.out = (float*)out; a.in_stats = nullptr; a.out_part = out_partial;
-  a.H = H; a.W = W; a.Cin = 4; a.Cout = Cout; a.ldw = ldw; a.ldo = ldo;
-  a.slots = mvt_detail_conv_rows_slots(Ho, Wo, TR);
+  a.H = H; a.W = W; a.Cin = 4; a.Cout = Cout; a.ldw = p.ldw; a.ldo = ldo;
+  a.slots = p.slots;
   a.in_bf16 = 0;
-  a.out_bf16 = io_flags & MVT_IO_OUT_BF16 ? 1 : 0;
-  const long long tiles = (long long)n * mvt_cdiv(Ho, TR) * mvt_cdiv(Wo, TC);
-  MVT_REQUIRE(tiles < (1LL << 31) && (long long)(TC + 8) * ldo * 4 < (1LL << 31));
-  const bool st_ok = a.out_bf16 && Cout % 8 == 0 && ldo % 8 == 0 && ((uintptr_t)out & 15) == 0;
-  if (Cout <= 32) {
-    if (st_ok) hipLaunchKernelGGL((stem7x7_rows_bf16<1, true>), dim3((unsigned)tiles), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((stem7x7_rows_bf16<1, false>), dim3((unsigned)tiles), dim3(256), 0, stream, a);
-  } else {
-    if (st_ok) hipLaunchKernelGGL((stem7x7_rows_bf16<2, true>), dim3((unsigned)tiles), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((stem7x7_rows_bf16<2, false>), dim3((unsigned)tiles), dim3(256), 0, stream, a);
+  a.out_bf16 = p.out_bf16;
+  const dim3 grid((unsigned)p.grid), wg(p.threads);
+  switch (p.tn * 10 + (p.staged ? 1 : 0)) {
+    case 11: hipLaunchKernelGGL((stem7x7_rows_bf16<1, true>), grid, wg, 0, stream, a); break;
+    case 10: hipLaunchKernelGGL((stem7x7_rows_bf16<1, false>), grid, wg, 0, stream, a); break;
+    case 21: hipLaunchKernelGGL((stem7x7_rows_bf16<2, true>), grid, wg, 0, stream, a); break;
+    case 20: hipLaunchKernelGGL((stem7x7_rows_bf16<2, false>), grid, wg, 0, stream, a); break;
+    default: return MVT_ERR_ARG;
   }
   return mvt_launch_status();
 }

@@ -5,6 +5,7 @@
 // caller-provided workspace.  bf16 mode, bf16 activations (the configuration bench.py measures).  56 launches per call; beside
 // the tracking windows the half-resolution layers run a few images at a time (group_size below): 12 launches per further group.
 #include "common.h"
+#include "conv_detail.h"
 #include <stdlib.h>
 
 namespace {
@@ -40,14 +41,10 @@ inline Plan plan(long long n, int H, int W, int C) {
   P.d = take(n * hs * ws * 96 * 2);
   P.cat = take(n * hs * ws * 416 * 2);
   P.c2 = take(n * hs * ws * 2 * C * 2);
-  // statistics: per conv n * slots * Cout * 2 floats.  Sized as the 8 x 32 tiles of the H/2 map times the widest launch: conv2
-  // with 2C channels, or the 2 x 128 of a folded launch.  Every launch fits that product, not each factor: with MVT_ROWS_NW8=2
-  // the 64-channel layer 1 has twice the slots (four-row tiles), 2 x 64 <= 256 -- and every later map has at most half the rows,
-  // so its four-row tiles are no more than the H/2 map's eight-row ones.  encoder_run checks every launch against part_floats
-  // before the first one (partials_fit).
-  const long long slots_max = ((h2 + 7) / 8) * ((w2 + 31) / 32);
-  P.st_ch = 2 * C > 256 ? 2 * C : 256;
-  P.part_floats = n * slots_max * P.st_ch * 2;
+  // statistics: per conv n * slots * Cout * 2 floats (conv_plan.h has the sizing rule).  encoder_run checks every launch against
+  // part_floats before the first one (encoder_partials_fit).
+  P.st_ch = mvt_plan::encoder_stat_channels(C);
+  P.part_floats = mvt_plan::encoder_part_floats(n, H, W, C);
   P.part = take(P.part_floats * 4);
   P.st = take(8 * n * P.st_ch * 2 * 4);            // up to 8 live (mean, rstd) tables
   P.total = o;
@@ -86,12 +83,6 @@ extern "C" long long mvt_encoder_workspace_bytes(int n, int H, int W, int C) {
     if (rc_ != MVT_OK) return rc_; \
   } while (0)
 
-int mvt_detail_conv_rows_slots(int Ho, int Wo, int tile_rows);
-int mvt_detail_conv_rows_tile_rows(int ksize, int stride, int Ho);
-int mvt_detail_stem7x7_rows_src(const float* in, const void* rgb, int rgb_u8, int rgb_V, int rgb_T, long long rgb_img0, const unsigned short* w,
-                                int ldw, const float* bias, void* out, int n, int H, int W, int Cout, int ldo, int io_flags, float* out_partial,
-                                hipStream_t stream);
-
 // x4 != null: normalised [n][H][W][4] input; else the planar clip rgb (V,T,3,H,W), images img0 .. img0 + n - 1 frame-major
 static int encoder_run(const mvt_encoder_weights* w, const float* x4, const void* rgb, int rgb_u8, int rgb_V, int rgb_T, long long img0,
                        int n, int H, int W, void* out_rows, int ldo, int out_bf16, void* workspace, long long workspace_bytes, void* stream) {
@@ -111,33 +102,13 @@ static int encoder_run(const mvt_encoder_weights* w, const float* x4, const void
   const int h2 = H / 2, w2 = W / 2;
   int g = n;
   ENC_TRY(group_size(n, h2, w2, w->short_workgroups, &g));
-  static const bool no_fold = getenv("MVT_FOLD_DOWNSAMPLE") && atoi(getenv("MVT_FOLD_DOWNSAMPLE")) == 0;  // (A/B runs)
 
-  // The partial sums of every launch below fit the partials buffer (plan()): n * slots * Cout * 2 floats, twice that where a strided
-  // block's conv1 and downsample[0] share one launch.  Checked here, for the whole sequence, so that a refusal leaves nothing queued.
-  auto partials_fit = [&]() -> bool {
-    auto fits = [&](int slots, int cout, int halves) { return slots > 0 && (long long)halves * n * slots * cout * 2 <= P.part_floats; };
-    auto conv_fits = [&](int hh, int ww, int cin, int cout, int k, int stride, int halves) {
-      return fits(mvt_conv2d_stat_slots(hh, ww, cin, k, k, stride, k / 2, 0), cout, halves);
-    };
-    if (!(x4 ? conv_fits(H, W, 4, 64, 7, 2, 1) : fits(mvt_detail_conv_rows_slots(h2, w2, mvt_detail_conv_rows_tile_rows(7, 2, h2)), 64, 1))) return false;
-    const int couts[4] = {64, 96, 128, 128};
-    int hh = h2, ww = w2, cin = 64;
-    for (int l = 0; l < 4; ++l) {
-      const int cout = couts[l], stride = l ? 2 : 1;
-      if (l && cout % 32 == 0 && !no_fold) {  // (res_block's fold)
-        if (!conv_fits(hh, ww, cin, cout, 3, 2, 2)) return false;
-      } else if (!conv_fits(hh, ww, cin, cout, 3, stride, 1) || (l && !conv_fits(hh, ww, cin, cout, 1, stride, 1))) {
-        return false;
-      }
-      hh = (hh - 1) / stride + 1;
-      ww = (ww - 1) / stride + 1;
-      if (!conv_fits(hh, ww, cout, cout, 3, 1, 1)) return false;  // .0.conv2, .1.conv1, .1.conv2
-      cin = cout;
-    }
-    return conv_fits(H / 4, W / 4, 416, 2 * C, 3, 1, 1);
-  };
-  MVT_REQUIRE(partials_fit());
+  // The network's convolutions, the one table that the launches below take their geometry from.  The partial sums of every launch
+  // fit the partials buffer (plan()): checked here over the same table, for the whole sequence, so that a refusal leaves nothing queued.
+  const mvt_plan::ConvSwitches sw = mvt_detail_conv_switches();
+  mvt_plan::EncConv net[MVT_ENCODER_CONVS];
+  mvt_plan::encoder_convs(H, W, C, sw, net);
+  MVT_REQUIRE(mvt_plan::encoder_partials_fit(net, n, P.part_floats, sw));
 
   // The launches below act on images [ga, ga + gn) of the call.  Every buffer keeps the whole call's layout -- image i owns slice
   // i of each activation buffer, of the partial sums of a launch and of a (mean, rstd) table -- so a group is the same launch
@@ -146,53 +117,39 @@ static int encoder_run(const mvt_encoder_weights* w, const float* x4, const void
   auto img = [&](const void* p, long long bytes_per_image) { return (char*)p + ga * bytes_per_image; };
   auto rows_of = [&](const float* table, int ch) { return table ? table + (long long)ga * ch * 2 : nullptr; };
 
-  // one convolution + the (mean, rstd) of its output; *st_out is the whole call's table
-  auto conv = [&](int ci, const void* in, int io_in, void* out, int hh, int ww, int cin, int cout, int k, int stride, int pad, int ld_out,
-                  const float* in_stats, float** st_out, int io_out) -> int {
+  // convolution ci of the table (+ the (mean, rstd) of its output where st_out is given; *st_out is the whole call's table)
+  auto conv = [&](int ci, const void* in, int io_in, void* out, int ld_out, const float* in_stats, float** st_out, int io_out) -> int {
     const mvt_conv_weights& cw = w->conv[ci];
-    const int ho = (hh + 2 * pad - k) / stride + 1, wo = (ww + 2 * pad - k) / stride + 1;
-    const long long in_img = (long long)hh * ww * cin * (io_in & MVT_IO_IN_BF16 ? 2 : 4);
+    const mvt_plan::EncConv& t = net[ci];
+    const int pad = t.k / 2, ho = mvt_plan::conv_out(t.H, t.k, t.stride, pad), wo = mvt_plan::conv_out(t.W, t.k, t.stride, pad);
+    const long long in_img = (long long)t.H * t.W * t.Cin * (io_in & MVT_IO_IN_BF16 ? 2 : 4);
     const long long out_img = (long long)ho * wo * ld_out * (io_out & MVT_IO_OUT_BF16 ? 2 : 4);
-    float* pp = nullptr;
-    int slots = 0;
-    if (st_out) {
-      slots = mvt_conv2d_stat_slots(hh, ww, cin, k, k, stride, pad, 0);
-      MVT_REQUIRE(slots > 0);
-      pp = part + (long long)ga * slots * cout * 2;
+    const int slots = st_out ? mvt_plan::encoder_slots(t, sw) : 0;
+    float* pp = st_out ? part + (long long)ga * slots * t.Cout * 2 : nullptr;
+    if (ci == 0 && !x4) {
+      // the stem reads the clip's planar frames itself (normalisation on load): no [n][H][W][4] staging tensor, one launch less
+      const mvt_plan::ConvPlan p = mvt_plan::plan_stem(gn, t.H, t.W, t.Cout, ld_out, io_out, ((uintptr_t)img(out, out_img) & 15) == 0);
+      ENC_TRY(mvt_detail_stem7x7_rows_src(p, nullptr, rgb, rgb_u8, rgb_V, rgb_T, img0 + ga, cw.w, cw.b, img(out, out_img), gn, t.H, t.W, t.Cout,
+                                          ld_out, pp, mvt_stream(stream)));
+    } else {
+      ENC_TRY(mvt_conv2d_bf16(img(in, in_img), cw.w, nullptr, cw.b, img(out, out_img), gn, t.H, t.W, t.Cin, t.Cout, t.k, t.k, t.stride, pad, ld_out,
+                              MVT_ACT_NONE, io_in | io_out | (w->short_workgroups ? MVT_IO_SHORT_WG : 0), rows_of(in_stats, t.Cin), pp, stream));
     }
-    ENC_TRY(mvt_conv2d_bf16(img(in, in_img), cw.w, nullptr, cw.b, img(out, out_img), gn, hh, ww, cin, cout, k, k, stride, pad, ld_out,
-                            MVT_ACT_NONE, io_in | io_out | (w->short_workgroups ? MVT_IO_SHORT_WG : 0), rows_of(in_stats, cin), pp, stream));
     if (st_out) {
       *st_out = new_st();
-      ENC_TRY(mvt_instnorm_finish_slots(pp, slots, (float*)rows_of(*st_out, cout), gn, (long long)ho * wo, cout, stream));
+      ENC_TRY(mvt_instnorm_finish_slots(pp, slots, (float*)rows_of(*st_out, t.Cout), gn, (long long)ho * wo, t.Cout, stream));
     }
     return MVT_OK;
   };
 
-  // stem: 7x7 / 2, its InstanceNorm + ReLU is applied by its two consumers (conv1 of layer1.0 and that block's skip)
-  auto stem = [&](float** st_stem) -> int {
-    if (x4) return conv(0, x4, 0, base + P.stem, H, W, 4, 64, 7, 2, 3, 64, nullptr, st_stem, MVT_IO_OUT_BF16);
-    // the stem reads the clip's planar frames itself (normalisation on load): no [n][H][W][4] staging tensor, one launch less
-    const mvt_conv_weights& cw = w->conv[0];
-    const int slots = mvt_detail_conv_rows_slots(h2, w2, mvt_detail_conv_rows_tile_rows(7, 2, h2));
-    float* pp = part + (long long)ga * slots * 64 * 2;
-    // (weight rows as mvt_conv2d_bf16 takes them: [64][round_up(7 * 32, 64)])
-    ENC_TRY(mvt_detail_stem7x7_rows_src(nullptr, rgb, rgb_u8, rgb_V, rgb_T, img0 + ga, cw.w, (7 * 32 + 63) & ~63, cw.b,
-                                        img(base + P.stem, (long long)h2 * w2 * 64 * 2), gn, H, W, 64, 64, MVT_IO_OUT_BF16, pp, mvt_stream(stream)));
-    *st_stem = new_st();
-    return mvt_instnorm_finish_slots(pp, slots, (float*)rows_of(*st_stem, 64), gn, (long long)h2 * w2, 64, stream);
-  };
-
   // ResidualBlock (blocks.py:84-128): conv1 -> IN -> ReLU -> conv2 -> IN -> ReLU, + (downsampled, normalised) input, ReLU
-  auto res_block = [&](int c1, int c2, int cd, const void* xin, const float* x_stats, int hh, int ww, int cin, int cout, int stride,
-                       void* zout) -> int {
-    const int ho = (hh + 2 - 3) / stride + 1, wo = (ww + 2 - 3) / stride + 1;
+  auto res_block = [&](int c1, int c2, int cd, const void* xin, const float* x_stats, void* zout) -> int {
+    const int hh = net[c1].H, ww = net[c1].W, cin = net[c1].Cin, cout = net[c1].Cout, ho = net[c2].H, wo = net[c2].W;
     const long long in_img = (long long)hh * ww * cin * 2, out_img = (long long)ho * wo * cout * 2;
     float *s1 = nullptr, *s2 = nullptr, *sd = nullptr;
-    const bool fold = cd >= 0 && stride == 2 && !x_stats && cout % 32 == 0 && !no_fold;  // conv1 + downsample[0] read the same x: one launch
+    const bool fold = net[c1].with_down;  // conv1 + downsample[0] read the same x: one launch
     if (fold) {
-      const int slots = mvt_conv2d_stat_slots(hh, ww, cin, 3, 3, 2, 1, 0);
-      MVT_REQUIRE(slots > 0);
+      const int slots = mvt_plan::encoder_slots(net[c1], sw);
       float* part_3 = part + (long long)ga * slots * cout * 2;
       float* part_d = part_3 + (long long)n * slots * cout * 2;  // (both halves fit: partials_fit)
       ENC_TRY(mvt_conv3x3s2_down_bf16(img(xin, in_img), w->conv[c1].w, w->conv[c1].b, w->conv[cd].w, w->conv[cd].b, img(base + P.y, out_img),
@@ -202,15 +159,15 @@ static int encoder_run(const mvt_encoder_weights* w, const float* x4, const void
       sd = new_st();
       ENC_TRY(mvt_instnorm_finish_slots(part_d, slots, (float*)rows_of(sd, cout), gn, (long long)ho * wo, cout, stream));
     } else {
-      ENC_TRY(conv(c1, xin, MVT_IO_IN_BF16, base + P.y, hh, ww, cin, cout, 3, stride, 1, cout, x_stats, &s1, MVT_IO_OUT_BF16));
+      ENC_TRY(conv(c1, xin, MVT_IO_IN_BF16, base + P.y, cout, x_stats, &s1, MVT_IO_OUT_BF16));
     }
-    ENC_TRY(conv(c2, base + P.y, MVT_IO_IN_BF16, zout, ho, wo, cout, cout, 3, 1, 1, cout, s1, &s2, MVT_IO_OUT_BF16));
+    ENC_TRY(conv(c2, base + P.y, MVT_IO_IN_BF16, zout, cout, s1, &s2, MVT_IO_OUT_BF16));
     const void* skip = xin;
     long long skip_img = in_img;
     const float* skip_stats = x_stats;
     int flags = BF | (x_stats ? MVT_APPLY_SKIP_RELU : 0);
     if (cd >= 0) {
-      if (!fold) ENC_TRY(conv(cd, xin, MVT_IO_IN_BF16, base + P.d, hh, ww, cin, cout, 1, stride, 0, cout, nullptr, &sd, MVT_IO_OUT_BF16));
+      if (!fold) ENC_TRY(conv(cd, xin, MVT_IO_IN_BF16, base + P.d, cout, nullptr, &sd, MVT_IO_OUT_BF16));
       skip = base + P.d;
       skip_img = out_img;
       skip_stats = sd;
@@ -220,15 +177,12 @@ static int encoder_run(const mvt_encoder_weights* w, const float* x4, const void
                               (long long)ho * wo, cout, flags, stream);
   };
 
-  // conv indices: 0 stem; layer l (1..4): 1 + 5 (l - 1) + {0: .0.conv1, 1: .0.conv2, 2: .0.downsample, 3: .1.conv1, 4: .1.conv2};
-  // 21: conv2 (3x3, 416 -> 2C); 22: conv3 (1x1, 2C -> C)
-  const int couts[4] = {64, 96, 128, 128}, strides[4] = {1, 2, 2, 2};
-  auto layer = [&](int l, const void* xin, const float* xst, int hh, int ww, int cin) -> int {
-    const int b0 = 1 + 5 * l, cout = couts[l], stride = strides[l];
-    ENC_TRY(res_block(b0, b0 + 1, l == 0 ? -1 : b0 + 2, xin, xst, hh, ww, cin, cout, stride, base + P.z0));
-    hh = (hh + 2 - 3) / stride + 1;
-    ww = (ww + 2 - 3) / stride + 1;
-    return res_block(b0 + 3, b0 + 4, -1, base + P.z0, nullptr, hh, ww, cout, cout, 1, base + P.s[l]);
+  // layer l (0..3) = two blocks, convolutions b0 = 1 + 5 l .. b0 + 4 of the table (mvt_plan::encoder_convs has the indices);
+  // only a strided layer's first block has a downsample branch
+  auto layer = [&](int l, const void* xin, const float* xst) -> int {
+    const int b0 = 1 + 5 * l;
+    ENC_TRY(res_block(b0, b0 + 1, l == 0 ? -1 : b0 + 2, xin, xst, base + P.z0));
+    return res_block(b0 + 3, b0 + 4, -1, base + P.z0, nullptr, base + P.s[l]);
   };
 
   // The half-resolution section (stem and layer 1, the largest maps of the network) in groups of g images, up to where s[0] is
@@ -238,23 +192,23 @@ static int encoder_run(const mvt_encoder_weights* w, const float* x4, const void
   for (ga = 0; ga < n; ga += g) {
     gn = n - ga < g ? n - ga : g;
     st_next = 0;
+    // stem: 7x7 / 2, its InstanceNorm + ReLU is applied by its two consumers (conv1 of layer1.0 and that block's skip)
     float* st_stem = nullptr;
-    ENC_TRY(stem(&st_stem));
-    ENC_TRY(layer(0, base + P.stem, st_stem, h2, w2, 64));
+    ENC_TRY(conv(0, x4, 0, base + P.stem, 64, nullptr, &st_stem, MVT_IO_OUT_BF16));
+    ENC_TRY(layer(0, base + P.stem, st_stem));
   }
   ga = 0, gn = n;
-  const void* stage[4] = {base + P.s[0]};
-  int sh[4] = {h2}, sw[4] = {w2}, sc[4] = {64};
-  for (int l = 1; l < 4; ++l) {
-    ENC_TRY(layer(l, base + P.s[l - 1], nullptr, sh[l - 1], sw[l - 1], sc[l - 1]));
-    stage[l] = base + P.s[l]; sh[l] = (sh[l - 1] - 1) / 2 + 1; sw[l] = (sw[l - 1] - 1) / 2 + 1; sc[l] = couts[l];
+  const void* stage[4];
+  int sh[4], swd[4], sc[4];
+  for (int l = 0; l < 4; ++l) {
+    if (l) ENC_TRY(layer(l, base + P.s[l - 1], nullptr));
+    const mvt_plan::EncConv& last = net[1 + 5 * l + 4];  // (3x3 / stride 1: its output has its input's size)
+    stage[l] = base + P.s[l]; sh[l] = last.H; swd[l] = last.W; sc[l] = last.Cout;
   }
-  const int hs = H / 4, ws = W / 4;
-  ENC_TRY(mvt_concat_resize_bilinear_ac(4, stage, sh, sw, sc, base + P.cat, n, hs, ws, 416, BF, stream));
+  ENC_TRY(mvt_concat_resize_bilinear_ac(4, stage, sh, swd, sc, base + P.cat, n, net[21].H, net[21].W, net[21].Cin, BF, stream));
   float* st_c2 = nullptr;
-  ENC_TRY(conv(21, base + P.cat, MVT_IO_IN_BF16, base + P.c2, hs, ws, 416, 2 * C, 3, 1, 1, 2 * C, nullptr, &st_c2, MVT_IO_OUT_BF16));
-  ENC_TRY(conv(22, base + P.c2, MVT_IO_IN_BF16, out_rows, hs, ws, 2 * C, C, 1, 1, 0, ldo, st_c2, nullptr, out_bf16 ? MVT_IO_OUT_BF16 : 0));
-  return MVT_OK;
+  ENC_TRY(conv(21, base + P.cat, MVT_IO_IN_BF16, base + P.c2, 2 * C, nullptr, &st_c2, MVT_IO_OUT_BF16));
+  return conv(22, base + P.c2, MVT_IO_IN_BF16, out_rows, ldo, st_c2, nullptr, out_bf16 ? MVT_IO_OUT_BF16 : 0);
 }
 
 extern "C" int mvt_encoder_forward(const mvt_encoder_weights* w, const float* x4, int n, int H, int W, void* out_rows, int ldo,

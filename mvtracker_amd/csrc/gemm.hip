@@ -14,8 +14,15 @@
 // row stride makes the 16-lane ds_read_b128 groups conflict-free and keeps ds_write_b128 aligned.
 // Global loads for k-tile t+1 are issued into registers before the MFMAs of tile t.
 #include "common.h"
+#include "conv_detail.h"
 
 namespace {
+
+using mvt_plan::BK;    // k-tiles of the fp32 and of the bf16 kernels
+using mvt_plan::BKB;
+using mvt_plan::HT;    // the halo kernel's output tile and channel chunk
+using mvt_plan::HW_;
+using mvt_plan::CK;
 
 struct GemmArgs {
   const float* A;
@@ -44,7 +51,6 @@ struct GemmArgs {
   const float* ln_b;
 };
 
-constexpr int BK = 32;
 constexpr int LDS_LD = BK + 4;
 
 template <int TM, int TN, int WM, int WN>
@@ -220,7 +226,6 @@ __global__ __launch_bounds__(256) void gemm_mfma_f32(GemmArgs p) {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
-constexpr int BKB = 64;
 constexpr int LDB = BKB + 8;  // bf16 elements per LDS row
 
 __device__ __forceinline__ void split4(const f32x4& v, uint2& hi, uint2& lo) {
@@ -489,9 +494,8 @@ __global__ __launch_bounds__(256) void gemm_mfma_bf16(GemmArgs p) {
 // read it back at shifted offsets, so global traffic per MAC drops ~6x and the kernel becomes MFMA-bound.
 // Weights ([Cout][kh][kw][Cin] bf16, row stride ldw) are staged one filter row (3 taps) at a time.
 // Patch / weight rows are 32+8 bf16 (80 B): conflict-free ds_read_b128, 16-B aligned.
-constexpr int HT = 8, HW_ = 16;                 // output tile
-constexpr int PH = HT + 2, PW = HW_ + 2;        // patch
-constexpr int CK = 32, LDC = CK + 8;            // channel chunk, LDS row stride (bf16 elements)
+constexpr int PH = HT + 2, PW = HW_ + 2;        // patch of the HT x HW_ output tile
+constexpr int LDC = CK + 8;                     // LDS row stride of a CK-channel chunk (bf16 elements)
 
 template <int TM, int TN, int WM, int WN, bool SPLIT>
 __global__ __launch_bounds__(256) void conv3x3_halo_bf16(GemmArgs p) {
@@ -700,30 +704,30 @@ __global__ __launch_bounds__(256) void conv3x3_halo_bf16(GemmArgs p) {
   }
 }
 
+// The three launchers below name the instantiations of their kernel family; which one runs, on how many workgroups, is the
+// plan's (mvt_plan::halo_tile, mvt_plan::gemm_tile).
 template <bool SPLIT>
-int launch_conv3x3_halo(const GemmArgs& a, int nimg, hipStream_t s) {
-  const long long tiles = (long long)nimg * mvt_cdiv(a.Ho, HT) * mvt_cdiv(a.Wo, HW_);
-  if (a.N % 128 != 0 && a.N % 96 == 0) {
-    hipLaunchKernelGGL((conv3x3_halo_bf16<1, 3, 4, 1, SPLIT>), dim3((unsigned)(tiles * mvt_cdiv(a.N, 96))), dim3(256), 0, s, a);
-  } else if (a.N <= 64) {
-    hipLaunchKernelGGL((conv3x3_halo_bf16<1, 2, 4, 1, SPLIT>), dim3((unsigned)(tiles * mvt_cdiv(a.N, 64))), dim3(256), 0, s, a);
-  } else {
-    hipLaunchKernelGGL((conv3x3_halo_bf16<2, 2, 2, 2, SPLIT>), dim3((unsigned)(tiles * mvt_cdiv(a.N, 128))), dim3(256), 0, s, a);
+int launch_conv3x3_halo(const mvt_plan::GemmTile& t, const GemmArgs& a, hipStream_t s) {
+  const dim3 grid((unsigned)t.blocks), wg(256);
+  switch (mvt_plan::tile_key(t)) {
+    case 1341: hipLaunchKernelGGL((conv3x3_halo_bf16<1, 3, 4, 1, SPLIT>), grid, wg, 0, s, a); break;
+    case 1241: hipLaunchKernelGGL((conv3x3_halo_bf16<1, 2, 4, 1, SPLIT>), grid, wg, 0, s, a); break;
+    case 2222: hipLaunchKernelGGL((conv3x3_halo_bf16<2, 2, 2, 2, SPLIT>), grid, wg, 0, s, a); break;
+    default: return MVT_ERR_ARG;
   }
   return mvt_launch_status();
 }
 
-inline int pick_tile(const GemmArgs& a);
-
 template <bool SPLIT>
-int launch_gemm_bf16(const GemmArgs& a, hipStream_t s) {
-  auto blocks = [&](int bm, int bn) { return (unsigned)(mvt_cdiv(a.M, bm) * mvt_cdiv(a.N, bn)); };
-  switch (pick_tile(a)) {
-    case 1: hipLaunchKernelGGL((gemm_mfma_bf16<1, 3, 4, 1, SPLIT>), dim3(blocks(128, 96)), dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((gemm_mfma_bf16<2, 2, 4, 1, SPLIT>), dim3(blocks(256, 64)), dim3(256), 0, s, a); break;
-    case 3: hipLaunchKernelGGL((gemm_mfma_bf16<1, 2, 2, 2, SPLIT>), dim3(blocks(64, 128)), dim3(256), 0, s, a); break;
-    case 4: hipLaunchKernelGGL((gemm_mfma_bf16<1, 1, 2, 2, SPLIT>), dim3(blocks(64, 64)), dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL((gemm_mfma_bf16<2, 2, 2, 2, SPLIT>), dim3(blocks(128, 128)), dim3(256), 0, s, a); break;
+int launch_gemm_bf16(const mvt_plan::GemmTile& t, const GemmArgs& a, hipStream_t s) {
+  const dim3 grid((unsigned)t.blocks), wg(256);
+  switch (mvt_plan::tile_key(t)) {
+    case 1341: hipLaunchKernelGGL((gemm_mfma_bf16<1, 3, 4, 1, SPLIT>), grid, wg, 0, s, a); break;  // 128 x 96
+    case 2241: hipLaunchKernelGGL((gemm_mfma_bf16<2, 2, 4, 1, SPLIT>), grid, wg, 0, s, a); break;  // 256 x 64
+    case 1222: hipLaunchKernelGGL((gemm_mfma_bf16<1, 2, 2, 2, SPLIT>), grid, wg, 0, s, a); break;  // 64 x 128
+    case 1122: hipLaunchKernelGGL((gemm_mfma_bf16<1, 1, 2, 2, SPLIT>), grid, wg, 0, s, a); break;  // 64 x 64
+    case 2222: hipLaunchKernelGGL((gemm_mfma_bf16<2, 2, 2, 2, SPLIT>), grid, wg, 0, s, a); break;  // 128 x 128
+    default: return MVT_ERR_ARG;
   }
   return mvt_launch_status();
 }
@@ -738,27 +742,33 @@ __global__ void split_bf16_kernel(const float* __restrict__ src, unsigned short*
   }
 }
 
-// Tile choice: the largest tile that still gives every CU at least two workgroups (latency hiding comes from
-// co-resident blocks); narrow N picks the matching BN so no MFMA columns are wasted.
-inline int pick_tile(const GemmArgs& a) {
-  auto nb = [&](int bm, int bn) { return mvt_cdiv(a.M, bm) * mvt_cdiv(a.N, bn); };
-  if (a.N % 128 != 0 && a.N % 96 == 0) return 1;          // 128 x 96
-  if (a.N <= 64) return nb(256, 64) >= 512 ? 2 : 4;      // 256 x 64, else 64 x 64
-  if (nb(128, 128) >= 512) return 0;                      // 128 x 128
-  if (nb(64, 128) >= 512) return 3;                       // 64 x 128
-  return 4;                                               // 64 x 64
-}
-
-int launch_gemm(const GemmArgs& a, hipStream_t s) {
-  auto blocks = [&](int bm, int bn) { return (unsigned)(mvt_cdiv(a.M, bm) * mvt_cdiv(a.N, bn)); };
-  switch (pick_tile(a)) {
-    case 1: hipLaunchKernelGGL((gemm_mfma_f32<1, 3, 4, 1>), dim3(blocks(128, 96)), dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((gemm_mfma_f32<2, 2, 4, 1>), dim3(blocks(256, 64)), dim3(256), 0, s, a); break;
-    case 3: hipLaunchKernelGGL((gemm_mfma_f32<1, 2, 2, 2>), dim3(blocks(64, 128)), dim3(256), 0, s, a); break;
-    case 4: hipLaunchKernelGGL((gemm_mfma_f32<1, 1, 2, 2>), dim3(blocks(64, 64)), dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL((gemm_mfma_f32<2, 2, 2, 2>), dim3(blocks(128, 128)), dim3(256), 0, s, a); break;
+int launch_gemm(const mvt_plan::GemmTile& t, const GemmArgs& a, hipStream_t s) {
+  const dim3 grid((unsigned)t.blocks), wg(256);
+  switch (mvt_plan::tile_key(t)) {
+    case 1341: hipLaunchKernelGGL((gemm_mfma_f32<1, 3, 4, 1>), grid, wg, 0, s, a); break;
+    case 2241: hipLaunchKernelGGL((gemm_mfma_f32<2, 2, 4, 1>), grid, wg, 0, s, a); break;
+    case 1222: hipLaunchKernelGGL((gemm_mfma_f32<1, 2, 2, 2>), grid, wg, 0, s, a); break;
+    case 1122: hipLaunchKernelGGL((gemm_mfma_f32<1, 1, 2, 2>), grid, wg, 0, s, a); break;
+    case 2222: hipLaunchKernelGGL((gemm_mfma_f32<2, 2, 2, 2>), grid, wg, 0, s, a); break;
+    default: return MVT_ERR_ARG;
   }
   return mvt_launch_status();
+}
+
+// The implicit-GEMM arguments of a convolution call that plan_conv accepted (GEMM and halo families).
+GemmArgs conv_args(const mvt_plan::ConvCall& c, const mvt_plan::ConvPlan& p) {
+  GemmArgs a{};
+  a.Ho = mvt_plan::conv_out(c.H, c.KH, c.stride, c.pad);
+  a.Wo = mvt_plan::conv_out(c.W, c.KW, c.stride, c.pad);
+  a.M = c.n * a.Ho * a.Wo; a.N = c.Cout; a.ldc = c.ldo; a.act = c.act;
+  a.H = c.H; a.Wd = c.W; a.Cin = c.Cin; a.KH = c.KH; a.KW = c.KW; a.stride = c.stride; a.pad = c.pad;
+  a.mode = c.Cin == 4 ? 2 : 1;
+  a.K = c.Cin == 4 ? c.KH * 32 : c.KH * c.KW * c.Cin;
+  a.ldw = p.ldw;  // weights are [Cout][round_up(K, 64)], zero padded
+  a.slots = p.slots;
+  a.a_bf16 = c.io_flags & MVT_IO_IN_BF16 ? 1 : 0;
+  a.c_bf16 = c.io_flags & MVT_IO_OUT_BF16 ? 1 : 0;
+  return a;
 }
 
 }  // namespace
@@ -775,7 +785,7 @@ extern "C" int mvt_gemm(const float* A, int lda, const float* Wt, int ldw, const
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr; a.act = act;
   a.mode = 0;
   a.nk = (K + BK - 1) / BK;
-  return launch_gemm(a, mvt_stream(stream));
+  return launch_gemm(mvt_plan::gemm_tile(M, N), a, mvt_stream(stream));
 }
 
 extern "C" int mvt_conv2d(const float* in, const float* wt, const float* bias, float* out, int n, int H, int W, int Cin,
@@ -783,25 +793,16 @@ extern "C" int mvt_conv2d(const float* in, const float* wt, const float* bias, f
   MVT_REQUIRE(in && wt && out && n > 0 && H > 0 && W > 0 && Cout > 0);
   MVT_REQUIRE(KH >= 1 && KH <= 7 && KW >= 1 && KW <= 7 && stride >= 1 && stride <= 2 && pad >= 0 && pad <= 3);
   MVT_REQUIRE(H < 16384 && W < 16384 && ldo >= Cout && act >= 0 && act <= 3);
-  MVT_REQUIRE((Cin % 32 == 0) || (Cin == 4));
-  MVT_REQUIRE(((uintptr_t)in % 16 == 0) && ((uintptr_t)wt % 16 == 0));
-  const int Ho = (H + 2 * pad - KH) / stride + 1;
-  const int Wo = (W + 2 * pad - KW) / stride + 1;
-  MVT_REQUIRE(Ho > 0 && Wo > 0);
-  const long long M = (long long)n * Ho * Wo;
-  MVT_REQUIRE(M < (1LL << 31));
-  GemmArgs a{};
-  a.A = in; a.W = wt; a.bias = bias; a.R = nullptr; a.C = out;
-  a.M = (int)M; a.N = Cout; a.ldc = ldo; a.ldr = 0; a.act = act;
-  a.H = H; a.Wd = W; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
-  if (Cin == 4) {
-    a.mode = 2; a.nk = KH; a.K = KH * 32;
-  } else {
-    a.mode = 1; a.K = KH * KW * Cin; a.nk = a.K / BK;
-  }
-  a.ldw = (a.K + 63) & ~63;  // weights are [Cout][round_up(K, 64)], zero padded
-  a.lda = 0;
-  return launch_gemm(a, mvt_stream(stream));
+  mvt_plan::ConvCall c{n, H, W, Cin, Cout, KH, KW, stride, pad, ldo, act};
+  c.fp32 = true;
+  c.in_al16 = (uintptr_t)in % 16 == 0;
+  c.w_al16 = (uintptr_t)wt % 16 == 0;
+  const mvt_plan::ConvPlan p = mvt_plan::plan_conv(c, mvt_plan::ConvSwitches{});  // (no switch reaches the fp32 kernels)
+  MVT_REQUIRE(p.family == mvt_plan::CONV_GEMM_F32);
+  GemmArgs a = conv_args(c, p);
+  a.A = in; a.W = wt; a.bias = bias; a.C = out;
+  a.nk = a.mode == 2 ? KH : a.K / BK;
+  return launch_gemm(p.tile, a, mvt_stream(stream));
 }
 
 extern "C" int mvt_split_bf16(const float* src, unsigned short* hi, unsigned short* lo, long long n, void* stream) {
@@ -826,39 +827,22 @@ extern "C" int mvt_gemm_bf16(const float* A, int lda, const unsigned short* Whi,
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr; a.act = act;
   a.mode = 0;
   a.nk = (K + BKB - 1) / BKB;
-  return Wlo ? launch_gemm_bf16<true>(a, mvt_stream(stream)) : launch_gemm_bf16<false>(a, mvt_stream(stream));
+  const mvt_plan::GemmTile t = mvt_plan::gemm_tile(M, N);
+  return Wlo ? launch_gemm_bf16<true>(t, a, mvt_stream(stream)) : launch_gemm_bf16<false>(t, a, mvt_stream(stream));
 }
-
-int mvt_detail_conv_rows_slots(int Ho, int Wo, int tile_rows);
-int mvt_detail_conv_rows_tile_rows(int ksize, int stride, int Ho);
-int mvt_detail_stem7x7_rows(const float* in, const unsigned short* w, int ldw, const float* bias, void* out, int n, int H, int W, int Cout,
-                            int ldo, int io_flags, float* out_partial, hipStream_t stream);
-int mvt_detail_conv_rows(const void* in, const unsigned short* w, int ldw, const float* bias, void* out, int n, int H, int W, int Cin,
-                         int Cout, int ksize, int stride, int ldo, int io_flags, const float* in_stats, float* out_partial,
-                         hipStream_t stream);
 
 extern "C" int mvt_conv2d_stat_slots(int H, int W, int Cin, int KH, int KW, int stride, int pad, int split) {
-  const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-  if (Ho <= 0 || Wo <= 0) return 0;
-  if (!split && Cin % 32 == 0 && KH == KW && ((KH == 3 && pad == 1) || (KH == 1 && pad == 0)) && stride <= 2)
-    return mvt_detail_conv_rows_slots(Ho, Wo, mvt_detail_conv_rows_tile_rows(KH, stride, Ho));  // row-tile kernels: one slot per tile
-  if (KH == 3 && KW == 3 && stride == 1 && pad == 1 && Cin % CK == 0) return (int)(mvt_cdiv(Ho, HT) * mvt_cdiv(Wo, HW_) * 4);
-  if (!split && Cin == 4 && KH == 7 && KW == 7 && stride == 2 && pad == 3)
-    return mvt_detail_conv_rows_slots(Ho, Wo, mvt_detail_conv_rows_tile_rows(7, 2, Ho));  // stem kernel
-  return ((long long)Ho * Wo) % 256 == 0 ? Ho * Wo / 32 : 0;  // im2col tiles are <= 256 rows: they must not straddle images
+  return mvt_plan::conv_stat_slots(H, W, Cin, KH, KW, stride, pad, split != 0, mvt_detail_conv_switches());
 }
 
-int mvt_detail_conv3x3s2_down(const void* in, const unsigned short* w3, int ldw3, const float* b3, const unsigned short* wd, int ldwd,
-                              const float* bd, void* out3, void* outd, int n, int H, int W, int Cin, int Cout, int ldo, float* part3,
-                              float* partd, hipStream_t stream);
 extern "C" int mvt_conv3x3s2_down_bf16(const void* in, const unsigned short* w3, const float* b3, const unsigned short* wd, const float* bd,
                                        void* out3, void* outd, int n, int H, int W, int Cin, int Cout, int ldo, float* part3,
                                        float* partd, void* stream) {
   MVT_REQUIRE(in && w3 && wd && out3 && outd && n > 0 && H > 1 && W > 1 && H < 16384 && W < 16384 && Cin > 0 && Cout > 0);
-  MVT_REQUIRE(Cin % 32 == 0 && Cout % 32 == 0 && (long long)n * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) < (1LL << 31));
-  // (weight rows as mvt_conv2d_bf16 takes them: [Cout][round_up(K, 64)], zero padded)
-  return mvt_detail_conv3x3s2_down(in, w3, (9 * Cin + BKB - 1) / BKB * BKB, b3, wd, (Cin + BKB - 1) / BKB * BKB, bd, out3, outd, n, H, W, Cin,
-                                   Cout, ldo, part3, partd, mvt_stream(stream));
+  const bool al16 = (((uintptr_t)in | (uintptr_t)out3 | (uintptr_t)outd | (uintptr_t)w3 | (uintptr_t)wd) & 15) == 0;
+  const mvt_plan::DownPlan p = mvt_plan::plan_down(n, H, W, Cin, Cout, ldo, (!part3) == (!partd), al16);
+  MVT_REQUIRE(p.ok);
+  return mvt_detail_conv3x3s2_down(p, in, w3, b3, wd, bd, out3, outd, n, H, W, Cin, Cout, ldo, part3, partd, mvt_stream(stream));
 }
 
 extern "C" int mvt_conv2d_bf16(const void* in, const unsigned short* wt_hi, const unsigned short* wt_lo, const float* bias,
@@ -867,46 +851,30 @@ extern "C" int mvt_conv2d_bf16(const void* in, const unsigned short* wt_hi, cons
   MVT_REQUIRE(in && wt_hi && out && n > 0 && H > 0 && W > 0 && Cout > 0);
   MVT_REQUIRE(KH >= 1 && KH <= 7 && KW >= 1 && KW <= 7 && stride >= 1 && stride <= 2 && pad >= 0 && pad <= 3);
   MVT_REQUIRE(H < 16384 && W < 16384 && ldo >= Cout && act >= 0 && act <= 3);
-  MVT_REQUIRE((Cin % 32 == 0) || (Cin == 4));
-  MVT_REQUIRE(((uintptr_t)in % 16 == 0) && ((uintptr_t)wt_hi % 8 == 0) && ((uintptr_t)wt_lo % 8 == 0));
-  const int Ho = (H + 2 * pad - KH) / stride + 1;
-  const int Wo = (W + 2 * pad - KW) / stride + 1;
-  MVT_REQUIRE(Ho > 0 && Wo > 0);
-  const long long M = (long long)n * Ho * Wo;
-  MVT_REQUIRE(M < (1LL << 31));
-  GemmArgs a{};
-  a.A = (const float*)in; a.Whi = wt_hi; a.Wlo = wt_lo; a.bias = bias; a.R = nullptr; a.C = (float*)out;
-  a.M = (int)M; a.N = Cout; a.ldc = ldo; a.ldr = 0; a.act = act;
-  a.H = H; a.Wd = W; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
-  if (Cin == 4) {
-    a.mode = 2; a.K = KH * 32;
-  } else {
-    a.mode = 1; a.K = KH * KW * Cin;
+  mvt_plan::ConvCall c{n, H, W, Cin, Cout, KH, KW, stride, pad, ldo, act, io_flags};
+  c.has_lo = wt_lo != nullptr; c.has_in_stats = in_stats != nullptr; c.has_out_partial = out_partial != nullptr;
+  c.in_al16 = (uintptr_t)in % 16 == 0; c.out_al16 = (uintptr_t)out % 16 == 0; c.stats_al16 = (uintptr_t)in_stats % 16 == 0;
+  c.w_al8 = (uintptr_t)wt_hi % 8 == 0; c.w_al16 = (uintptr_t)wt_hi % 16 == 0; c.lo_al8 = (uintptr_t)wt_lo % 8 == 0;
+  const mvt_plan::ConvPlan p = mvt_plan::plan_conv(c, mvt_detail_conv_switches());
+  hipStream_t s = mvt_stream(stream);
+  switch (p.family) {
+    case mvt_plan::CONV_STEM_ROWS:
+      return mvt_detail_stem7x7_rows_src(p, (const float*)in, nullptr, 0, 0, 0, 0, wt_hi, bias, out, n, H, W, Cout, ldo, out_partial, s);
+    case mvt_plan::CONV_ROWS:
+    case mvt_plan::CONV_BIG:
+      return mvt_detail_conv_rows(p, in, wt_hi, bias, out, n, H, W, Cin, Cout, ldo, in_stats, out_partial, s);
+    case mvt_plan::CONV_HALO:
+    case mvt_plan::CONV_IM2COL: {
+      GemmArgs a = conv_args(c, p);
+      a.A = (const float*)in; a.Whi = wt_hi; a.Wlo = wt_lo; a.bias = bias; a.C = (float*)out;
+      a.nk = (a.K + BKB - 1) / BKB;
+      a.in_stats = in_stats;
+      a.out_part = out_partial;
+      if (p.family == mvt_plan::CONV_HALO) return wt_lo ? launch_conv3x3_halo<true>(p.tile, a, s) : launch_conv3x3_halo<false>(p.tile, a, s);
+      return wt_lo ? launch_gemm_bf16<true>(p.tile, a, s) : launch_gemm_bf16<false>(p.tile, a, s);
+    }
+    default: return MVT_ERR_ARG;
   }
-  a.nk = (a.K + BKB - 1) / BKB;
-  a.ldw = a.nk * BKB;  // weights are [Cout][round_up(K, 64)], zero padded
-  a.lda = 0;
-  const bool halo = KH == 3 && KW == 3 && stride == 1 && pad == 1 && Cin % CK == 0;
-  // bf16 mode: every 3x3 (pad 1) and 1x1 (pad 0) convolution with Cin % 32 == 0 runs on the row-tile kernels (conv_rows.hip)
-  const bool rows = !wt_lo && act == MVT_ACT_NONE && Cin % 32 == 0 && KH == KW && ((KH == 3 && pad == 1) || (KH == 1 && pad == 0));
-  MVT_REQUIRE(!in_stats || ((halo || rows) && ((uintptr_t)in_stats % 16 == 0)));  // normalise-on-load: halo / row-tile kernels only
-  a.in_stats = in_stats;
-  a.out_part = out_partial;
-  a.a_bf16 = io_flags & MVT_IO_IN_BF16 ? 1 : 0;
-  a.c_bf16 = io_flags & MVT_IO_OUT_BF16 ? 1 : 0;
-  MVT_REQUIRE((io_flags & ~(MVT_IO_IN_BF16 | MVT_IO_OUT_BF16 | MVT_IO_SHORT_WG)) == 0);
-  MVT_REQUIRE(!(io_flags & (MVT_IO_IN_BF16 | MVT_IO_OUT_BF16)) || !wt_lo);  // bf16 tensors: bf16 mode only
-  MVT_REQUIRE(!a.a_bf16 || (Cin % 32 == 0 && (uintptr_t)in % 8 == 0));                          // (the stem reads fp32 RGB)
-  a.slots = mvt_conv2d_stat_slots(H, W, Cin, KH, KW, stride, pad, wt_lo != nullptr);
-  MVT_REQUIRE(!out_partial || (a.slots > 0 && (wt_lo || act == MVT_ACT_NONE)));
-  if (!wt_lo && Cin == 4 && KH == 7 && KW == 7 && stride == 2 && pad == 3 && Cout <= 64 && act == MVT_ACT_NONE)
-    return mvt_detail_stem7x7_rows((const float*)in, wt_hi, a.ldw, bias, out, n, H, W, Cout, ldo, io_flags, out_partial, mvt_stream(stream));
-  if (rows)
-    return mvt_detail_conv_rows(in, wt_hi, a.ldw, bias, out, n, H, W, Cin, Cout, KH, stride, ldo, io_flags, in_stats, out_partial,
-                                mvt_stream(stream));
-  if (KH == 3 && KW == 3 && stride == 1 && pad == 1 && Cin % CK == 0 && (long long)n * mvt_cdiv(Ho, HT) * mvt_cdiv(Wo, HW_) * 4 < (1LL << 31))
-    return wt_lo ? launch_conv3x3_halo<true>(a, n, mvt_stream(stream)) : launch_conv3x3_halo<false>(a, n, mvt_stream(stream));
-  return wt_lo ? launch_gemm_bf16<true>(a, mvt_stream(stream)) : launch_gemm_bf16<false>(a, mvt_stream(stream));
 }
 
 extern "C" int mvt_ln_gemm_bf16(const float* A, int lda, const float* ln_w, const float* ln_b, float ln_eps,
@@ -924,5 +892,6 @@ extern "C" int mvt_ln_gemm_bf16(const float* A, int lda, const float* ln_w, cons
   a.mode = 0;
   a.nk = (K + BKB - 1) / BKB;
   a.ln = 1; a.ln_eps = ln_eps; a.ln_w = ln_w; a.ln_b = ln_b;
-  return Wlo ? launch_gemm_bf16<true>(a, mvt_stream(stream)) : launch_gemm_bf16<false>(a, mvt_stream(stream));
+  const mvt_plan::GemmTile t = mvt_plan::gemm_tile(M, N);
+  return Wlo ? launch_gemm_bf16<true>(t, a, mvt_stream(stream)) : launch_gemm_bf16<false>(t, a, mvt_stream(stream));
 }

@@ -49,12 +49,13 @@ switch values as arguments and default to the process's environment, so the slot
 import collections
 import functools
 import os
-import re
 import zlib
 
 import pytest
 import torch
 import torch.nn.functional as F
+
+from test_gpu_matmul_exact import conv_out, env_int, rows_staged_fits, rows_tile  # the one definition of these restatements
 
 gpu = pytest.mark.gpu
 
@@ -194,39 +195,9 @@ def stats_tensor(mean, rstd):
 Conv = collections.namedtuple("Conv", "prec io Cin Cout k s ldo_extra norm big", defaults=(0, False, True))
 
 
-def conv_out(H, W, k, s):
-    p = k // 2
-    return (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
-
-
-def rows_staged_fits(tm, ks, s, nw, tn):
-    """conv_rows.hip LAUNCH2 `fits`: the per-wave staging tiles of the bf16 epilogue fit the patch LDS (Geo<TM, KS, S, NW>)."""
-    rows = nw * tm
-    pr = rows if ks == 1 else s * (rows - 1) + 3
-    pc = 32 if ks == 1 else s * 31 + 3
-    rs = 2 * ((pc + 1) // 2) if (ks == 3 and s == 2) else pc
-    return nw * 32 * (tn * 32 + 8) <= pr * rs * 40
-
-
-def env_int(name):
-    """A once-per-process tuning variable as the library reads it: atoi of the value, 0 when unset."""
-    m = re.match(r"\s*[+-]?\d+", os.environ.get(name, ""))
-    return int(m.group()) if m else 0
-
-
-def rows_tile(k, s, Ho=None, nw8=None):
-    """conv_rows.hip: (TM, NW) of the row-tile kernel for (kernel size, stride) -- NW * TM output rows per workgroup.
-    nw8 = MVT_ROWS_NW8 (default: this process's): 1 = eight waves / 16 rows where Ho % 16 == 0, 2 = TM 1 / four rows.
-    Without Ho (the callers that ask for a case's kernel family, not for a launch) =1 answers for an Ho that is no multiple of 16."""
-    nw8 = env_int("MVT_ROWS_NW8") if nw8 is None else nw8
-    if k == 3 and s == 1:
-        return (2, 8) if (nw8 == 1 and Ho is not None and Ho % 16 == 0) else ((1, 4) if nw8 == 2 else (2, 4))
-    return (1, 4) if (k == 3 and s == 2) else (2, 4)
-
-
 def conv_variant(c, Ho=None, nw8=None):
-    """The kernel mvt_conv2d_bf16 launches for case c (gemm.hip mvt_conv2d_bf16, conv_rows.hip mvt_detail_conv_rows); the row
-    tile, and with it the staged epilogue, follows MVT_ROWS_NW8 (rows_tile)."""
+    """The kernel mvt_conv2d_bf16 launches for case c (conv_plan.h plan_conv); the row tile, and with it the staged epilogue,
+    follows MVT_ROWS_NW8 (rows_tile)."""
     stem = c.Cin == 4
     inb, outb = c.io[0] == "b", c.io[1] == "b"
     ldo = c.Cout + c.ldo_extra
@@ -262,7 +233,7 @@ def epilogue_form(c, Ho=None, nw8=None):
 
 
 def tile_rows(c, Ho=None, nw8=None):
-    """Output rows of one statistics slot (conv_rows.hip mvt_detail_conv_rows_tile_rows): the stem and the big tile keep 8."""
+    """Output rows of one statistics slot (conv_plan.h tile_rows): the stem and the big tile keep 8."""
     if conv_variant(c, Ho, nw8)[0] == "rows":
         tm, nw = rows_tile(c.k, c.s, Ho, nw8)
         return tm * nw
@@ -516,6 +487,31 @@ def test_im2col_refuses_partials_it_cannot_slot(hip):
         hip.conv2d_bf16(guarded(d["x"], torch.float32), hi, lo, d["b"].float().to(DEV), out, N_IMG, 9, 33, 32, 64, 1, 1, 1, 0, 64, out_partial=part)
     torch.cuda.synchronize()
     assert bool(torch.isnan(out).all()) and bool(torch.isnan(part).all())
+
+
+@gpu
+def test_wide_stem_shape_refuses_partials(hip):
+    """The stem shape with more than 64 output channels runs the im2col GEMM kernel, whose slots are 32-pixel blocks, while
+    mvt_conv2d_stat_slots answers the stem's 8 x 32 tiles (conv_plan.h plan_conv: statistics only where the family that runs writes
+    the slots the caller sized by): with out_partial the entry must refuse, not write; without, the call runs."""
+    n, H, W, Cout = N_IMG, 16, 64, 96
+    assert hip.conv2d_stat_slots(H, W, 4, 7, 7, 2, 3) == 1 and (H // 2) * (W // 2) // 32 == 8
+    g = gen("wide-stem")
+    x4 = torch.zeros(n, H, W, 4, dtype=torch.float64)
+    x4[..., :3] = rint(g, -2, 2, n, H, W, 3)
+    wt = torch.zeros(Cout, 7, 8, 4, dtype=torch.float64)
+    wt[:, :, :7, :3] = rint(g, -1, 1, Cout, 7, 7, 3)
+    hi, _ = weights_bf16(hip, wt.reshape(Cout, -1))
+    b = torch.zeros(Cout, device=DEV)
+    M = n * (H // 2) * (W // 2)
+    out, part = poisoned(M * Cout), poisoned(n * 1 * Cout * 2)
+    with pytest.raises(hip.HipError):
+        hip.conv2d_bf16(guarded(x4, torch.float32), hi, None, b, out, n, H, W, 4, Cout, 7, 7, 2, 3, Cout, out_partial=part)
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(out).all()) and bool(torch.isnan(part).all())
+    hip.conv2d_bf16(guarded(x4, torch.float32), hi, None, b, out, n, H, W, 4, Cout, 7, 7, 2, 3, Cout)
+    want = conv_ref(x4[..., :3], wt[:, :, :7, :3], torch.zeros(Cout, dtype=torch.float64), 7, 2)
+    assert_equal(taken(out, M, Cout, Cout, "wide stem shape").reshape(n, H // 2, W // 2, Cout), want, "wide stem shape without statistics")
 
 
 @gpu

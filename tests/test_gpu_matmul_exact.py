@@ -9,8 +9,9 @@ integer, and a dropped, doubled or misplaced product term moves an element by at
 also have to stay at or below 256 (entries in {-1, +1}, K <= 864).  Each test asserts that bound on its own reference before it
 looks at the device.
 
-A. The host dispatch restated (pick_tile, the halo tiles, the branch of mvt_conv2d_bf16, the row-tile variants of conv_rows.hip, the
-   launch forms of mvt_block_fused_bf16 / mvt_ln_proj_bf16): `test_cases_reach_every_variant` asserts that the parametrised shapes
+A. The host dispatch restated (gemm_tile, halo_tile, plan_conv and the row-tile variants of csrc/conv_plan.h, the launch forms of
+   mvt_block_fused_bf16 / mvt_ln_proj_bf16 of csrc/launch_plan.h; test_conv_plan_host.py and test_launch_plan_host.py tie the
+   restatements to the headers on the CPU): `test_cases_reach_every_variant` asserts that the parametrised shapes
    reach every variant the library compiles for these entry points, so a shape that falls back to another variant fails on the CPU.
    (The MVT_ROWS_NW8 / MVT_BLOCK_NMB / MVT_BLOCK_NOSPLIT tuning overrides, which a process reads once from its environment, are
    reached by tests/test_gpu_tuning_switches.py: it runs cases of this file in a child process per value.  The restatements
@@ -63,7 +64,7 @@ def cdiv(a, b):
 
 
 def pick_tile(M, N):
-    """gemm.hip pick_tile: 0 = 128x128, 1 = 128x96, 2 = 256x64, 3 = 64x128, 4 = 64x64."""
+    """conv_plan.h gemm_tile: 0 = 128x128, 1 = 128x96, 2 = 256x64, 3 = 64x128, 4 = 64x64."""
     nb = lambda bm, bn: cdiv(M, bm) * cdiv(N, bn)
     if N % 128 != 0 and N % 96 == 0:
         return 1
@@ -80,7 +81,7 @@ TILE_ROWS = {0: 128, 1: 128, 2: 256, 3: 64, 4: 64}
 
 
 def halo_tile(Cout):
-    """launch_conv3x3_halo: output channels per workgroup (8 x 16 pixels each)."""
+    """conv_plan.h halo_tile: output channels per workgroup (8 x 16 pixels each)."""
     if Cout % 128 != 0 and Cout % 96 == 0:
         return 96
     return 64 if Cout <= 64 else 128
@@ -96,17 +97,18 @@ def env_set(name):
     return name in os.environ
 
 
-def rows_tile(k, s, Ho, nw8=None):
-    """conv_rows.hip: (TM, NW) of the row-tile kernel for (kernel size, stride) -- NW * TM output rows per workgroup.
-    nw8 = MVT_ROWS_NW8 (default: this process's): 1 = eight waves / 16 rows where Ho % 16 == 0, 2 = TM 1 / four rows."""
+def rows_tile(k, s, Ho=None, nw8=None):
+    """conv_plan.h tile_rows: (TM, NW) of the row-tile kernel for (kernel size, stride) -- NW * TM output rows per workgroup.
+    nw8 = MVT_ROWS_NW8 (default: this process's): 1 = eight waves / 16 rows where Ho % 16 == 0, 2 = TM 1 / four rows.
+    Without Ho (the callers that ask for a case's kernel family, not for a launch) =1 answers for an Ho that is no multiple of 16."""
     nw8 = env_int("MVT_ROWS_NW8") if nw8 is None else nw8
     if k == 3 and s == 1:
-        return (2, 8) if (nw8 == 1 and Ho % 16 == 0) else ((1, 4) if nw8 == 2 else (2, 4))
+        return (2, 8) if (nw8 == 1 and Ho is not None and Ho % 16 == 0) else ((1, 4) if nw8 == 2 else (2, 4))
     return (1, 4) if (k == 3 and s == 2) else (2, 4)
 
 
 def rows_staged_fits(tm, ks, s, nw, tn):
-    """conv_rows.hip LAUNCH2 `fits`: the per-wave staging tiles of the bf16 epilogue fit the patch LDS (Geo<TM, KS, S, NW>)."""
+    """conv_plan.h rows_staged_fits: the per-wave staging tiles of the bf16 epilogue fit the patch LDS (patch_slots)."""
     rows = nw * tm
     pr = rows if ks == 1 else s * (rows - 1) + 3
     pc = 32 if ks == 1 else s * 31 + 3

@@ -2,7 +2,8 @@
 
 The library reads a handful of tuning variables as `static const ... = getenv("MVT_...")`, once per process: on the first call of
 the entry that holds the line, or -- the four of the block kernels, which block_fused.hip keeps together in block_switches() -- on
-the first call of any block entry or of the composite updater.  `monkeypatch.setenv` inside the pytest process cannot reach them, and the code behind them -- row tiles of 16 and of 4 output rows,
+the first call of any block entry or of the composite updater, and MVT_ROWS_NW8 / MVT_FOLD_DOWNSAMPLE, which conv_rows.hip keeps in
+conv_switches(), on the first bf16 convolution, slot query or composite encoder call.  `monkeypatch.setenv` inside the pytest process cannot reach them, and the code behind them -- row tiles of 16 and of 4 output rows,
 1 / 2 / 4 / 8 kNN queries per wave on either side of the default, the 64-row block tiles on a few rows and the 32-row ones on many,
 the folded context form at a few hundred tracks, the generic bf16 apply / concat kernels, the unfolded strided blocks of the
 composite encoder -- is what the next change of a threshold or a default puts under production shapes.  The exact suites give
@@ -275,6 +276,14 @@ def only_under(var, *values):
 SLOT_SIZES = [(16, 32), (16, 33), (32, 40), (48, 100), (8, 32), (9, 33), (17, 20), (5, 7)]
 
 
+def switched_slots(H, W, k, s, nw8):
+    """The slots of a row-tile convolution (k, s) of an H x W image under MVT_ROWS_NW8 = 1 or 2: only the 3x3 / stride-1 tile follows
+    the switch (test_conv_plan_host.py holds csrc/conv_plan.h to this on the CPU)."""
+    ho, wo = EN.conv_out(H, W, k, s)
+    rows = (4 if nw8 == 2 else (16 if ho % 16 == 0 else 8)) if (k, s) == (3, 1) else (4 if k == 3 else 8)
+    return cdiv(ho, rows) * cdiv(wo, 32)
+
+
 @gpu
 @only_under("MVT_ROWS_NW8", "1", "2")
 def test_child_stat_slots_follow_rows_nw8(hip):
@@ -284,11 +293,9 @@ def test_child_stat_slots_follow_rows_nw8(hip):
     for H, W in SLOT_SIZES:
         for Cin in (32, 64, 416):
             got = hip.conv2d_stat_slots(H, W, Cin, 3, 3, 1, 1)
-            rows = 4 if nw8 == 2 else (16 if H % 16 == 0 else 8)
-            assert got == cdiv(H, rows) * cdiv(W, 32), (H, W, Cin, got)
-        ho, wo = EN.conv_out(H, W, 3, 2)
-        assert hip.conv2d_stat_slots(H, W, 32, 3, 3, 2, 1) == cdiv(ho, 4) * cdiv(wo, 32)
-        assert hip.conv2d_stat_slots(H, W, 32, 1, 1, 1, 0) == cdiv(H, 8) * cdiv(W, 32)
+            assert got == switched_slots(H, W, 3, 1, nw8), (H, W, Cin, got)
+        assert hip.conv2d_stat_slots(H, W, 32, 3, 3, 2, 1) == switched_slots(H, W, 3, 2, nw8)
+        assert hip.conv2d_stat_slots(H, W, 32, 1, 1, 1, 0) == switched_slots(H, W, 1, 1, nw8)
     assert any(H % 16 == 0 for H, _ in SLOT_SIZES) and any(H % 16 and H % 4 == 0 for H, _ in SLOT_SIZES) and any(H % 4 for H, _ in SLOT_SIZES)
 
 

@@ -13,17 +13,14 @@ around it; the probe runs ONCE over every case below and the tests compare its a
     test comes before any GPU run.
 """
 import itertools
-import os
-import shutil
-import subprocess
 
 import pytest
 
 import test_gpu_attention_forms as AF
 import test_gpu_matmul_exact as MM
 import test_gpu_updater_wiring_exact as UW
+from plan_probe import run_probe
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H = 1024  # the MLP width of the updater's blocks
 
 
@@ -82,17 +79,8 @@ def probe_input():
 @pytest.fixture(scope="module")
 def answers(tmp_path_factory):
     """{tag: [answer lines]} of ONE run of the probe over every case of this module."""
-    cxx = shutil.which("g++") or next((c for c in ("/opt/rocm/llvm/bin/clang++",) if os.path.exists(c)), None)
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = tmp_path_factory.mktemp("launch_plan") / "probe"
-    r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", os.path.join(ROOT, "tests", "launch_plan_probe.cpp"), "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr  # (also: the header needs nothing of HIP)
     cases = probe_input()
-    p = subprocess.run([str(exe)], input="\n".join(line for _, line in cases) + "\n", capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stderr
-    lines = p.stdout.splitlines()
+    lines = run_probe(tmp_path_factory, "launch_plan_probe.cpp", [line for _, line in cases])
     out, at = {}, 0
     for tag, _ in cases:
         k = len(UPD_N) if tag == "upd" else 1
