@@ -301,34 +301,34 @@ class BlockNext(C.Structure):
 BLOCK_MAX_NEXT = 3
 
 
+def _next_array(nexts):
+    """The mvt_block_next array of a list of follow-up projections (the dicts of ``block_fused_bf16``); never zero-sized."""
+    arr = (BlockNext * max(1, len(nexts)))()
+    for i, nx in enumerate(nexts):
+        arr[i] = BlockNext(_ptr(nx["w"]), _ptr(nx["b"]), _ptr(nx.get("lnw")), _ptr(nx.get("lnb")), _ptr(nx["y"]), nx["ldw"], nx["N"],
+                           nx["ldy"], nx["eps"], *nx.get("rows", (0, 0)), 1 if nx["y"].dtype == torch.bfloat16 else 0)
+    return arr
+
+
 def block_fused_bf16(x, ldx, att, ldatt, Ko, wo, ldwo, bo, w1, ldw1, b1, w2, ldw2, b2, H, nexts, M, Cc, ws=None):
     """nexts: list of dicts(w, ldw, b, N, lnw, lnb, eps, y, ldy[, rows=(lo, hi)]) -- at most BLOCK_MAX_NEXT follow-up
     projections; ``rows`` restricts one to a row range (y is always indexed by the global row).  ``ws``: optional fp32
     workspace of (H/256 + 1) * M * Cc elements that lets M <= 2048 run cut over 4x more workgroups."""
     assert ws is None or (ws.dtype == torch.float32 and ws.numel() >= (H // 256 + 1) * M * Cc)
-    arr = (BlockNext * max(1, len(nexts)))()
-    for i, nx in enumerate(nexts):
-        arr[i] = BlockNext(_ptr(nx["w"]), _ptr(nx["b"]), _ptr(nx.get("lnw")), _ptr(nx.get("lnb")), _ptr(nx["y"]), nx["ldw"], nx["N"],
-                           nx["ldy"], nx["eps"], *nx.get("rows", (0, 0)), 1 if nx["y"].dtype == torch.bfloat16 else 0)
+    arr = _next_array(nexts)
     _call("mvt_block_fused_bf16", _ptr(x), ldx, _ptr(att), 1 if (att is not None and att.dtype == torch.bfloat16) else 0, ldatt, Ko, _ptr(wo), ldwo, _ptr(bo), _ptr(w1), ldw1, _ptr(b1), _ptr(w2),
           ldw2, _ptr(b2), H, C.cast(arr, C.c_void_p), len(nexts), M, Cc, _ptr(ws), _stream())
 
 
 def ln_proj_bf16(x, ldx, nexts, M, Cc):
     """LayerNorm + projections of ``nexts`` (same dicts as ``block_fused_bf16``); x is only read."""
-    arr = (BlockNext * len(nexts))()
-    for i, nx in enumerate(nexts):
-        arr[i] = BlockNext(_ptr(nx["w"]), _ptr(nx["b"]), _ptr(nx.get("lnw")), _ptr(nx.get("lnb")), _ptr(nx["y"]), nx["ldw"], nx["N"],
-                           nx["ldy"], nx["eps"], *nx.get("rows", (0, 0)), 1 if nx["y"].dtype == torch.bfloat16 else 0)
+    arr = _next_array(nexts)
     _call("mvt_ln_proj_bf16", _ptr(x), ldx, C.cast(arr, C.c_void_p), len(nexts), M, Cc, _stream())
 
 
 def input_proj_bf16(tokens, ldtok, token_dim, Mp, win, bin_, virtual_tokens, S, x, ldx, nexts, M, Cc):
     """x = [tokens . Win^T + b ; virtual tokens] written, then the LayerNorm + projections of ``nexts`` (one launch)."""
-    arr = (BlockNext * len(nexts))()
-    for i, nx in enumerate(nexts):
-        arr[i] = BlockNext(_ptr(nx["w"]), _ptr(nx["b"]), _ptr(nx.get("lnw")), _ptr(nx.get("lnb")), _ptr(nx["y"]), nx["ldw"], nx["N"],
-                           nx["ldy"], nx["eps"], *nx.get("rows", (0, 0)), 1 if nx["y"].dtype == torch.bfloat16 else 0)
+    arr = _next_array(nexts)
     _call("mvt_input_proj_bf16", _ptr(_f32c(tokens)), ldtok, token_dim, Mp, _ptr(win), _ptr(bin_), _ptr(virtual_tokens), S, _ptr(x), ldx,
           C.cast(arr, C.c_void_p), len(nexts), M, Cc, _stream())
 
@@ -715,10 +715,7 @@ def attn_block_fused_bf16(x, ldx, kind, S, q, ldq, k, v, ldkv, n_keys, wo, bo, w
     assert kind == ATTN_PARTIALS or q.dtype == k.dtype == v.dtype == torch.bfloat16
     assert partials is None or partials.dtype == torch.float32
     at = BlockAttn(kind, S, n_keys, 6, 48, ldq, ldkv, _ptr(q), _ptr(k), _ptr(v), _ptr(partials), n_splits, 1 if defer_pass2 else 0, None)
-    arr = (BlockNext * max(1, len(nexts)))()
-    for i, nx in enumerate(nexts):
-        arr[i] = BlockNext(_ptr(nx["w"]), _ptr(nx["b"]), _ptr(nx.get("lnw")), _ptr(nx.get("lnb")), _ptr(nx["y"]), nx["ldw"], nx["N"],
-                           nx["ldy"], nx["eps"], *nx.get("rows", (0, 0)), 1 if nx["y"].dtype == torch.bfloat16 else 0)
+    arr = _next_array(nexts)
     _call("mvt_attn_block_fused_bf16", _ptr(x), ldx, C.addressof(at), _ptr(wo), _ptr(bo), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), H,
           C.cast(arr, C.c_void_p), len(nexts), M, Cc, _ptr(ws), _stream())
 

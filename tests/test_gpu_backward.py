@@ -9,6 +9,7 @@ pytestmark = pytest.mark.gpu
 
 from mvtracker_amd import hip, synth  # noqa: E402
 from mvtracker_amd.backward import reversed_layout  # noqa: E402
+from mvtracker_amd.frame_store import nseg  # noqa: E402
 from oracle import mvt_oracle as O  # noqa: E402
 
 from test_backward_host import args_of, backward_clip, flip_args, merge, reached_by_reversed  # noqa: E402
@@ -124,7 +125,7 @@ def test_signed_frame_step_equals_flipped_store(model, clips):
             hip.knn_search_levels(lv(idx0, idx1), moved, n, S, fr, step, T, K, seed_k=K)
             res["search_levels_seeded"] = idx1
             # the two-launch forms: per-segment keys, then the merge
-            nsegs = [model._nseg(store["P"][l], K) for l in range(L)]
+            nsegs = [nseg(store["P"][l], K) for l in range(L)]
             keys = [torch.empty(n * S * nsegs[l] * K, device=DEV, dtype=torch.int64) for l in range(L)]
             idx2 = torch.empty_like(idx0)
             lv2 = [dict(d, keys=keys[l], nseg=nsegs[l]) for l, d in enumerate(lv(idx0, idx2))]

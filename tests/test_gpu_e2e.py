@@ -586,8 +586,9 @@ def _query_state(model, a, store, t=0):
     xyz = q[sel, 1:].contiguous()
     n = xyz.shape[0]
     from mvtracker_amd import hip
+    from mvtracker_amd.frame_store import nseg
     P0 = store["P"][0]
-    ns = model._nseg(P0, 1)
+    ns = nseg(P0, 1)
     keys = torch.empty(n * ns, device=DEV, dtype=torch.int64)
     feat = torch.empty(n, model.latent_dim, device=DEV)
     hip.knn_scan(store["xyz"][0], P0, xyz, n, 1, t, 0, store["T"], 1, ns, keys, box=store["box"][0], grid=store["tile_grid"][0])
