@@ -5,6 +5,7 @@ its remote pieces (torch.hub / HuggingFace downloads, Rerun logging, depth estim
     python demo_amd.py --sample-path data_sample.npz --checkpoint mvtracker_200000_june2025.pth --save-npz tracks.npz
     python demo_amd.py --synthetic --precision bf16            # seeded synthetic clip, seeded random weights (no files needed)
     python demo_amd.py --synthetic --query-masks bands --per-mask-tracking --print-masks   # queries per segmented object, tracked apart
+    python demo_amd.py --synthetic --query-masks bands --per-mask-tracking --rigid-motion --print-rigid   # and how every object moved
 
 Mirrors reference demo.py: sample layout :650, 922-929; temporal / spatial subsampling :905-944 (``--temporal_stride``,
 ``--spatial_downsample``); ``--random_query_points`` :967-993 (512 queries drawn from the depth of frame 0 inside a cylinder);
@@ -82,6 +83,16 @@ def build_parser():
     ap.add_argument("--per-mask-tracking", action="store_true",
                     help="track every object's queries as a query set of its own (EvaluationPredictor.forward(query_groups=...))")
     ap.add_argument("--print-masks", action="store_true", help="print the mask query report (matching table, frames, pools, rows)")
+    ap.add_argument("--rigid-motion", action="store_true",
+                    help="fit one rigid pose per object and frame to the tracks on the device (mvtracker_amd.rigid_motion): the objects are "
+                         "those of --query-masks, or one object of all queries; the saved NPZ gains object_poses, rigid_inliers, rigid_status")
+    ap.add_argument("--rigid-threshold", type=float, default=None, metavar="C",
+                    help="a track moves with its object within this distance of where the pose puts it (default 0.02, in the clip's units)")
+    ap.add_argument("--rigid-iterations", type=int, default=None, metavar="K", help="fits per object and frame (default 3)")
+    ap.add_argument("--rigid-min-points", type=int, default=None, metavar="P", help="members a fit needs (default 4)")
+    ap.add_argument("--rigid-fill", action="store_true",
+                    help="put every occluded track point where its object's pose says it is (mvtracker_amd.fill_tracks) before saving")
+    ap.add_argument("--print-rigid", action="store_true", help="print the per-object table of the rigid motion")
     ap.add_argument("--print-motion", action="store_true",
                     help="print the clip's motion report (static share per view and frame, mean frame differences) and its static "
                          "prefix: the leading frames before anything moves (the reference demo's _detect_static_prefix_frames)")
@@ -249,6 +260,21 @@ def query_masks_from_args(args):
         raise SystemExit(str(e)) from None
 
 
+def rigid_motion_from_args(args):
+    """The RigidMotion of --rigid-motion and the --rigid-* flags, or None."""
+    details = (args.rigid_threshold, args.rigid_iterations, args.rigid_min_points)
+    if not args.rigid_motion:
+        if any(d is not None for d in details) or args.rigid_fill or args.print_rigid:
+            raise SystemExit("--rigid-threshold, --rigid-iterations, --rigid-min-points, --rigid-fill and --print-rigid need --rigid-motion")
+        return None
+    from mvtracker_amd import RigidMotion
+    kw = {k: v for k, v in zip(("inlier_threshold", "iterations", "min_points"), details) if v is not None}
+    try:
+        return RigidMotion(live_before_query=bool(args.backward_tracking), **kw)
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+
+
 def mask_labels(args, s):
     """The label map of --query-masks: from the sample NPZ, or (--synthetic) three depth bands per view, numbered from the far band
     in odd views so that the cameras' ids differ."""
@@ -313,6 +339,7 @@ def main():
     track_overlay = track_overlay_from_args(args)
     region, region_poses = query_region_from_args(args, args.temporal_stride)  # (flag errors before any work)
     motion, motion_keep = query_motion_from_args(args)
+    rigid_options = rigid_motion_from_args(args)
     mask_options = query_masks_from_args(args)
     if not torch.cuda.is_available():
         raise SystemExit("demo_amd.py needs an MI355X: the tracker has no CPU path")
@@ -428,6 +455,20 @@ def main():
     n = s["query_points_3d"].shape[1]
     print(f"{'streaming session' if args.streaming else 'predictor call'}: {1e3 * dt:.1f} ms = {T / dt:.1f} frames/s = {n * T / dt:.0f} query-points*frames/s; "
           f"{int(out['vis_e'].sum())} of {out['vis_e'].numel()} track points visible; NaN guard {'TRIPPED' if predictor.last_nan else 'clean'}")
+    if rigid_options is not None:  # after the timed call, from what it returned: the streaming path has the same tracks
+        from mvtracker_amd import fill_tracks, rigid_motion
+        n_q = s["query_points_3d"].shape[1]
+        ids = object_ids if mask_options is not None else torch.zeros(n_q, dtype=torch.int32, device=out["traj_e"].device)
+        tracks, visible = out["traj_e"][0].float().contiguous(), out["vis_e"][0].bool().contiguous()
+        rigid = rigid_motion(tracks, visible, s["query_points_3d"][0, :, 0].to(torch.int32), ids, rigid_options)
+        print("rigid motion:", rigid.summary())
+        if args.print_rigid:
+            print(rigid.table())
+        if args.rigid_fill:
+            filled, where = fill_tracks(tracks, visible, rigid)
+            out["traj_e"] = filled[None]
+            print(f"rigid fill: {int(where.sum())} occluded track points put where their object's pose says they are")
+        s["object_poses"], s["rigid_inliers"], s["rigid_status"] = (x.cpu().numpy() for x in (rigid.poses, rigid.inliers, rigid.status))
     if args.save_npz:
         if keep is not None:
             s["keep"] = keep[0].cpu().numpy()

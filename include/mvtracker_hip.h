@@ -1138,6 +1138,51 @@ int mvt_mask_pool(const unsigned char* labels, const float* depths, const float*
                   int t, int H, int W, float min_depth, float max_depth, float conf_thresh, const int* table, int object, int capacity,
                   float* pool, int* pixel, int* count, int* block_counts, void* stream);
 
+/* ---- rigid object motion (csrc/rigid_motion.hip; mvtracker_amd/rigid.py drives these; DESIGN section 8 "Rigid motion") ----
+ * tracks (T, N, 3) fp32, visibility (T, N) bytes (0 / 1), query_frames (N) int32, object_ids (N) int32: track i belongs to object
+ * object_ids[i] when 0 <= object_ids[i] < G and to none otherwise.  A pose is a row-major 4 x 4 fp32 matrix [R t; 0 0 0 1] that maps
+ * an object's reference configuration (its members' points at its reference frame) to a frame.  All sums are fp64 over a fixed
+ * order (a lane's stride of the member list, then a fixed tree): the same bits in every run, no float atomics; the results of one
+ * (object, frame) depend on that frame's rows and the reference frame's rows only.
+ * Limits: 1 <= T <= 65535, 1 <= N (and M) <= 2^30, 1 <= G <= MVT_RIGID_MAX_OBJECTS; anything else: MVT_ERR_ARG before any launch. */
+#define MVT_RIGID_MAX_OBJECTS 65535
+#define MVT_RIGID_MAX_ITERATIONS 64
+#define MVT_RIGID_OK 0          /* status of an (object, frame): fitted */
+#define MVT_RIGID_TOO_FEW 1     /*   fewer than min_points members with base weight 1 (an object without members: everywhere) */
+#define MVT_RIGID_DEGENERATE 2  /*   the members' reference points are collinear or coincident (see mvt_rigid_fit) */
+#define MVT_RIGID_FILL_OCCLUDED 1 /* mvt_rigid_fill's replace bits */
+#define MVT_RIGID_FILL_OUTLIERS 2
+/* The member lists: counts (G) <- members per object, offsets (G + 1) <- their exclusive prefix, members (N) <- the tracks of object g
+ * at members[offsets[g] .. offsets[g + 1]) in ascending track order, reference_frames (G) <- the largest query frame of the object's
+ * members, clamped to [0, T - 1]; -1 for an object without members.  Count (integer atomics), scan, stable scatter. */
+int mvt_rigid_members(const int* object_ids, const int* query_frames, int N, int G, int T, int* counts, int* offsets, int* members,
+                      int* reference_frames, void* stream);
+/* One workgroup per (object g, frame t), r = reference_frames[g], P_i = tracks[r, i], Q_i = tracks[t, i].  Base weight of member i: 1
+ * when (t >= query_frames[i] or live_before_query) and (not use_visibility or visibility[t, i] and visibility[r, i]) and P_i, Q_i are
+ * finite.  Weighted Kabsch in fp64 (centroids, then the centred moments; the proper rotation that maximises tr(R^T H) as the top
+ * eigenvector of Horn's 4 x 4 matrix), iterations - 1 refits on base and (residual of the previous fit <= inlier_threshold); a refit
+ * that keeps fewer than min_points members, or a degenerate set, is dropped and the previous fit stands.  Degenerate: the
+ * second-largest eigenvalue of the weighted covariance of P, over the weight sum, is below min_spread^2.
+ * poses (G, T, 16), used / inlier_count / status (G, T) int32, rmse (G, T) fp32 (over the inliers), residual (T, N) fp32 and
+ * inliers (T, N) bytes: residual = ||R P + t - Q|| of the fit that stood for every member (NaN where status != 0, and for tracks
+ * of no object), inliers = base and residual <= inlier_threshold. */
+int mvt_rigid_fit(const float* tracks, const unsigned char* visibility, const int* query_frames, const int* object_ids, const int* offsets,
+                  const int* members, const int* reference_frames, int T, int N, int G, double inlier_threshold, int iterations,
+                  int min_points, int use_visibility, double min_spread, int live_before_query, float* poses, float* residual,
+                  unsigned char* inliers, int* used, int* inlier_count, float* rmse, int* status, void* stream);
+/* xf (G, T, 12) fp64 <- rows 0..2 of pose[g, t] (frame < 0) or of pose[g, t] * pose[g, frame]^-1 (0 <= frame < T; the inverse of a
+ * rigid pose is [R^T, -R^T t]), composed in fp64; NaN where status[g, t] != 0 or, with a frame, status[g, frame] != 0. */
+int mvt_rigid_compose(const float* poses, const int* status, int G, int T, int frame, double* xf, void* stream);
+/* out (T, M, 3) fp32 <- xf[point_objects[m], t] applied to points[m] (M, 3) in fp64, rounded once; NaN for a point of no object
+ * (an id outside [0, G)). */
+int mvt_rigid_move(const float* points, const int* point_objects, const double* xf, int M, int T, int G, float* out, void* stream);
+/* out (T, N, 3) <- pose[g, t] * tracks[r_g, i] (fp64, rounded once) and filled (T, N) bytes <- 1 where track i of object g has
+ * status[g, t] == 0, is live (t >= query_frames[i] or live_before_query) and is not visible (MVT_RIGID_FILL_OCCLUDED) or not an
+ * inlier (MVT_RIGID_FILL_OUTLIERS); everywhere else the bits of tracks and 0. */
+int mvt_rigid_fill(const float* tracks, const unsigned char* visibility, const unsigned char* inliers, const int* query_frames,
+                   const int* object_ids, const int* reference_frames, const float* poses, const int* status, int T, int N, int G,
+                   int replace, int live_before_query, float* out, unsigned char* filled, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

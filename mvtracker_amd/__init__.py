@@ -1,6 +1,6 @@
 """MI355X-native multi-view point-tracking forward path (drop-in for mvtracker.models' predictor).
 
-    from mvtracker_amd import MVTracker, EvaluationPredictor, load_mvtracker, sample_queries, auto_scene_normalization, DepthCleaning, clean_depths, CameraAlignment, align_cameras, estimate_normals, voxel_downsample, ReprojectionCheck, reprojection_report, RegionCluster, region_masks, cluster_points, MotionMask, motion_masks, TrackOverlay, render_track_overlays, MaskQueries, mask_queries
+    from mvtracker_amd import MVTracker, EvaluationPredictor, load_mvtracker, sample_queries, auto_scene_normalization, DepthCleaning, clean_depths, CameraAlignment, align_cameras, estimate_normals, voxel_downsample, ReprojectionCheck, reprojection_report, RegionCluster, region_masks, cluster_points, MotionMask, motion_masks, TrackOverlay, render_track_overlays, MaskQueries, mask_queries, RigidMotion, rigid_motion, move_points, fill_tracks
 
 ``synth`` (numpy only) can be imported without the HIP library; everything else loads
 libmvtracker_hip.so on import and raises if it is missing -- there is no CPU fallback.
@@ -13,7 +13,7 @@ __all__ = ["MVTracker", "EvaluationPredictor", "load_mvtracker", "hip", "synth",
            "region_masks", "motion", "MotionMask", "MotionReport", "motion_masks", "overlay", "TrackOverlay", "TrackOverlaySession", "project_tracks",
            "render_track_overlays", "open_track_overlay", "stack_views", "masks", "MaskQueries", "MaskStatistics", "MaskMatching",
            "MaskQueryReport", "labels_from_instances", "mask_statistics", "match_mask_ids", "global_masks", "lift_masks", "mask_queries",
-           "object_colors"]
+           "object_colors", "rigid", "RigidMotion", "RigidMotionResult", "rigid_motion", "move_points", "fill_tracks"]
 
 
 def __getattr__(name):
@@ -57,7 +57,10 @@ def __getattr__(name):
                 "global_masks", "lift_masks", "mask_queries", "object_colors"):
         from . import masks
         return getattr(masks, name)
-    if name in ("hip", "synth", "sample_io", "adapter", "geometry", "parallel", "queries", "scene", "clean", "align", "cloud", "reproject", "cluster", "motion", "overlay", "masks"):
+    if name in ("RigidMotion", "RigidMotionResult", "rigid_motion", "move_points", "fill_tracks"):
+        from . import rigid
+        return getattr(rigid, name)
+    if name in ("hip", "synth", "sample_io", "adapter", "geometry", "parallel", "queries", "scene", "clean", "align", "cloud", "reproject", "cluster", "motion", "overlay", "masks", "rigid"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

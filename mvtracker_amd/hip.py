@@ -141,6 +141,11 @@ SIGNATURES = {
     "mvt_mask_match": [P, I, I, I, C.c_double, I, P, P, P, P, P],
     "mvt_mask_relabel": [P, P, I, I, I, I, P, P],
     "mvt_mask_pool": [P, P, P, P, P, I, I, I, I, I, F, F, F, P, I, I, P, P, P, P, P],
+    "mvt_rigid_members": [P, P, I, I, I, P, P, P, P, P],
+    "mvt_rigid_fit": [P, P, P, P, P, P, P, I, I, I, C.c_double, I, I, I, C.c_double, I, P, P, P, P, P, P, P, P],
+    "mvt_rigid_compose": [P, P, I, I, I, P, P],
+    "mvt_rigid_move": [P, P, P, I, I, I, P, P],
+    "mvt_rigid_fill": [P, P, P, P, P, P, P, P, I, I, I, I, I, P, P, P],
 }
 _RET = {"mvt_build_arch": C.c_char_p, "mvt_encoder_workspace_bytes": C.c_longlong, "mvt_updateformer_workspace_bytes": C.c_longlong,
         "mvt_updateformer_grouped_workspace_bytes": C.c_longlong}
@@ -1361,3 +1366,83 @@ def mask_pool(labels, depths, conf, kinv, einv, V, T, t, H, W, min_depth, max_de
     _call("mvt_mask_pool", _ptr(labels), _ptr(depths), _ptr(conf), _ptr(kinv), _ptr(einv), V, T, t, H, W, min_depth, max_depth,
           0.0 if conf is None else conf_thresh, _ptr(table), obj, capacity, _ptr(pool) if capacity else None, _ptr(pixel) if capacity else None,
           _ptr(count), _ptr(block_counts), _stream())
+
+
+# ------------------------------------------------------------------ rigid object motion (mvtracker_amd/rigid.py drives these)
+RIGID_MAX_OBJECTS, RIGID_MAX_ITERATIONS, RIGID_MAX_FRAMES = 65535, 64, 65535  # MVT_RIGID_*
+RIGID_OK, RIGID_TOO_FEW, RIGID_DEGENERATE = 0, 1, 2
+RIGID_FILL_OCCLUDED, RIGID_FILL_OUTLIERS = 1, 2
+
+
+def _i32(t, n):
+    assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n, (t.dtype, tuple(t.shape), n)
+    return t
+
+
+def _u8(t, n):
+    """(bool and uint8 tensors are both one byte of 0 / 1 per element)"""
+    assert t.dtype in (torch.bool, torch.uint8) and t.is_contiguous() and t.numel() == n, (t.dtype, tuple(t.shape), n)
+    return t
+
+
+def _rigid_dims(T, N, G):
+    assert 1 <= T <= RIGID_MAX_FRAMES and 1 <= N <= 1 << 30 and 1 <= G <= RIGID_MAX_OBJECTS, (T, N, G)
+
+
+def rigid_members(object_ids, query_frames, N, G, T, counts, offsets, members, reference_frames):
+    """counts (G), offsets (G + 1), members (N), reference_frames (G) int32 <- the member lists of the objects 0..G-1 in ascending
+    track order and every object's largest query frame (clamped to the clip; -1 without members)."""
+    _rigid_dims(T, N, G)
+    _i32(object_ids, N), _i32(query_frames, N), _i32(counts, G), _i32(offsets, G + 1), _i32(members, N), _i32(reference_frames, G)
+    _call("mvt_rigid_members", _ptr(object_ids), _ptr(query_frames), N, G, T, _ptr(counts), _ptr(offsets), _ptr(members), _ptr(reference_frames),
+          _stream())
+
+
+def rigid_fit(tracks, visibility, query_frames, object_ids, offsets, members, reference_frames, T, N, G, inlier_threshold, iterations, min_points,
+              use_visibility, min_spread, live_before_query, poses, residual, inliers, used, inlier_count, rmse, status):
+    """poses (G, T, 4, 4) fp32, residual (T, N) fp32, inliers (T, N) bool, used / inlier_count / status (G, T) int32, rmse (G, T) fp32
+    <- the weighted Kabsch fit of every (object, frame) with its inlier refits; tracks (T, N, 3) fp32, visibility (T, N) bool."""
+    _rigid_dims(T, N, G)
+    assert _f32c(tracks).numel() == T * N * 3 and _f32c(poses).numel() == G * T * 16 and _f32c(residual).numel() == T * N
+    assert _f32c(rmse).numel() == G * T
+    _u8(visibility, T * N), _u8(inliers, T * N)
+    _i32(query_frames, N), _i32(object_ids, N), _i32(offsets, G + 1), _i32(members, N), _i32(reference_frames, G)
+    _i32(used, G * T), _i32(inlier_count, G * T), _i32(status, G * T)
+    assert 1 <= iterations <= RIGID_MAX_ITERATIONS and min_points >= 3 and inlier_threshold >= 0 and min_spread >= 0
+    _call("mvt_rigid_fit", _ptr(tracks), _ptr(visibility), _ptr(query_frames), _ptr(object_ids), _ptr(offsets), _ptr(members),
+          _ptr(reference_frames), T, N, G, float(inlier_threshold), iterations, min_points, int(bool(use_visibility)), float(min_spread),
+          int(bool(live_before_query)), _ptr(poses), _ptr(residual), _ptr(inliers), _ptr(used), _ptr(inlier_count), _ptr(rmse), _ptr(status),
+          _stream())
+
+
+def rigid_compose(poses, status, G, T, frame, xf):
+    """xf (G, T, 3, 4) fp64 <- rows 0..2 of pose[g, t] (frame None) or of pose[g, t] pose[g, frame]^-1, NaN where a status it needs is
+    not 0."""
+    _rigid_dims(T, 1, G)
+    assert _f32c(poses).numel() == G * T * 16 and xf.dtype == torch.float64 and xf.is_contiguous() and xf.numel() == G * T * 12
+    _i32(status, G * T)
+    frame = -1 if frame is None else int(frame)
+    assert -1 <= frame < T, frame
+    _call("mvt_rigid_compose", _ptr(poses), _ptr(status), G, T, frame, _ptr(xf), _stream())
+
+
+def rigid_move(points, point_objects, xf, M, T, G, out):
+    """out (T, M, 3) fp32 <- xf[point_objects[m], t] applied to points[m]; NaN for ids outside [0, G)."""
+    _rigid_dims(T, M, G)
+    assert _f32c(points).numel() == M * 3 and _f32c(out).numel() == T * M * 3
+    assert xf.dtype == torch.float64 and xf.is_contiguous() and xf.numel() == G * T * 12
+    _i32(point_objects, M)
+    _call("mvt_rigid_move", _ptr(points), _ptr(point_objects), _ptr(xf), M, T, G, _ptr(out), _stream())
+
+
+def rigid_fill(tracks, visibility, inliers, query_frames, object_ids, reference_frames, poses, status, T, N, G, replace, live_before_query, out,
+               filled):
+    """out (T, N, 3) fp32 <- tracks with the occluded (replace & 1) and / or outlying (replace & 2) points of live members under a
+    status-0 pose replaced by pose * (the member's reference point); filled (T, N) bool <- where."""
+    _rigid_dims(T, N, G)
+    assert _f32c(tracks).numel() == T * N * 3 and _f32c(out).numel() == T * N * 3 and out.data_ptr() != tracks.data_ptr()
+    assert _f32c(poses).numel() == G * T * 16 and 0 <= replace <= 3
+    _u8(visibility, T * N), _u8(inliers, T * N), _u8(filled, T * N)
+    _i32(query_frames, N), _i32(object_ids, N), _i32(reference_frames, G), _i32(status, G * T)
+    _call("mvt_rigid_fill", _ptr(tracks), _ptr(visibility), _ptr(inliers), _ptr(query_frames), _ptr(object_ids), _ptr(reference_frames),
+          _ptr(poses), _ptr(status), T, N, G, replace, int(bool(live_before_query)), _ptr(out), _ptr(filled), _stream())

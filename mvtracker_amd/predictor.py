@@ -168,6 +168,7 @@ class EvaluationPredictor(torch.nn.Module):
         # the ReprojectionReport of the cameras the last forward tracked with, and of the uncorrected ones when it also aligned them
         self.last_reprojection_report = self.last_reprojection_report_before = None
         self.last_track_overlay = None  # (video (V,T,3,Hp,Wp) uint8, colors (N,3) uint8) of the last forward with track_overlay
+        self.last_rigid_motion = None  # the RigidMotionResult of the last forward with rigid_motion
         self.model.eval()
 
     # ---- helpers -------------------------------------------------------------------------
@@ -408,9 +409,16 @@ class EvaluationPredictor(torch.nn.Module):
             reprojection_check=None,
             track_overlay=None,
             query_groups=None,
+            rigid_motion=None,
             **kwargs,
     ):
-        """``query_groups``: (N,) integers, one per query (``mask_queries``' ``object_ids``): in joint mode the queries of every
+        """``rigid_motion``: a ``RigidMotion``: after the tracking, one rigid pose per object and frame is fitted to the tracks on the
+        device (``mvtracker_amd.rigid_motion``) and the result is kept as ``last_rigid_motion`` (reset to None by every forward).  The
+        objects are the ids of ``query_groups``; without ``query_groups`` every query belongs to object 0.  It runs on the caller's
+        rows only (no support point takes part), in the caller's world (after the scene normalisation is undone), with the
+        thresholded ``vis_e`` and the query frames of ``query_points_3d[..., 0]``.  Nothing the tracker reads is changed.  None: not
+        one launch.
+        ``query_groups``: (N,) integers, one per query (``mask_queries``' ``object_ids``): in joint mode the queries of every
         distinct id, in ascending id order, are a query set of their own -- [its queries; the support rows] -- and all sets go
         through ``MVTracker.forward_grouped``: per-object independent tracking in one encoder pass and one launch sequence, the
         results scattered back to the caller's rows.  Refused with ``single_point``, ``backward_tracking`` and a model without
@@ -452,6 +460,10 @@ class EvaluationPredictor(torch.nn.Module):
         if track_overlay is not None:  # checked before anything is launched; drawn after the tracking
             from . import overlay
             overlay._check(track_overlay)
+        self.last_rigid_motion = None
+        if rigid_motion is not None:  # checked before anything is launched; fitted after the tracking
+            from . import rigid
+            rigid._check(rigid_motion)
         caller_rgbs, caller_query_frames = rgbs, query_points_3d[0, :, 0]  # the overlay is drawn on the caller's own frames
         # the clip stages, in the order the docstring promises; everything up to the resize works on the raw-resolution clip
         rgbs, depths, intrs, extrs = _cast(rgbs, depths, intrs, extrs, self.interp_shape)
@@ -490,7 +502,23 @@ class EvaluationPredictor(torch.nn.Module):
         if track_overlay is not None:
             self.last_track_overlay = overlay.render_track_overlays(caller_rgbs[0], traj_e[0], vis_e[0] > self.visibility_threshold, caller_query_frames,
                                                                     caller_intrs[0], caller_extrs[0], track_overlay)
+        if rigid_motion is not None:
+            self.last_rigid_motion = self._rigid_motion(traj_e[0], vis_e[0] > self.visibility_threshold, caller_query_frames, query_groups,
+                                                        rigid_motion)
         return {"traj_e": traj_e, "vis_e": vis_e > self.visibility_threshold, "vis_e_as_prob": vis_e}
+
+    @staticmethod
+    def _rigid_motion(tracks, visible, query_frames, query_groups, options):
+        """The poses of the caller's rows: the objects are ``query_groups``' ids (their number is known from the host copy
+        ``_query_groups`` already took, so nothing is read back here), or object 0 for every row."""
+        from . import rigid
+        n, dev = tracks.shape[1], tracks.device
+        if query_groups is None:
+            ids, num = torch.zeros(n, dtype=torch.int32, device=dev), 1
+        else:
+            host = torch.as_tensor(query_groups).cpu()
+            ids, num = host.to(torch.int32).to(dev), max(int(host.max()) + 1, 0)
+        return rigid.rigid_motion(tracks.contiguous(), visible.contiguous(), query_frames.to(torch.int32), ids, options, num_objects=num)
 
     @staticmethod
     def sample_queries(depths, intrs, extrs, spec=None, **kw):

@@ -76,4 +76,7 @@ def save_result(path: str, traj_e: torch.Tensor, vis_e: torch.Tensor, sample: Di
         data["keep"] = np.asarray(sample["keep"])
     if "camera_corrections" in sample:  # the camera alignment's per-view transforms (V,4,4), when the demo aligned the cameras
         data["camera_corrections"] = np.asarray(sample["camera_corrections"])
+    for k in ("object_poses", "rigid_inliers", "rigid_status"):  # the rigid motion (G,T,4,4), (T,N), (G,T), when the demo fitted it
+        if k in sample:
+            data[k] = np.asarray(sample[k])
     np.savez_compressed(path, **data)
