@@ -806,17 +806,19 @@ def updateformer_forward_tokens_grouped(weights: UpdaterWeights, coords, fcorr, 
 POOL_RADIUS_INCLUSIVE = 1  # MVT_POOL_RADIUS_INCLUSIVE
 KMEANS_MAX_K, KMEANS_MAX_CAND, KMEANS_SEED_BLOCKS, KMEANS_STAT_BLOCKS = 4096, 10, 4096, 1024
 KM_LO, KM_HI, KM_SCALE, KM_SCALE2, KM_TOL, KM_ITER, KM_CONVERGED, KM_EMPTY, KM_INERTIA, KM_SHIFT, KM_POT, KM_WORDS = 0, 3, 6, 7, 8, 9, 10, 11, 12, 14, 15, 32
+KM_INERTIA_ACC, KM_CAND = 13, 16  # the running fixed-point inertia; KMEANS_MAX_CAND candidate indices of the running seeding step
 
 
 def query_pool(depths, conf, kinv, einv, V, T, t, H, W, conf_threshold, x0, y0, radius_sq, z_min, z_max, pool, count, block_counts,
-               radius_inclusive=False):
-    """Candidate pool of frame t of the clip depths (V,T,1,H,W) [conf: the same layout or None] -> pool (V*H*W,3), count (1,) int32."""
+               radius_inclusive=False, flags=None):
+    """Candidate pool of frame t of the clip depths (V,T,1,H,W) [conf: the same layout or None] -> pool (V*H*W,3), count (1,) int32.
+    ``flags``: the raw MVT_POOL_* word in place of ``radius_inclusive``."""
     assert depths.is_contiguous() and depths.dtype == torch.float32 and depths.numel() == V * T * H * W
     assert conf is None or (conf.is_contiguous() and conf.dtype == torch.float32 and conf.numel() == V * T * H * W)
     assert pool.dtype == torch.float32 and pool.numel() >= V * H * W * 3 and count.dtype == torch.int32
     assert block_counts.dtype == torch.int32 and block_counts.numel() >= (V * H * W + 255) // 256
     _call("mvt_query_pool", _ptr(depths), _ptr(conf), _ptr(_f32c(kinv)), _ptr(_f32c(einv)), V, T, t, H, W, conf_threshold, x0, y0, radius_sq,
-          z_min, z_max, POOL_RADIUS_INCLUSIVE if radius_inclusive else 0, _ptr(pool), _ptr(count), _ptr(block_counts), _stream())
+          z_min, z_max, (POOL_RADIUS_INCLUSIVE if radius_inclusive else 0) if flags is None else int(flags), _ptr(pool), _ptr(count), _ptr(block_counts), _stream())
 
 
 def _km_check(pts, M, state):

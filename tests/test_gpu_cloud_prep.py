@@ -253,6 +253,27 @@ def test_voxels_are_exact_on_dyadic_clouds(name):
         assert name == "one" or (on_face > 0 and got["counts"].max() > 1)
 
 
+@pytest.mark.parametrize("P,nb", [(65700, 257), (179000, 700)])
+def test_voxels_of_more_than_256_workgroups(P, nb):
+    """More than 65 536 points: every thread of mvt_voxel_emit's one-workgroup scan owns a chunk of 2 (257 workgroups) or 3 (700: the
+    last chunk partial) counts.  A dyadic cloud (multiples of 1/8) in a box that grows in steps with the index, so that cells are
+    repeated many times and first points of new voxels still appear in late workgroups, with whole workgroups between them that emit
+    nothing."""
+    assert (P + 255) // 256 == nb
+    rng = np.random.default_rng(P)
+    limit = 16 + 4 * ((np.arange(P) * 8) // P)  # coordinates below 2, 2.5, .. 5.5 (in eighths): the box grows by a cell eight times
+    pts = (np.floor(rng.random((P, 3)) * limit[:, None]) / 8.0).astype(np.float32)
+    pts[::1001] = np.nan  # rows that take no part
+    r, got = R.voxel(pts, 0.5), device_voxel(pts, 0.5)
+    per = np.bincount(r["first"] // 256, minlength=nb)
+    print(f"{P} points, {nb} workgroups -> {len(got['counts'])} voxels (ref {len(r['counts'])}), largest {int(r['counts'].max())}, "
+          f"{int((per == 0).sum())} workgroups emit nothing, the last one that emits: {int(np.flatnonzero(per)[-1])}")
+    assert got["points"].shape == (len(r["counts"]), 3) and len(r["counts"]) > 1000  # n_out
+    assert np.array_equal(got["counts"], r["counts"]) and np.array_equal(got["first"], r["first"]) and np.array_equal(got["labels"], r["labels"])
+    assert np.array_equal(got["points"].view(np.uint32), r["points"].view(np.uint32))
+    assert r["counts"].max() > 20 and (per == 0).sum() > 10 and np.flatnonzero(per)[-1] > nb // 2 and (np.diff(per.nonzero()[0]) > 1).any()
+
+
 @pytest.mark.parametrize("voxel_size", [0.05, 0.2])
 def test_voxels_on_a_rendered_cloud(planted, voxel_size):
     pts = planted["moved"][:, 0].reshape(-1, 3).astype(np.float32)

@@ -188,6 +188,35 @@ def test_lift_several_objects(clip):
     assert all(torch.equal(a, b) for a, b in zip(again, (pts, oid, pix)))
 
 
+@pytest.mark.parametrize("h,w,nb", [(241, 272, 257), (399, 449, 700)])
+def test_pool_of_more_than_256_workgroups(h, w, nb):
+    """More than 65 536 pixels: every thread of mvt_mask_pool's one-workgroup scan owns a chunk of 2 (257 workgroups) or 3 (700: the
+    last chunk partial) counts.  The object covers a hashed half of the pixels, with runs of whole workgroups empty in the middle and
+    at the end; the scene's unprojection is exact in fp32, so the points are compared for equality."""
+    from mvtracker_amd import lift_masks, mask_statistics, match_mask_ids
+    depths, intrs, extrs = R.exact_scene(1, 2, h, w, seed=nb)
+    n = h * w
+    assert (n + 255) // 256 == nb
+    i = np.arange(n, dtype=np.uint64)
+    blk = (i // 256).astype(np.int64)
+    on = (((i * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(40)) & np.uint64(1) == 1) & ~((blk >= nb // 3) & (blk < nb // 3 + 7)) & (blk < nb - 5)
+    lab = np.zeros((1, 2, h, w), np.uint8)
+    lab[0, 1] = on.reshape(h, w)
+    lab[0, 0, :3] = 1  # (frame 0 is not the frame read)
+    o = dict(match=False)
+    args = api_args(lab, depths, intrs, extrs)
+    mt = match_mask_ids(mask_statistics(*args, opts(**o)), opts(**o))
+    gid = mt.global_id.cpu().numpy()
+    assert gid[0][1] == 0
+    idx, ref = R.object_pool(lab, depths, intrs, extrs, R.options(**o), gid, 0, 1)
+    per = np.bincount(idx // 256, minlength=nb)
+    print(f"{h} x {w}: {nb} workgroups, pool {len(idx)} of {n}, {int((per == 0).sum())} workgroups empty")
+    assert np.array_equal(idx, np.flatnonzero(on)) and 0.4 * n < len(idx) < 0.55 * n and (per == 0).sum() == 12
+    pts, oid, pix = lift_masks(*args, 1, matching=mt, options=opts(**o))
+    assert pts.shape == (len(idx), 3) and np.array_equal(pix.cpu().numpy(), idx) and not oid.any()  # count, pixel
+    assert np.array_equal(pts.cpu().numpy(), ref)
+
+
 # ------------------------------------------------------------------------------------------------------------------ matching
 def _all(frames, rect):
     return {t: rect for t in frames}
